@@ -16,7 +16,6 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # before anything initialises HIP: see ptudes-lab_amd/_lib.py
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")  # cpu_baseline's OpenMP pass: idle threads must not burn the cgroup quota
 
 import numpy as np  # noqa: E402
@@ -30,6 +29,8 @@ PARITY_EXTRA_SEQS = 8     # sequences beside sequence 0 whose trajectories are c
 PARITY_EXTRA_SWEEPS = 40  # ... over their first sweeps
 DEFAULT_REPEATS = 3       # timed repeats of the K steps (>= 3, the median is reported)
 GATHER_TIMEOUT_S = 120
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20251015  # --dump-outputs: fixed generator of the sequence sample when all of them do not fit
 CPU_MIN_SWEEPS = 300  # sweeps offered to the CPU baseline (it stops at its time budget)
 HBM_PEAK = 8.0e12  # B/s, MI355X spec (/opt/skills/guides/MI355X_MICROARCH.md)
 HBM_COPY_RATE = 6.29e12  # B/s a streaming copy reaches on MI355X (same guide)
@@ -211,6 +212,33 @@ def upstream_kiss_leg(seq, n, budget_s, kiss_oracle):
     return {"available": True, "kind": f"upstream kiss-icp {ver}", "value": done / spent, "unit": "scans/s", "sweeps": done,
             "mode": "ICP only, constant-velocity guess (reference kiss.py:102-105)",
             "poses_last": np.asarray(icp.poses[-1]).tolist()}
+
+
+def dump_outputs(outdir, outs, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what the timed path handed back after its last step - per sequence the runner's results(j) - as float64 .npy files
+    in outdir: kiss_poses (S', T', 4, 4), res_poses (S', T', 4, 4) and res_t (S', T') when the filter runs, stats (S', T', 12: the
+    IcpStats fields in declaration order), and the sequence / scan indices the rows belong to.  When all S x T rows exceed max_bytes,
+    the last T' scans (the last step included) of a fixed, seeded sample of S' sequences are written.  Returns the written names."""
+    fields = list(outs[0]["stats"][0])
+    arrays = {"kiss_poses": [o["kiss_poses"] for o in outs],
+              "stats": [np.array([[s[k] for k in fields] for s in o["stats"]], dtype=np.float64) for o in outs]}
+    if "res_poses" in outs[0]:
+        arrays["res_poses"] = [o["res_poses"] for o in outs]
+        arrays["res_t"] = [o["res_t"] for o in outs]
+    S, T = len(outs), len(outs[0]["kiss_poses"])
+    row_bytes = 8 * sum(int(np.prod(v[0].shape[1:])) for v in arrays.values())
+    budget = max_bytes - 4096  # (the .npy headers)
+    t_keep = max(1, min(T, (budget - 16) // (row_bytes + 8)))
+    s_keep = max(1, min(S, (budget - 8 * t_keep) // (8 + t_keep * row_bytes)))
+    pick = np.arange(S) if s_keep == S else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(S, size=s_keep, replace=False))
+    rows = np.arange(T - t_keep, T)
+    os.makedirs(outdir, exist_ok=True)
+    written = {"sequence": pick.astype(np.float64), "scan": rows.astype(np.float64)}
+    for name, per_seq in arrays.items():
+        written[name] = np.ascontiguousarray(np.stack([np.asarray(per_seq[j], dtype=np.float64)[T - t_keep:] for j in pick]))
+    for name, a in written.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return sorted(written)
 
 
 def _free_port():
@@ -455,6 +483,10 @@ def main():
                     help="skip the extra figure of the default line: sequence 0 alone through the single-sequence latency pipeline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--dump-traj", type=str, default="", help="rank 0 writes the gathered (T, 8) NC-GT rows of every sequence to this .npz")
+    ap.add_argument("--dump-outputs", type=str, default="",
+                    help="after the timed steps rank 0 writes what the timed path returned for its sequences after the last step (poses, "
+                         "filter times, per-scan statistics) as float64 DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample "
+                         "of the sequences beyond that): two builds run with the same arguments compare output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -660,6 +692,8 @@ def main():
 
     # per-rank accounting
     outs = [runner.results(j) for j in range(S)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
     gn_ms, gn_n = runner.profile(enable=False)
     gn_bytes, gn_bytes_all, b_scan = 0.0, 0.0, 0.0
     iters = []

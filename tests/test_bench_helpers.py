@@ -182,3 +182,57 @@ def test_pmc_summary_takes_the_timed_launches_of_the_dominant_kernel(tmp_path):
     assert r["FETCH_SIZE_timed"] == {"launches": 1, "mean_per_launch_KB": 100.0}
     assert r["traffic_bytes_per_launch"] == 2 * 100.0 * 1024 + 40.0 * 1024
     assert r["traffic_bytes_per_scan"] == (2 * 100.0 * 1024 + 40.0 * 1024) / 9600.0
+
+
+def _fake_outs(S, T, with_ekf=True):
+    rng = np.random.default_rng(S * 1000 + T)
+    keys = ("sigma", "err_dt", "err_drot", "iterations", "n_corr_last", "n_in", "n_valid", "n_down", "n_src", "sum_cand",
+            "map_voxels", "map_points")
+    outs = []
+    for _ in range(S):
+        o = {"kiss_poses": rng.standard_normal((T, 4, 4)),
+             "stats": [{k: (float(rng.random()) if i < 3 else int(rng.integers(0, 1 << 20))) for i, k in enumerate(keys)} for _ in range(T)]}
+        if with_ekf:
+            o.update(res_poses=rng.standard_normal((T, 4, 4)), res_t=rng.random(T))
+        outs.append(o)
+    return outs
+
+
+def test_dump_outputs_writes_what_the_runner_returned(tmp_path):
+    """--dump-outputs: every sequence's results as float64 .npy files when they fit, the filter's arrays only when it runs"""
+    b = _bench()
+    outs = _fake_outs(5, 7)
+    names = b.dump_outputs(str(tmp_path / "d"), outs)
+    assert names == ["kiss_poses", "res_poses", "res_t", "scan", "sequence", "stats"]
+    got = {n: np.load(tmp_path / "d" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["sequence"], np.arange(5.0)) and np.array_equal(got["scan"], np.arange(7.0))
+    assert np.array_equal(got["kiss_poses"], np.stack([o["kiss_poses"] for o in outs]))
+    assert np.array_equal(got["res_poses"], np.stack([o["res_poses"] for o in outs]))
+    assert np.array_equal(got["res_t"], np.stack([o["res_t"] for o in outs]))
+    assert got["stats"].shape == (5, 7, 12) and got["stats"][2, 3, 3] == outs[2]["stats"][3]["iterations"]
+    assert got["stats"][4, 6, 11] == outs[4]["stats"][6]["map_points"]
+    assert b.dump_outputs(str(tmp_path / "icp"), _fake_outs(2, 3, with_ekf=False)) == ["kiss_poses", "scan", "sequence", "stats"]
+
+
+def test_dump_outputs_samples_a_fixed_subset_within_the_size_cap(tmp_path):
+    """beyond the cap: the last scans (the last step's among them) of a seeded sample of sequences, the same sample every time"""
+    b = _bench()
+    outs = _fake_outs(40, 30)
+    cap = 64 << 10
+    for d in ("a", "c"):
+        b.dump_outputs(str(tmp_path / d), outs, max_bytes=cap)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= cap
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "c" / f))
+    seqs, scans = np.load(tmp_path / "a" / "sequence.npy"), np.load(tmp_path / "a" / "scan.npy")
+    assert 1 <= len(seqs) < 40 and len(set(seqs)) == len(seqs) and np.all(np.diff(seqs) > 0)
+    assert np.array_equal(scans, np.arange(30.0))
+    kp = np.load(tmp_path / "a" / "kiss_poses.npy")
+    assert np.array_equal(kp, np.stack([outs[int(j)]["kiss_poses"] for j in seqs]))
+    # one sequence larger than the cap: its last scans alone
+    b.dump_outputs(str(tmp_path / "t"), _fake_outs(3, 400), max_bytes=cap)
+    scans = np.load(tmp_path / "t" / "scan.npy")
+    assert len(np.load(tmp_path / "t" / "sequence.npy")) == 1 and 1 <= len(scans) < 400 and scans[-1] == 399
+    assert sum(os.path.getsize(tmp_path / "t" / f) for f in os.listdir(tmp_path / "t")) <= cap

@@ -267,3 +267,27 @@ def test_icp_only_ranks_gather_the_registrations_own_poses(tmp_path):
     assert g["sequences"] == 16 and g["rows_each"] == [9] and "RCCL" in g["backend"] and "FALLBACK" not in g["backend"], g
     rows = np.load(dump1)["rank0_seq3"]
     assert np.array_equal(rows[:, 0], np.arange(9.0)) and abs(np.linalg.norm(rows[-1, 4:8]) - 1.0) < 1e-12
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_paths_results_and_repeat_exactly(tmp_path):
+    """`--dump-outputs DIR`: after exactly --steps timed steps the batch's results land in DIR as float64 .npy files, and a second run
+    with the same arguments writes the same arrays bit for bit (same seeded inputs, deterministic path)"""
+    import numpy as np
+    K, W, S = 6, 3, 16
+    got = []
+    for d in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                              "--seqs-per-gpu", str(S), "--repeats", "1", "--no-cpu-baseline", "--no-single-sequence",
+                              "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == K and line["ms_per_step"] > 0
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = got
+    assert sorted(a) == ["kiss_poses", "res_poses", "res_t", "scan", "sequence", "stats"]
+    assert a["kiss_poses"].shape == (S, K + W, 4, 4) and a["res_poses"].shape == (S, K + W, 4, 4) and a["stats"].shape == (S, K + W, 12)
+    assert all(v.dtype == np.float64 for v in a.values()) and np.all(np.isfinite(a["res_poses"]))
+    assert np.abs(a["kiss_poses"][:, -1, :3, 3]).max() > 0  # the last step moved every sequence somewhere
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
