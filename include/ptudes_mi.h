@@ -43,7 +43,8 @@ extern "C" {
  * ptl_last_error() - without writing a byte.  A binding in another language (ctypes, cgo, JNI) that was written against an older header
  * therefore fails at its first call instead of being overrun by the library's memset or read past its end (a field appended to
  * ptl_icp_cfg did exactly that to round 5's documented stub).  ptl_abi_version() / ptl_sizeof_cfg() let such a binding assert its
- * layout at load time (INTEGRATION.md section 2 does).  Bump PTL_ABI_VERSION with every change of a struct or a prototype. */
+ * layout at load time (INTEGRATION.md section 2 does).  Bump PTL_ABI_VERSION with every change of a struct or a prototype; a new entry point
+ * changes neither, so it does not bump the version. */
 #define PTL_ABI_VERSION 6
 #define PTL_CFG_ICP 0
 #define PTL_CFG_EKF 1
@@ -250,6 +251,29 @@ int ptl_ekf_get_state(ptl_ekf *h, double nav[19], double cov[324]);
 int ptl_ekf_pose_mat(ptl_ekf *h, double T[16]); /* NavState.pose_mat (ins/data.py:70-74) */
 int ptl_ekf_ts(ptl_ekf *h, double *ts);         /* ESEKF.ts (:186-189) */
 
+/* Fixed-interval Rauch-Tung-Striebel smoother over the filter's own history (no reference counterpart: the reference's filter is causal).
+ * While the log is on, every pose update appends one entry (8 KB, fp64) to a device log: the filter's time, the state and covariance
+ * before the update (x_{k|k-1}, P_{k|k-1}), the product Phi of the IMU transitions Fx since the previous update, and the state and
+ * covariance after it (x_{k|k}, P_{k|k}).  The filter's arithmetic does not change: its outputs are bit-identical with the log on or off.
+ * The backward pass (one workgroup per filter) gives, per logged update in update order, the smoothed 4x4 pose (the res_poses form), its
+ * timestamp, optionally the smoothed nav[19] (ptl_ekf_get_state's layout) and P^s (18x18); every output but poses16 may be NULL.
+ * A full log stops writing and the smoothing call returns PTL_ERR_CAPACITY; smoothing without a log returns PTL_ERR_STATE, and so does a
+ * P_{k+1|k} that is not positive definite (ptl_last_error() names the entry).  A failed call leaves the handle usable.
+ * ptl_ekf_log_enable: a fresh, empty log for `capacity` updates (0 = off, frees it). */
+int ptl_ekf_log_enable(ptl_ekf *h, int64_t capacity);
+/* copies up to max_rows rows; *n_rows (nullable) = rows copied */
+int ptl_ekf_smooth(ptl_ekf *h, double *poses16, double *ts, double *nav19, double *cov324, int64_t max_rows, int64_t *n_rows);
+/* The raw log: up to max_entries entries of PTL_SMOOTHER_LOG_STRIDE doubles each (layout below; the rest of an entry is padding);
+ * *n_entries = entries logged (nullable); *overflow (nullable) = 1 once an update found the log full */
+#define PTL_SMOOTHER_LOG_STRIDE 1024
+#define PTL_SMOOTHER_LOG_TS 0          /* the filter's time at the update (= res_t) */
+#define PTL_SMOOTHER_LOG_NAV_PRED 1    /* nav[19] before the update, x_{k|k-1} */
+#define PTL_SMOOTHER_LOG_P_PRED 20     /* 18x18 before the update, P_{k|k-1} */
+#define PTL_SMOOTHER_LOG_PHI 344       /* 18x18 product of the IMU transitions Fx since the previous logged update, Phi_{k-1->k} */
+#define PTL_SMOOTHER_LOG_NAV_POST 668  /* nav[19] after the update, x_{k|k} */
+#define PTL_SMOOTHER_LOG_P_POST 687    /* 18x18 after the update, P_{k|k} */
+int ptl_ekf_smoother_log(ptl_ekf *h, double *entries, int64_t max_entries, int64_t *n_entries, int32_t *overflow);
+
 /* ------------------------------------------------------------------------------------------------
  * Whole-sequence runner == the reference's driver loop (cli/ekf_bench.py:493-563) on a pre-uploaded
  * sequence: all scans + IMU samples resident in HBM, no host round trip per scan.
@@ -306,6 +330,12 @@ int ptl_seq_traj_device(ptl_seq *s, void **dev_ptr, int64_t *rows);
 /* device-to-device copy of those rows into a caller-owned DEVICE buffer (e.g. a torch tensor's data_ptr) */
 int ptl_seq_copy_traj(ptl_seq *s, void *dst_device, int64_t max_rows, int64_t *rows);
 int ptl_seq_icp(ptl_seq *s, ptl_icp **icp);
+/* The smoother (see ptl_ekf_log_enable) for the sequence's filter: capacity n_scans, refused (PTL_ERR_STATE) when with_ekf == 0.  A cold
+ * start (ptl_seq_run) empties the log, ptl_seq_advance / _enqueue continue it.  The rows of ptl_seq_smooth (n_scans capacity in every
+ * buffer) align one for one with the rows of ptl_seq_results: a scan skipped for want of IMU samples has no update and no entry. */
+int ptl_seq_smoother_enable(ptl_seq *s, int32_t on);
+int ptl_seq_smooth(ptl_seq *s, double *poses16, double *ts, double *nav19, double *cov324, int64_t *n_rows);
+int ptl_seq_smoother_log(ptl_seq *s, double *entries, int64_t max_entries, int64_t *n_entries, int32_t *overflow);
 int ptl_seq_profile(ptl_seq *s, int enable, double *gn_ms_total, int64_t *gn_launches, int reset);
 
 /* One scan of the reference's loop body (cli/ekf_bench.py:493-563) for the per-call handles in ONE host round trip: the n_imu IMU samples
@@ -340,6 +370,14 @@ int ptl_batch_wait(ptl_batch *b);
 int ptl_batch_results(ptl_batch *b, int32_t seq, double *res_poses, double *res_t, double *kiss_poses,
                       ptl_icp_stats *stats, int64_t max_n, int64_t *n_out);
 int ptl_batch_copy_traj(ptl_batch *b, int32_t seq, void *dst_device, int64_t max_rows, int64_t *rows);
+/* The smoother (see ptl_ekf_log_enable, ptl_seq_smoother_enable) for every sequence of the batch, either driver, resident or sweep ring.
+ * ptl_batch_run / _reset empty the logs, ptl_batch_enqueue continues them.  ptl_batch_smooth: one launch smooths every sequence and waits;
+ * ptl_batch_smoothed then copies sequence seq's rows (n_scans capacity in every buffer; PTL_ERR_STATE when nothing was smoothed since the
+ * last run / enqueue). */
+int ptl_batch_smoother_enable(ptl_batch *b, int32_t on);
+int ptl_batch_smooth(ptl_batch *b);
+int ptl_batch_smoothed(ptl_batch *b, int32_t seq, double *poses16, double *ts, double *nav19, double *cov324, int64_t *n_rows);
+int ptl_batch_smoother_log(ptl_batch *b, int32_t seq, double *entries, int64_t max_entries, int64_t *n_entries, int32_t *overflow);
 int ptl_batch_gn_phases(ptl_batch *b, int64_t out[8]); /* like ptl_icp_gn_phases, for the shared launch */
 int ptl_batch_icp(ptl_batch *b, int32_t seq, ptl_icp **icp); /* the ICP handle of one sequence (diagnostics, map export) */
 int ptl_batch_profile(ptl_batch *b, int enable, double *gn_ms_total, int64_t *gn_launches, int reset);

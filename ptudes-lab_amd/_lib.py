@@ -113,6 +113,9 @@ PROTOTYPES = {
     "ptl_ekf_get_state": (C.c_int, [_vp, c_d_p, c_d_p]),
     "ptl_ekf_pose_mat": (C.c_int, [_vp, c_d_p]),
     "ptl_ekf_ts": (C.c_int, [_vp, c_d_p]),
+    "ptl_ekf_log_enable": (C.c_int, [_vp, C.c_int64]),
+    "ptl_ekf_smooth": (C.c_int, [_vp, c_d_p, c_d_p, c_d_p, c_d_p, C.c_int64, c_i64_p]),
+    "ptl_ekf_smoother_log": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
     "ptl_icp_ekf_step": (C.c_int, [_vp, _vp, c_d_p, C.c_int64, _vp, C.c_int, C.c_int64, c_d_p, c_d_p, C.c_int32, c_d_p, c_d_p,
                                   c_d_p, C.POINTER(IcpStats)]),
     "ptl_seq_create": (C.c_int, [C.POINTER(SeqCfg), _vpp]),
@@ -133,6 +136,9 @@ PROTOTYPES = {
     "ptl_seq_traj_device": (C.c_int, [_vp, _vpp, c_i64_p]),
     "ptl_seq_icp": (C.c_int, [_vp, _vpp]),
     "ptl_seq_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),
+    "ptl_seq_smoother_enable": (C.c_int, [_vp, C.c_int32]),
+    "ptl_seq_smooth": (C.c_int, [_vp, c_d_p, c_d_p, c_d_p, c_d_p, c_i64_p]),
+    "ptl_seq_smoother_log": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
     "ptl_batch_create": (C.c_int, [C.POINTER(SeqCfg), C.c_int32, _vpp]),
     "ptl_batch_destroy": (C.c_int, [_vp]),
     "ptl_batch_upload_scan": (C.c_int, [_vp, C.c_int32, C.c_int64, C.POINTER(C.c_float)]),
@@ -144,6 +150,10 @@ PROTOTYPES = {
     "ptl_batch_wait": (C.c_int, [_vp]),
     "ptl_batch_results": (C.c_int, [_vp, C.c_int32, c_d_p, c_d_p, c_d_p, C.POINTER(IcpStats), C.c_int64, c_i64_p]),
     "ptl_batch_copy_traj": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, c_i64_p]),
+    "ptl_batch_smoother_enable": (C.c_int, [_vp, C.c_int32]),
+    "ptl_batch_smooth": (C.c_int, [_vp]),
+    "ptl_batch_smoothed": (C.c_int, [_vp, C.c_int32, c_d_p, c_d_p, c_d_p, c_d_p, c_i64_p]),
+    "ptl_batch_smoother_log": (C.c_int, [_vp, C.c_int32, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

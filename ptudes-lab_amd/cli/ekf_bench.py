@@ -20,6 +20,7 @@ from typing import List, Optional
 import click
 import numpy as np
 import numpy.random as npr
+from scipy.spatial.transform import Rotation
 
 from ..ins.data import GRAV, IMU, calc_ate, ekf_traj_ate
 from ..ins.es_ekf import ESEKF
@@ -62,7 +63,10 @@ def sim_imu(acc_mean=np.zeros(3), acc_std=1.5, acc_noise_std=0.4, acc_bias=np.ar
 @click.option("--corr-t", type=float, default=0.1, help="seconds between two pose corrections of the filter (default 0.1)")
 @click.option("--acc-noise-std", type=float, default=0.4, help="standard deviation of the accelerometer noise")
 @click.option("--gyr-noise-std", type=float, default=0.4, help="standard deviation of the gyroscope noise")
-def ptudes_ekf_sim(duration: float, corr_t: float, freq: float, acc_noise_std: float, gyr_noise_std: float) -> None:
+@click.option("--smooth", is_flag=True, help="also run the fixed-interval RTS smoother and print its ATE next to the filter's, "
+                                             "both at the update epochs")
+def ptudes_ekf_sim(duration: float, corr_t: float, freq: float, acc_noise_std: float, gyr_noise_std: float,
+                   smooth: bool = False) -> None:
     """EKF with simulated IMU measurements; the noise-free filter is the ground truth for pose corrections."""
     print("Using sim IMUs with params:")
     print(f"  freq: {freq} Hz")
@@ -71,6 +75,9 @@ def ptudes_ekf_sim(duration: float, corr_t: float, freq: float, acc_noise_std: f
     print(f"  correction dt: {corr_t:.02} s")
     print("Running EKF ... \n")
     ekf_gt, ekf = ESEKF(_logging=True), ESEKF(_logging=True)
+    if smooth:  # at most one update per IMU sample
+        ekf.enable_smoother(int(duration * freq) + 2)
+    upd_gt, upd_filt = [], []
     start_ts = last_corr_t = ts = None
     for imu_ideal, imu_noisy in sim_imu(freq=freq, acc_noise_std=acc_noise_std, gyr_noise_std=gyr_noise_std):
         ts = imu_ideal.ts
@@ -81,6 +88,9 @@ def ptudes_ekf_sim(duration: float, corr_t: float, freq: float, acc_noise_std: f
         if ts - last_corr_t > corr_t:
             ekf.processPose(ekf_gt.nav.pose_mat())
             last_corr_t = ts
+            if smooth:
+                upd_gt.append(ekf_gt.nav.pose_mat())
+                upd_filt.append(ekf.nav.pose_mat())
         if ts - start_ts > duration:
             break
     print("Results:")
@@ -91,6 +101,16 @@ def ptudes_ekf_sim(duration: float, corr_t: float, freq: float, acc_noise_std: f
     ate_rot, ate_trans = ekf_traj_ate(ekf_gt, ekf)
     print(f"ATE_rot:   {ate_rot:.04f} deg")
     print(f"ATE trans: {ate_trans:.04f} m")
+    if smooth and upd_gt:
+        # RMSE in the common frame (both filters start at the identity): the first-pose alignment of the ATE above would carry the
+        # smoothed first pose's own error into every GT pose
+        sm = ekf.smooth(nav=False, cov=False)
+        gt = np.asarray(upd_gt)
+        for label, poses in (("filtered", np.asarray(upd_filt)), ("RTS smoothed", sm["poses"])):
+            d_t = np.linalg.norm(poses[:, :3, 3] - gt[:, :3, 3], axis=1)
+            d_r = [np.linalg.norm(Rotation.from_matrix(a[:3, :3].T @ b[:3, :3]).as_rotvec()) for a, b in zip(poses, gt)]
+            print(f"RMSE at the {len(gt)} updates ({label}): rot {np.degrees(np.sqrt(np.mean(np.square(d_r)))):.06f} deg, "
+                  f"trans {np.sqrt(np.mean(np.square(d_t))):.06f} m")
 
 
 @click.command(name="nc")
@@ -204,10 +224,13 @@ def _synthetic_source(seed: int, n_scans: int):
               help="write the resulting poses to this file, Newer College ground-truth format")
 @click.option("--synthetic", type=int, default=None,
               help="Run on the synthetic 128x1024 sequence with this seed instead of FILE (no ouster-sdk needed)")
+@click.option("--save-smoothed-poses", required=False, type=click.Path(exists=False, dir_okay=False),
+              help="also run the fixed-interval RTS smoother over the whole run and write its poses to this file, Newer College "
+                   "ground-truth format, with the timestamps of --save-nc-gt-poses; with -g, print its ATE")
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
-                      kiss_max_range: float, synthetic: Optional[int]) -> None:
+                      kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
@@ -287,7 +310,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
 
     stats = StreamStatsTracker(use_beams_num=32, metadata=info)  # reference :457
     out = run_events(feed(), info, kiss_min_range=kiss_min_range, kiss_max_range=kiss_max_range,
-                     use_imu_prediction=use_imu_prediction, guess_fn=guess_fn, logging=log_metrics, stats=stats)
+                     use_imu_prediction=use_imu_prediction, guess_fn=guess_fn, logging=log_metrics, stats=stats,
+                     smooth=bool(save_smoothed_poses))
     res_t, res_poses, kiss_poses = out["res_t"], out["res_poses"], out["kiss_poses"]
     header = display_header + f"(scans/updates num: {len(res_poses)})\n"
     header += "time: " + datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -297,6 +321,17 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
     if save_nc_gt_poses:
         save_poses_nc_gt_format(save_nc_gt_poses, t=res_t, poses=res_poses, header=header)
         print(f"NC GT poses saved to: {save_nc_gt_poses}")
+    if save_smoothed_poses:
+        sm_t, sm_poses = list(out["smoothed_t"]), list(out["smoothed_poses"])
+        save_poses_nc_gt_format(save_smoothed_poses, t=sm_t, poses=sm_poses, header=header)  # (stdout: only the ATE line below)
+        if gts and sm_poses:
+            gts_m, t_matched = filter_nc_gt_by_close_ts(gts, sm_t)
+            if gts_m:
+                at = {t: p for t, p in zip(sm_t, sm_poses)}
+                sm_m = [at[t] for t in t_matched]
+                pose0 = sm_m[0] @ np.linalg.inv(gts_m[0][1])
+                ate_rot, ate_trans = calc_ate(sm_m, [pose0 @ g[1] for g in gts_m])
+                print(f"ATE of the RTS smoothed poses ({len(gts_m)} poses): rot {ate_rot:.04f} deg, trans {ate_trans:.04f} m")
     tm = out["timings"]
     if tm["n_imu"] and tm["n_corr"]:  # reference :590-595
         print("\nTimings:")

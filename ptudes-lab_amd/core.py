@@ -266,6 +266,54 @@ class Ekf:
         L.check(L.lib().ptl_ekf_ts(self._h, C.byref(t)))
         return t.value
 
+    def enable_smoother(self, capacity):
+        """a fresh, empty history log for `capacity` pose updates (0 = off); include/ptudes_mi.h ptl_ekf_log_enable"""
+        L.check(L.lib().ptl_ekf_log_enable(self._h, int(capacity)))
+        self._sm_cap = int(capacity)
+
+    def smoother_log(self):
+        """the raw history log (dict of per-entry arrays; core._LOG_FIELDS)"""
+        return _smoother_log(getattr(self, "_sm_cap", 0), lambda p, m, n, o: L.lib().ptl_ekf_smoother_log(self._h, p, m, n, o))
+
+    def smooth(self, nav=True, cov=True):
+        """fixed-interval RTS smoother over the logged updates: dict(t, poses[, nav][, cov]), one row per update in update order"""
+        return _smoothed(getattr(self, "_sm_cap", 0), nav, cov,
+                         lambda p, t, n, c, w: L.lib().ptl_ekf_smooth(self._h, p, t, n, c, getattr(self, "_sm_cap", 0), w))
+
+
+def _smoothed(cap, nav, cov, call):
+    """one smoothing call with `cap`-row host buffers -> dict(t, poses, nav?, cov?) of the rows written"""
+    cap = max(int(cap), 1)
+    p, t = np.empty((cap, 4, 4)), np.empty(cap)
+    n = np.empty((cap, 19)) if nav else None
+    c = np.empty((cap, 18, 18)) if cov else None
+    w = C.c_int64()
+    L.check(call(L.dptr(p), L.dptr(t), None if n is None else L.dptr(n), None if c is None else L.dptr(c), C.byref(w)))
+    m = w.value
+    out = dict(t=t[:m], poses=p[:m])
+    if nav:
+        out["nav"] = n[:m]
+    if cov:
+        out["cov"] = c[:m]
+    return out
+
+
+# one entry of the smoother's log (include/ptudes_mi.h PTL_SMOOTHER_LOG_*)
+LOG_STRIDE = 1024
+_LOG_FIELDS = (("ts", 0, ()), ("nav_pred", 1, (19,)), ("P_pred", 20, (18, 18)), ("Phi", 344, (18, 18)),
+               ("nav_post", 668, (19,)), ("P_post", 687, (18, 18)))
+
+
+def _smoother_log(cap, call):
+    """one log read-out with a `cap`-entry host buffer -> dict(ts, nav_pred, P_pred, Phi, nav_post, P_post, overflow) of the entries"""
+    raw = np.zeros((max(int(cap), 1), LOG_STRIDE))
+    n, ovf = C.c_int64(), C.c_int32()
+    L.check(call(L.dptr(raw), raw.shape[0], C.byref(n), C.byref(ovf)))
+    m = min(n.value, raw.shape[0])
+    out = {k: raw[:m, o:o + int(np.prod(shp or (1,)))].reshape((m,) + shp).copy() for k, o, shp in _LOG_FIELDS}
+    out["overflow"] = bool(ovf.value)
+    return out
+
 
 def icp_ekf_step(icp: "Icp", ekf: "Ekf", imu_rows, xyz, t01=None, guess=None, use_imu_prediction=False):
     """One scan of the reference's loop body (cli/ekf_bench.py:493-563) in one host round trip (include/ptudes_mi.h ptl_icp_ekf_step):
@@ -392,6 +440,18 @@ class SeqRunner:
         ms, n = C.c_double(), C.c_int64()
         L.check(L.lib().ptl_seq_profile(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
+
+    def enable_smoother(self, on=True):
+        """log the filter's history (capacity n_scans) for smooth(); include/ptudes_mi.h ptl_seq_smoother_enable"""
+        L.check(L.lib().ptl_seq_smoother_enable(self._h, int(bool(on))))
+
+    def smoother_log(self):
+        """the raw history log of the sequence's filter (dict of per-entry arrays; core._LOG_FIELDS)"""
+        return _smoother_log(self.n_scans, lambda p, m, n, o: L.lib().ptl_seq_smoother_log(self._h, p, m, n, o))
+
+    def smooth(self, nav=True, cov=True):
+        """fixed-interval RTS smoother: dict(t, poses[, nav][, cov]), rows aligned with results()'s res_poses / res_t"""
+        return _smoothed(self.n_scans, nav, cov, lambda p, t, n, c, w: L.lib().ptl_seq_smooth(self._h, p, t, n, c, w))
 
 
 class BatchRunner:
@@ -545,6 +605,22 @@ class BatchRunner:
         ms, n = C.c_double(), C.c_int64()
         L.check(L.lib().ptl_batch_profile(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
+
+    def enable_smoother(self, on=True):
+        """log every sequence's filter history (capacity n_scans each); include/ptudes_mi.h ptl_batch_smoother_enable"""
+        L.check(L.lib().ptl_batch_smoother_enable(self._h, int(bool(on))))
+
+    def smooth(self):
+        """the backward pass of every sequence in one launch (waits); smoothed(s) then gives sequence s's rows"""
+        L.check(L.lib().ptl_batch_smooth(self._h))
+
+    def smoother_log(self, s):
+        """the raw history log of sequence s's filter (dict of per-entry arrays; core._LOG_FIELDS)"""
+        return _smoother_log(self.n_scans, lambda p, m, n, o: L.lib().ptl_batch_smoother_log(self._h, s, p, m, n, o))
+
+    def smoothed(self, s, nav=True, cov=True):
+        """dict(t, poses[, nav][, cov]) of sequence s after smooth(), rows aligned with results(s)'s res_poses / res_t"""
+        return _smoothed(self.n_scans, nav, cov, lambda p, t, n, c, w: L.lib().ptl_batch_smoothed(self._h, s, p, t, n, c, w))
 
 
 BUILD_INFO = ("kcand", "ans_row_doubles", "lds_points", "seq_u", "seq_u2", "gn8_threads", "lanes_per_point", "spec", "surv",

@@ -31,7 +31,28 @@ struct EkfState {
     double Fx[EKF_N * EKF_N];  // persistent: identity + rewritten blocks (es_ekf.py:142, :216-223)
     double W[EKF_N * EKF_N];   // persistent: zero + rewritten diagonal blocks (es_ekf.py:145, :226-233)
     double pose[16];  // NavState.pose_mat() after the last step (ins/data.py:70-74)
+    // Filter history for the fixed-interval smoother (k_ekf_smooth), off while `log` is null.  Phi = product of the Fx of the active
+    // samples since the last logged update (identity at init, at a cold start and right after every logged update); every pose
+    // update appends one EKF_LOG_STRIDE-double entry while log_count < log_cap, else raises log_overflow and writes nothing.
+    double Phi[EKF_N * EKF_N];
+    double* log;
+    long long log_cap, log_count;
+    int log_overflow, log_pad;
 };
+// one log entry (doubles): ts | nav before the update (19: pos, q xyzw, vel, bg, ba, grav) | P before | Phi since the previous
+// logged update | nav after (inject + PHI-block projection + reset) | P after; 1011 used, padded to 8 KB
+#define EKF_LOG_STRIDE 1024
+#define EKF_LOG_TS 0
+#define EKF_LOG_NAV_PRED 1
+#define EKF_LOG_P_PRED 20
+#define EKF_LOG_PHI 344
+#define EKF_LOG_NAV_POST 668
+#define EKF_LOG_P_POST 687
+
+__device__ __forceinline__ void ekf_nav19(const EkfNav& n, double* o) {
+    for (int k = 0; k < 3; ++k) { o[k] = n.pos[k]; o[7 + k] = n.vel[k]; o[10 + k] = n.bg[k]; o[13 + k] = n.ba[k]; o[16 + k] = n.grav[k]; }
+    for (int k = 0; k < 4; ++k) o[3 + k] = n.q[k];
+}
 
 __device__ __forceinline__ void ekf_write_pose(EkfState* e) {
     double R[9];
@@ -67,6 +88,9 @@ __global__ void k_ekf_init(EkfState* e, const double* grav, const double* bacc, 
         e->P[(EKF_G + i) * EKF_N + EKF_G + i] = 6.25;
     }
     e->nav.cur_ts = 0.0; e->nav.cur_dt = 0.0; e->nav.initialized = 0; e->nav.n_updates = 0;
+    // a cold start empties the log (its buffer and capacity stay)
+    for (int i = 0; i < EKF_N * EKF_N; ++i) e->Phi[i] = (i % (EKF_N + 1) == 0) ? 1.0 : 0.0;
+    e->log_count = 0; e->log_overflow = 0;
     for (int i = 0; i < 3; ++i) { e->nav.cur_lacc[i] = 0.0; e->nav.cur_avel[i] = 0.0; }
     ekf_write_pose(e);
 }
@@ -119,10 +143,18 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
     __shared__ int sPiv;
     __shared__ double sRd[EKF_CHUNK][10];  // per-sample Exp(dtheta) (9) and dt
     __shared__ double sBias[8];
+    __shared__ double sPhi[EKF_N * EKF_N];  // the smoother's transition accumulator (only touched while the log is on)
     const int tid = threadIdx.x;
     const int ti = tid / EKF_N, tj = tid % EKF_N;
     const bool cell = tid < EKF_N * EKF_N;
     if (cell) { sP[tid] = e->P[tid]; sF2[0][tid] = sF2[1][tid] = e->Fx[tid]; sW2[0][tid] = sW2[1][tid] = e->W[tid]; }
+    double* const lg = e->log;  // uniform: the history log of the smoother, null = off
+    long long lcount = 0;
+    if (lg) {
+        lcount = e->log_count;
+        if (cell) sPhi[tid] = e->Phi[tid];
+    }
+    double phin = 0.0;
     if (tid == 0) s_lastbuf = 0;
     // the mechanisation (one lane) runs in a wavefront of its own when the launch has one to spare, so that it overlaps
     // the covariance products instead of preceding them
@@ -198,6 +230,14 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
                             acc += sF[ti * EKF_N + k] * sP[k * EKF_N + tj];
                         }
                         sT[tid] = acc;
+                        if (lg) {  // Phi = Fx Phi with the same Fx (written back in stage 2, nobody reads sPhi there)
+                            double ph = 0.0;
+                            for (unsigned m = ekf_row_mask(ti); m; m &= m - 1) {
+                                const int k = __ffs(m) - 1;
+                                ph += sF[ti * EKF_N + k] * sPhi[k * EKF_N + tj];
+                            }
+                            phin = ph;
+                        }
                     }
                     __syncthreads();
                     // ---- stage 2
@@ -231,6 +271,7 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
                             acc += sT[ti * EKF_N + k] * sF[tj * EKF_N + k];
                         }
                         sP[tid] = acc + sW2[bp][tid];
+                        if (lg) sPhi[tid] = phin;
                     }
                     __syncthreads();
                 }
@@ -238,6 +279,13 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
             continue;
         }
         if (!do_update) continue;
+        // the smoother's log entry: the state before the update (all writers of nv / sP are behind a barrier here)
+        const bool logit = lg && lcount < e->log_cap;
+        double* const ent = logit ? lg + (size_t)lcount * EKF_LOG_STRIDE : nullptr;
+        if (logit) {
+            if (cell) { ent[EKF_LOG_P_PRED + tid] = sP[tid]; ent[EKF_LOG_PHI + tid] = sPhi[tid]; }
+            if (tid == 0) { ent[EKF_LOG_TS] = nv.cur_ts; ekf_nav19(nv, ent + EKF_LOG_NAV_PRED); }
+        }
         // ---- processPose (:259-329); the error state is zero on entry (reset at :327)
         if (tid == 0) {
             double Rk[9], RkT[9], Rm[9], D[9];
@@ -360,9 +408,23 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
             }
         }
         __syncthreads();
+        if (lg) {  // the state after the update; Phi starts again
+            if (logit) {
+                if (cell) ent[EKF_LOG_P_POST + tid] = sP[tid];
+                if (tid == 0) ekf_nav19(nv, ent + EKF_LOG_NAV_POST);
+                lcount += 1;
+            } else if (tid == 0) {
+                e->log_overflow = 1;
+            }
+            if (cell) sPhi[tid] = (ti == tj) ? 1.0 : 0.0;
+        }
     }
     if (cell) { e->P[tid] = sP[tid]; e->Fx[tid] = sF2[s_lastbuf][tid]; e->W[tid] = sW2[s_lastbuf][tid]; }
     if (tid == 0) { e->nav = nv; ekf_write_pose(e); }
+    if (lg) {
+        if (cell) e->Phi[tid] = sPhi[tid];
+        if (tid == 0) e->log_count = lcount;
+    }
 }
 
 #define EKF_THREADS 448  /* 324 covariance cells (six wavefronts) + a seventh wavefront for the mechanisation lane */
@@ -404,4 +466,187 @@ struct EkfBatchArgs {
 __global__ __launch_bounds__(384) void kb_ekf_step(EkfBatchArgs a) {
     const int s = blockIdx.x;
     d_ekf_step(a.e[s], a.imu[s], a.i0[s], a.i1[s], a.pose[s], nullptr, a.out_pose[s], a.out_t[s], a.out_row8[s], a.update_first);
+}
+
+// ================================================================================================ fixed-interval RTS smoother
+// k_ekf_smooth: the Rauch-Tung-Striebel backward pass over one filter's log (EkfState::log), one workgroup per filter, thread (i, j)
+// of the first 324 owns entry (i, j) of the 18x18 matrices in LDS.  From x^s_N = x_{N|N}, P^s_N = P_{N|N}, for k = N-2 .. 0
+// (entry k: post = x_{k|k}, P_{k|k}; entry k+1: pred = x_{k+1|k}, P_{k+1|k}, Phi = Phi_{k->k+1}):
+//   P_{k+1|k} X = Phi P_{k|k}              (Cholesky, right-looking in LDS),  C = X^T
+//   e     = x^s_{k+1} [-] x_{k+1|k}        (pos / vel / bg / ba / grav: difference; attitude: Log(R_{k+1|k}^T R^s_{k+1}))
+//   x^s_k = x_{k|k} [+] C e                (attitude: R_{k|k} Exp(dphi), the filter's right perturbation)
+//   P^s_k = P_{k|k} + C (P^s_{k+1} - P_{k+1|k}) C^T, then (P + P^T) / 2
+// The chain is serial per filter; entry k-1 (about 8 KB) is loaded into registers while entry k is computed.
+// info[0]: 0 = done, -1 = the log overflowed, -2 = no log, 1 + i = P_pred of entry i is not positive definite (outputs not
+// trusted); info[1]: rows written (rows k .. N-1 are valid when the pass stopped early).
+struct EkfSmoothJob {
+    const EkfState* e;
+    double *pose, *t, *nav, *cov;  // [N][16], [N], [N][19], [N][324]
+    long long* info;               // [2]
+};
+#define EKF_SMOOTH_THREADS 384
+
+__device__ __forceinline__ void ekf_smooth_row(const double* xs, double t, const double* Ps, const EkfSmoothJob& J, long long k, int tid) {
+    if (tid < 19) J.nav[19 * k + tid] = xs[tid];
+    if (tid < EKF_N * EKF_N) J.cov[324 * k + tid] = Ps[tid];
+    if (tid == 0) {  // the res_poses form (ekf_write_pose)
+        double R[9];
+        quat_to_R(xs + 3, R);
+        double* o = J.pose + 16 * k;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) o[4 * i + j] = R[3 * i + j];
+            o[4 * i + 3] = xs[i];
+        }
+        o[12] = o[13] = o[14] = 0.0;
+        o[15] = 1.0;
+        J.t[k] = t;
+    }
+}
+
+__global__ __launch_bounds__(EKF_SMOOTH_THREADS) void k_ekf_smooth(const EkfSmoothJob* jobs) {
+    __shared__ double sPs[EKF_N * EKF_N], sPk[EKF_N * EKF_N], sPp[EKF_N * EKF_N], sPhi[EKF_N * EKF_N];
+    __shared__ double sL[EKF_N * EKF_N], sX[EKF_N * EKF_N], sT[EKF_N * EKF_N];
+    __shared__ double sxs[19], snk[19], snp[19], se[EKF_N], sdx[EKF_N];
+    __shared__ int sbad;
+    const EkfSmoothJob J = jobs[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int ti = tid / EKF_N, tj = tid % EKF_N;
+    const bool cell = tid < EKF_N * EKF_N;
+    const double* lg = J.e->log;
+    const long long N = J.e->log_count;
+    if (!lg || J.e->log_overflow) {
+        if (tid == 0) { J.info[0] = lg ? -1 : -2; J.info[1] = 0; }
+        return;
+    }
+    if (N <= 0) {
+        if (tid == 0) { J.info[0] = 0; J.info[1] = 0; }
+        return;
+    }
+    const double* last = lg + (size_t)(N - 1) * EKF_LOG_STRIDE;
+    if (cell) sPs[tid] = last[EKF_LOG_P_POST + tid];
+    if (tid < 19) sxs[tid] = last[EKF_LOG_NAV_POST + tid];
+    if (tid == 0) sbad = 0;
+    __syncthreads();
+    ekf_smooth_row(sxs, last[EKF_LOG_TS], sPs, J, N - 1, tid);
+    // registers: entry k's post part and entry k + 1's pred part, loaded one step ahead
+    double rPk = 0.0, rPp = 0.0, rPhi = 0.0, rnk = 0.0, rnp = 0.0, rt = 0.0;
+    auto fetch = [&](long long k) {
+        const double* ek = lg + (size_t)k * EKF_LOG_STRIDE;
+        const double* e1 = ek + EKF_LOG_STRIDE;
+        if (cell) { rPk = ek[EKF_LOG_P_POST + tid]; rPp = e1[EKF_LOG_P_PRED + tid]; rPhi = e1[EKF_LOG_PHI + tid]; }
+        if (tid < 19) { rnk = ek[EKF_LOG_NAV_POST + tid]; rnp = e1[EKF_LOG_NAV_PRED + tid]; }
+        rt = ek[EKF_LOG_TS];
+    };
+    if (N >= 2) fetch(N - 2);
+    long long k = N - 2;
+    for (; k >= 0; --k) {
+        if (cell) { sPk[tid] = rPk; sPp[tid] = rPp; sL[tid] = rPp; sPhi[tid] = rPhi; }
+        if (tid < 19) { snk[tid] = rnk; snp[tid] = rnp; }
+        const double tk = rt;
+        __syncthreads();
+        if (k >= 1) fetch(k - 1);
+        // A = Phi P_{k|k} (into sX, solved in place below)
+        if (cell) {
+            double acc = 0.0;
+            for (int m = 0; m < EKF_N; ++m) acc += sPhi[ti * EKF_N + m] * sPk[m * EKF_N + tj];
+            sX[tid] = acc;
+        }
+        // Cholesky P_{k+1|k} = L L^T, lower triangle of sL
+#pragma unroll 1
+        for (int j = 0; j < EKF_N; ++j) {
+            if (tid == 0) {
+                const double d = sL[j * EKF_N + j];
+                if (!(d > 0.0)) sbad = 1;
+                sL[j * EKF_N + j] = sqrt(d);
+            }
+            __syncthreads();
+            if (tid > j && tid < EKF_N) sL[tid * EKF_N + j] /= sL[j * EKF_N + j];
+            __syncthreads();
+            if (cell && tj > j && ti >= tj) sL[ti * EKF_N + tj] -= sL[ti * EKF_N + j] * sL[tj * EKF_N + j];
+            __syncthreads();
+        }
+        if (sbad) {
+            if (tid == 0) { J.info[0] = 1 + (k + 1); J.info[1] = N - 1 - k; }
+            return;
+        }
+        // L L^T X = A, one column per thread: forward then back substitution
+        if (tid < EKF_N) {
+            const int c = tid;
+#pragma unroll 1
+            for (int i = 0; i < EKF_N; ++i) {
+                double v = sX[i * EKF_N + c];
+                for (int m = 0; m < i; ++m) v -= sL[i * EKF_N + m] * sX[m * EKF_N + c];
+                sX[i * EKF_N + c] = v / sL[i * EKF_N + i];
+            }
+#pragma unroll 1
+            for (int i = EKF_N - 1; i >= 0; --i) {
+                double v = sX[i * EKF_N + c];
+                for (int m = i + 1; m < EKF_N; ++m) v -= sL[m * EKF_N + i] * sX[m * EKF_N + c];
+                sX[i * EKF_N + c] = v / sL[i * EKF_N + i];
+            }
+        }
+        if (tid == 0) {  // e = x^s_{k+1} [-] x_{k+1|k} in the state order (POS, VEL, PHI, BG, BA, G)
+            double Rp[9], Rs[9], D[9];
+            quat_to_R(snp + 3, Rp);
+            quat_to_R(sxs + 3, Rs);
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) {
+                    double acc = 0.0;
+                    for (int m = 0; m < 3; ++m) acc += Rp[3 * m + r] * Rs[3 * m + c];
+                    D[3 * r + c] = acc;
+                }
+            R_to_rotvec(D, se + EKF_PHI);
+            for (int i = 0; i < 3; ++i) {
+                se[EKF_POS + i] = sxs[i] - snp[i];
+                se[EKF_VEL + i] = sxs[7 + i] - snp[7 + i];
+                se[EKF_BG + i] = sxs[10 + i] - snp[10 + i];
+                se[EKF_BA + i] = sxs[13 + i] - snp[13 + i];
+                se[EKF_G + i] = sxs[16 + i] - snp[16 + i];
+            }
+        }
+        __syncthreads();
+        // dx = C e (C = X^T); T = C (P^s_{k+1} - P_{k+1|k})
+        if (tid < EKF_N) {
+            double acc = 0.0;
+            for (int m = 0; m < EKF_N; ++m) acc += sX[m * EKF_N + tid] * se[m];
+            sdx[tid] = acc;
+        }
+        if (cell) {
+            double acc = 0.0;
+            for (int m = 0; m < EKF_N; ++m) acc += sX[m * EKF_N + ti] * (sPs[m * EKF_N + tj] - sPp[m * EKF_N + tj]);
+            sT[tid] = acc;
+        }
+        __syncthreads();
+        // P^s_k = P_{k|k} + T C^T, symmetrised
+        double pn = 0.0;
+        if (cell) {
+            double acc = 0.0;
+            for (int m = 0; m < EKF_N; ++m) acc += sT[ti * EKF_N + m] * sX[m * EKF_N + tj];
+            pn = sPk[tid] + acc;
+        }
+        __syncthreads();
+        if (cell) sPs[tid] = pn;
+        __syncthreads();
+        if (cell) pn = 0.5 * (sPs[ti * EKF_N + tj] + sPs[tj * EKF_N + ti]);
+        __syncthreads();
+        if (cell) sPs[tid] = pn;
+        if (tid == 0) {  // x^s_k = x_{k|k} [+] dx
+            double R[9], Rd[9], Rn[9];
+            for (int i = 0; i < 3; ++i) {
+                sxs[i] = snk[i] + sdx[EKF_POS + i];
+                sxs[7 + i] = snk[7 + i] + sdx[EKF_VEL + i];
+                sxs[10 + i] = snk[10 + i] + sdx[EKF_BG + i];
+                sxs[13 + i] = snk[13 + i] + sdx[EKF_BA + i];
+                sxs[16 + i] = snk[16 + i] + sdx[EKF_G + i];
+            }
+            quat_to_R(snk + 3, R);
+            rotvec_to_R(sdx + EKF_PHI, Rd);
+            mat3_mul(R, Rd, Rn);
+            R_to_quat(Rn, sxs + 3);
+        }
+        __syncthreads();
+        ekf_smooth_row(sxs, tk, sPs, J, k, tid);
+        __syncthreads();
+    }
+    if (tid == 0) { J.info[0] = 0; J.info[1] = N; }
 }

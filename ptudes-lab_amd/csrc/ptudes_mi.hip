@@ -1043,6 +1043,13 @@ struct ptl_ekf {
     EkfState* st;
     double* d_buf;  // staging: imu rows / pose / cov
     int64_t buf_rows;
+    // fixed-interval smoother (ptl_ekf_log_enable): the history log in HBM, the backward pass's outputs, its job and status words
+    double* d_log;
+    int64_t log_cap;
+    double* d_sm;  // [cap][16] poses | [cap] t | [cap][19] nav | [cap][324] P^s
+    EkfSmoothJob job;
+    EkfSmoothJob* d_job;
+    long long* d_info;
 };
 
 extern "C" int ptl_ekf_default_cfg(ptl_ekf_cfg* cfg) {
@@ -1076,7 +1083,9 @@ static int ekf_create_impl(const ptl_ekf_cfg* cfg, hipStream_t shared, ptl_ekf**
         delete h;
         return set_err(PTL_ERR_HIP, "device allocation failed");
     }
-    int rc = ekf_reset(h);
+    int rc = PTL_OK;
+    if (hipMemsetAsync(h->st, 0, sizeof(EkfState), h->stream) != hipSuccess) rc = set_err(PTL_ERR_HIP, "memset");  // smoother log off
+    if (rc == PTL_OK) rc = ekf_reset(h);
     if (rc == PTL_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = set_err(PTL_ERR_HIP, "sync");
     if (rc) { (void)hipFree(h->st); (void)hipFree(h->d_buf); delete h; return rc; }
     *out = h;
@@ -1087,6 +1096,8 @@ extern "C" int ptl_ekf_destroy(ptl_ekf* h) {
     if (!h) return PTL_OK;
     (void)hipSetDevice(h->cfg.device_id);
     (void)hipFree(h->st); (void)hipFree(h->d_buf);
+    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info})
+        if (p) (void)hipFree(p);
     if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return PTL_OK;
@@ -1148,6 +1159,106 @@ extern "C" int ptl_ekf_ts(ptl_ekf* h, double* ts) {
     HIPCHK(hipMemcpyAsync(ts, (char*)h->st + (offsetof(EkfState, nav) + offsetof(EkfNav, cur_ts)), 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PTL_OK;
+}
+
+// ---- fixed-interval RTS smoother (ekf_kernels.h: the log inside d_ekf_step, k_ekf_smooth)
+__global__ void k_ekf_log_set(EkfState* e, double* log, long long cap) {
+    const int t = threadIdx.x;
+    for (int i = t; i < EKF_N * EKF_N; i += blockDim.x) e->Phi[i] = (i % (EKF_N + 1) == 0) ? 1.0 : 0.0;
+    if (t == 0) { e->log = log; e->log_cap = cap; e->log_count = 0; e->log_overflow = 0; }
+}
+static void ekf_log_free(ptl_ekf* h) {
+    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info})
+        if (p) (void)hipFree(p);
+    h->d_log = nullptr; h->d_sm = nullptr; h->d_job = nullptr; h->d_info = nullptr;
+    h->log_cap = 0;
+}
+// capacity > 0: a fresh, empty log of that many updates (the old one, if any, is dropped); 0: off.  The caller's other streams must be idle.
+static int ekf_log_set(ptl_ekf* h, int64_t cap) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    k_ekf_log_set<<<1, 64, 0, h->stream>>>(h->st, nullptr, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    ekf_log_free(h);
+    if (cap <= 0) return PTL_OK;
+    const size_t c = (size_t)cap;
+    if (dalloc(&h->d_log, c * EKF_LOG_STRIDE) != hipSuccess || dalloc(&h->d_sm, c * 360) != hipSuccess ||
+        dalloc(&h->d_job, 1) != hipSuccess || dalloc(&h->d_info, 2) != hipSuccess) {
+        ekf_log_free(h);
+        return set_err(PTL_ERR_HIP, "smoother log allocation failed (%lld entries, %.1f MB)", (long long)cap, cap * (EKF_LOG_STRIDE + 360) * 8 / 1e6);
+    }
+    h->log_cap = cap;
+    h->job.e = h->st;
+    h->job.pose = h->d_sm; h->job.t = h->d_sm + 16 * c; h->job.nav = h->d_sm + 17 * c; h->job.cov = h->d_sm + 36 * c;
+    h->job.info = h->d_info;
+    HIPCHK(hipMemcpyAsync(h->d_job, &h->job, sizeof h->job, hipMemcpyHostToDevice, h->stream));
+    k_ekf_log_set<<<1, 64, 0, h->stream>>>(h->st, h->d_log, (long long)cap);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PTL_OK;
+}
+// the status words of k_ekf_smooth -> return code
+static int smooth_status(const ptl_ekf* h, const long long info[2], const char* who, int seq) {
+    if (info[0] == 0) return PTL_OK;
+    if (info[0] == -1) return set_err(PTL_ERR_CAPACITY, "%s: sequence %d: the smoother log overflowed (capacity %lld updates); a cold start or a new log empties it", who, seq, (long long)h->log_cap);
+    if (info[0] == -2) return set_err(PTL_ERR_STATE, "%s: sequence %d: no smoother log", who, seq);
+    return set_err(PTL_ERR_STATE, "%s: sequence %d: P_pred of log entry %lld is not positive definite (Cholesky failed): smoothed rows not valid", who, seq, info[0] - 1);
+}
+// rows [0, n) of the last backward pass of h -> host (poses16 required, the others nullable)
+static int smooth_copy_out(const ptl_ekf* h, int64_t n, double* poses16, double* ts, double* nav19, double* cov324) {
+    if (n <= 0) return PTL_OK;
+    const size_t c = (size_t)h->log_cap;
+    HIPCHK(hipMemcpy(poses16, h->d_sm, (size_t)n * 128, hipMemcpyDeviceToHost));
+    if (ts) HIPCHK(hipMemcpy(ts, h->d_sm + 16 * c, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (nav19) HIPCHK(hipMemcpy(nav19, h->d_sm + 17 * c, (size_t)n * 19 * 8, hipMemcpyDeviceToHost));
+    if (cov324) HIPCHK(hipMemcpy(cov324, h->d_sm + 36 * c, (size_t)n * 324 * 8, hipMemcpyDeviceToHost));
+    return PTL_OK;
+}
+static int ekf_smooth_impl(ptl_ekf* h, const char* who, double* poses16, double* ts, double* nav19, double* cov324, int64_t max_rows, int64_t* n_rows) {
+    if (!h->d_log) return set_err(PTL_ERR_STATE, "%s: the smoother log is not enabled", who);
+    k_ekf_smooth<<<1, EKF_SMOOTH_THREADS, 0, h->stream>>>(h->d_job);
+    HIPCHK(hipGetLastError());
+    long long info[2];
+    HIPCHK(hipMemcpyAsync(info, h->d_info, sizeof info, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int rc = smooth_status(h, info, who, 0);
+    if (rc) return rc;
+    const int64_t n = info[1] < max_rows ? info[1] : max_rows;
+    rc = smooth_copy_out(h, n, poses16, ts, nav19, cov324);
+    if (rc) return rc;
+    if (n_rows) *n_rows = n;
+    return PTL_OK;
+}
+static int ekf_log_read(ptl_ekf* h, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
+    if (!h->d_log) return set_err(PTL_ERR_STATE, "the smoother log is not enabled");
+    long long cnt = 0;
+    int ovf = 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(&cnt, (char*)h->st + offsetof(EkfState, log_count), sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ovf, (char*)h->st + offsetof(EkfState, log_overflow), sizeof ovf, hipMemcpyDeviceToHost));
+    const int64_t n = cnt < max_entries ? cnt : max_entries;
+    if (entries && n > 0) HIPCHK(hipMemcpy(entries, h->d_log, (size_t)n * EKF_LOG_STRIDE * 8, hipMemcpyDeviceToHost));
+    if (n_entries) *n_entries = cnt;
+    if (overflow) *overflow = ovf;
+    return PTL_OK;
+}
+static_assert(EKF_LOG_STRIDE == PTL_SMOOTHER_LOG_STRIDE && EKF_LOG_TS == PTL_SMOOTHER_LOG_TS && EKF_LOG_NAV_PRED == PTL_SMOOTHER_LOG_NAV_PRED &&
+              EKF_LOG_P_PRED == PTL_SMOOTHER_LOG_P_PRED && EKF_LOG_PHI == PTL_SMOOTHER_LOG_PHI && EKF_LOG_NAV_POST == PTL_SMOOTHER_LOG_NAV_POST &&
+              EKF_LOG_P_POST == PTL_SMOOTHER_LOG_P_POST, "log layout of include/ptudes_mi.h");
+extern "C" int ptl_ekf_smoother_log(ptl_ekf* h, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
+    if (!h || max_entries < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    return ekf_log_read(h, entries, max_entries, n_entries, overflow);
+}
+extern "C" int ptl_ekf_log_enable(ptl_ekf* h, int64_t capacity) {
+    if (!h || capacity < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    return ekf_log_set(h, capacity);
+}
+extern "C" int ptl_ekf_smooth(ptl_ekf* h, double* poses16, double* ts, double* nav19, double* cov324, int64_t max_rows, int64_t* n_rows) {
+    if (!h || !poses16 || max_rows < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    return ekf_smooth_impl(h, "ptl_ekf_smooth", poses16, ts, nav19, cov324, max_rows, n_rows);
 }
 
 // ================================================================================================ one scan of the driver loop, per-call handles
@@ -1420,6 +1531,27 @@ extern "C" int ptl_seq_advance(ptl_seq* s, int64_t n) {
     if (rc) return rc;
     return ptl_seq_wait(s);
 }
+extern "C" int ptl_seq_smoother_enable(ptl_seq* s, int32_t on) {
+    if (!s) return set_err(PTL_ERR_ARG, "null argument");
+    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_smoother_enable: an ICP-only sequence (with_ekf = 0) has no filter to smooth");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return ekf_log_set(s->ekf, on ? s->cfg.n_scans : 0);
+}
+extern "C" int ptl_seq_smooth(ptl_seq* s, double* poses16, double* ts, double* nav19, double* cov324, int64_t* n_rows) {
+    if (!s || !poses16) return set_err(PTL_ERR_ARG, "null argument");
+    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_smooth: an ICP-only sequence has no filter to smooth");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return ekf_smooth_impl(s->ekf, "ptl_seq_smooth", poses16, ts, nav19, cov324, s->cfg.n_scans, n_rows);
+}
+extern "C" int ptl_seq_smoother_log(ptl_seq* s, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
+    if (!s || max_entries < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only sequence has no filter log");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return ekf_log_read(s->ekf, entries, max_entries, n_entries, overflow);
+}
 extern "C" int ptl_seq_copy_traj(ptl_seq* s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!s || !dst_device) return set_err(PTL_ERR_ARG, "null argument");
     if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "trajectory rows need with_ekf");
@@ -1524,6 +1656,11 @@ struct ptl_batch {
     size_t ev_used;
     double gn_ms;
     int64_t gn_launches;
+    // fixed-interval smoother (ptl_batch_smoother_enable): one k_ekf_smooth job per sequence, their status words side by side
+    EkfSmoothJob* d_sm_jobs;
+    long long* d_sm_info;
+    std::vector<long long> h_sm_info;
+    bool sm_done;  // the last ptl_batch_smooth succeeded and nothing ran since
 };
 
 // launch geometry: workgroups per team.  Lockstep (kx_assign): one team per sequence, 1 / 2 / 4 per XCD.  Free-running: 1 / 2 / 4
@@ -1586,6 +1723,8 @@ extern "C" int ptl_batch_destroy(ptl_batch* b) {
     if (b->d_status) (void)hipFree(b->d_status);
     if (b->d_flags) (void)hipFree(b->d_flags);
     if (b->h_flags) (void)hipHostFree(b->h_flags);
+    if (b->d_sm_jobs) (void)hipFree(b->d_sm_jobs);
+    if (b->d_sm_info) (void)hipFree(b->d_sm_info);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
     if (b->ev_gn) (void)hipEventDestroy(b->ev_gn);
     if (b->ev_side) (void)hipEventDestroy(b->ev_side);
@@ -1774,6 +1913,7 @@ static int batch_reset(ptl_batch* b) {
     b->next_scan = 0;
     b->n_out = 0;
     b->done_scans = 0;
+    b->sm_done = false;
     if (b->ring_lap != 0) { b->ring_lap = 0; b->ctx_dirty = true; }
     if (b->ring < b->cfg.n_scans)  // a ring that has been lapped no longer holds the run's first sweeps: they are uploaded again; else what is there stays
         for (int s = 0; s < b->S; ++s) if (b->up_hi[s] > b->ring) b->up_hi[s] = 0;
@@ -1907,6 +2047,7 @@ extern "C" int ptl_batch_team_workgroups(ptl_batch* b, int32_t* team_workgroups,
 extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
     if (!b || n < 0 || b->next_scan + n > b->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    b->sm_done = false;
     if (b->ctx_dirty) { int rc = batch_push_ctx(b); if (rc) return rc; }
     if (b->free_running) return batch_enqueue_free(b, n);
     if (b->S > 32) return set_err(PTL_ERR_ARG, "the lockstep driver serves up to 32 sequences (four per XCD); %d need the free-running one", b->S);
@@ -2115,6 +2256,69 @@ extern "C" int ptl_batch_results(ptl_batch* b, int32_t s, double* res_poses, dou
     }
     if (n_out) *n_out = n;
     return PTL_OK;
+}
+extern "C" int ptl_batch_smoother_enable(ptl_batch* b, int32_t on) {
+    if (!b) return set_err(PTL_ERR_ARG, "null argument");
+    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_batch_smoother_enable: ICP-only sequences (with_ekf = 0) have no filter to smooth");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->side));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->sm_done = false;
+    if (b->d_sm_jobs) { (void)hipFree(b->d_sm_jobs); b->d_sm_jobs = nullptr; }
+    if (b->d_sm_info) { (void)hipFree(b->d_sm_info); b->d_sm_info = nullptr; }
+    for (int s = 0; s < b->S; ++s) {
+        int rc = ekf_log_set(b->ekf[s], on ? b->cfg.n_scans : 0);
+        if (rc) {
+            for (int q = 0; q < s; ++q) (void)ekf_log_set(b->ekf[q], 0);
+            return rc;
+        }
+    }
+    if (!on) return PTL_OK;
+    if (dalloc(&b->d_sm_jobs, (size_t)b->S) != hipSuccess || dalloc(&b->d_sm_info, (size_t)b->S * 2) != hipSuccess) {
+        for (int q = 0; q < b->S; ++q) (void)ekf_log_set(b->ekf[q], 0);
+        return set_err(PTL_ERR_HIP, "smoother job allocation failed");
+    }
+    std::vector<EkfSmoothJob> jobs((size_t)b->S);
+    for (int s = 0; s < b->S; ++s) {
+        jobs[(size_t)s] = b->ekf[s]->job;
+        jobs[(size_t)s].info = b->d_sm_info + 2 * s;  // every status word in one copy
+    }
+    b->h_sm_info.assign((size_t)b->S * 2, 0);
+    HIPCHK(hipMemcpy(b->d_sm_jobs, jobs.data(), jobs.size() * sizeof(EkfSmoothJob), hipMemcpyHostToDevice));
+    return PTL_OK;
+}
+extern "C" int ptl_batch_smooth(ptl_batch* b) {
+    if (!b) return set_err(PTL_ERR_ARG, "null argument");
+    if (!b->d_sm_jobs) return set_err(PTL_ERR_STATE, "ptl_batch_smooth: the smoother is not enabled (ptl_batch_smoother_enable)");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    b->sm_done = false;
+    HIPCHK(hipStreamSynchronize(b->side));
+    k_ekf_smooth<<<b->S, EKF_SMOOTH_THREADS, 0, b->stream>>>(b->d_sm_jobs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_sm_info.data(), b->d_sm_info, (size_t)b->S * 2 * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int s = 0; s < b->S; ++s) {
+        const int rc = smooth_status(b->ekf[s], &b->h_sm_info[2 * (size_t)s], "ptl_batch_smooth", s);
+        if (rc) return rc;
+    }
+    b->sm_done = true;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_smoothed(ptl_batch* b, int32_t seq, double* poses16, double* ts, double* nav19, double* cov324, int64_t* n_rows) {
+    if (!b || !poses16 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
+    if (!b->sm_done) return set_err(PTL_ERR_STATE, "ptl_batch_smoothed: no backward pass since the last run (ptl_batch_smooth)");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    const int64_t n = b->h_sm_info[2 * (size_t)seq + 1];
+    int rc = smooth_copy_out(b->ekf[seq], n, poses16, ts, nav19, cov324);
+    if (rc) return rc;
+    if (n_rows) *n_rows = n;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_smoother_log(ptl_batch* b, int32_t seq, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
+    if (!b || seq < 0 || seq >= b->S || max_entries < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->side));
+    return ekf_log_read(b->ekf[seq], entries, max_entries, n_entries, overflow);
 }
 extern "C" int ptl_batch_copy_traj(ptl_batch* b, int32_t s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!b || !dst_device || s < 0 || s >= b->S) return set_err(PTL_ERR_ARG, "bad argument");

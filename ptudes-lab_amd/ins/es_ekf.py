@@ -98,6 +98,15 @@ class ESEKF:
         self._ts = float(ts)
         self._nav_cache = None
 
+    # ------------------------------------------------------------------ fixed-interval smoother (not the plotting log `_logging`)
+    def enable_smoother(self, capacity: int) -> None:
+        """log the filter's history on the device for `capacity` pose updates (0 = off); the filter's outputs do not change"""
+        self._ekf.enable_smoother(capacity)
+
+    def smooth(self, nav: bool = True, cov: bool = True) -> dict:
+        """RTS-smoothed estimates at every logged update given all of them: dict(t, poses[, nav][, cov]), in update order"""
+        return self._ekf.smooth(nav=nav, cov=cov)
+
     def processPose(self, pose_corr: np.ndarray, meas_cov: Optional[np.ndarray] = None) -> None:
         """update step with a 4x4 pose measurement and optional 6x6 covariance (es_ekf.py:259-329)"""
         if self._logging:

@@ -17,7 +17,7 @@ from .kiss import KissICPWrapper
 
 
 def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use_imu_prediction=False,
-               guess_fn=None, logging=False, device_id=0, stats=None, lazy_map_stats=True, fused=None):
+               guess_fn=None, logging=False, device_id=0, stats=None, lazy_map_stats=True, fused=None, smooth=False):
     """Returns dict(res_t, res_poses, kiss_poses, kiss_icp, ekf, timings).  `guess_fn(ts)` (optional) supplies an
     external guess (the reference's --use-gt-guess, ekf_bench.py:536-542); `stats` (optional) is the StreamStatsTracker
     the loop feeds (ekf_bench.py:497-499, :522-524), its time goes into timings["track"].
@@ -29,13 +29,19 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
     samples between two scans is served (the entry point feeds what exceeds its staging buffer in chunks).
     timings: in the fused form `kiss` is the whole loop body of a scan (predicts + registration + update, one call) and `imu` /
     `corr` only count the host's hold-back (about 0): the reference's three per-stage means (ekf_bench.py:590-595) exist
-    separately only with fused=False; timings["fused"] says which form ran."""
+    separately only with fused=False; timings["fused"] says which form ran.
+    smooth: the filter logs its history (the event stream is read into a list first, to size the log by its scans) and the result
+    gains smoothed_poses / smoothed_t - the fixed-interval RTS smoother at every update (ESEKF.smooth), aligned with res_poses / res_t."""
+    if smooth:
+        events = list(events)
     if fused is None:
         fused = not logging
     # (the loop reads poses only - ekf_bench.py:549-563: the registration need not wait for its map update, lazy_map_stats)
     kiss_icp = KissICPWrapper(metadata, _use_extrinsics=True, _min_range=kiss_min_range, _max_range=kiss_max_range,
                               device_id=device_id, lazy_map_stats=lazy_map_stats)
     ekf = ESEKF(_logging=logging, device_id=device_id)
+    if smooth:
+        ekf.enable_smoother(max(1, sum(1 for ev in events if ev[0] != "imu")))
     res_t, res_poses, kiss_poses = [], [], []
     t_imu = t_corr = t_kiss = t_track = 0.0
     n_imu = n_corr = 0
@@ -123,7 +129,11 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
             ekf.processImu(i)
     timings = dict(imu=t_imu / max(n_imu, 1), corr=t_corr / max(n_corr, 1), kiss=t_kiss / max(n_corr, 1),
                    track=t_track / max(n_corr, 1), n_imu=n_imu, n_corr=n_corr, fused=bool(fused))
-    return dict(res_t=res_t, res_poses=res_poses, kiss_poses=kiss_poses, kiss_icp=kiss_icp, ekf=ekf, timings=timings)
+    out = dict(res_t=res_t, res_poses=res_poses, kiss_poses=kiss_poses, kiss_icp=kiss_icp, ekf=ekf, timings=timings)
+    if smooth:
+        sm = ekf.smooth(nav=False, cov=False)
+        out.update(smoothed_poses=sm["poses"], smoothed_t=sm["t"])
+    return out
 
 
 def synthetic_events(seq, n_scans=None):
@@ -136,8 +146,9 @@ def synthetic_events(seq, n_scans=None):
         yield ("scan", seq.scan(k), None, float(seq.t_base + (k + 1) * seq.scan_dt))
 
 
-def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, device_id=0, **icp_over):
-    """Upload a synth.Sequence and run the loop on device.  Returns the SeqRunner results dict + 'seconds'."""
+def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, device_id=0, smooth=False, **icp_over):
+    """Upload a synth.Sequence and run the loop on device.  Returns the SeqRunner results dict + 'seconds'; smooth=True adds
+    smoothed_poses / smoothed_t (SeqRunner.smooth, rows aligned with res_poses / res_t)."""
     n = seq.n_scans if n_scans is None else n_scans
     n_imu = seq.imu_range_for_scan(n - 1)[1] if with_ekf else 0
     r = core.SeqRunner(n, seq.H * seq.W, n_imu, max_range=seq.max_range, min_range=seq.min_range,
@@ -147,9 +158,14 @@ def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, 
         r.upload_scan(k, seq.scan(k))
     ends = [seq.imu_range_for_scan(k)[1] if with_ekf else 0 for k in range(n)]
     r.upload_imu(seq.imu[:n_imu] if with_ekf else np.zeros((0, 7)), ends)
+    if smooth:
+        r.enable_smoother(True)
     t0 = time.perf_counter()
     r.run()
     out = r.results()
     out["seconds"] = time.perf_counter() - t0
     out["runner"] = r
+    if smooth:
+        sm = r.smooth(nav=False, cov=False)
+        out.update(smoothed_poses=sm["poses"], smoothed_t=sm["t"])
     return out
