@@ -477,6 +477,57 @@ int ptl_gather_trajectories(ptl_comm *c, const double *d_rows, int64_t S, int64_
  * rows_out [world][n_sequences][n_scans][8], counts_out [world][n_sequences] */
 int ptl_batch_gather_trajectories(ptl_batch *b, ptl_comm *c, double *rows_out, int64_t *counts_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * IMU deskew (no reference counterpart: kiss-icp deskews with its constant-velocity model).  Optional, for the
+ * filter-coupled paths: the fused per-call step, ptl_seq_* and ptl_batch_* under both drivers.  Off: nothing changes, bit for bit.
+ *
+ * Knots.  The filter records (ts, pos[3], q xyzw[4]) of its nominal pose (world <- body, ptl_ekf_pose_mat's convention): knot 0 is the
+ * state right after the most recent pose update (before any update: after the filter's first IMU sample), then one knot per IMU sample
+ * consumed after it, taken after that sample's mechanisation; a sample whose ts does not exceed the previous knot's adds none.  Every pose
+ * update restarts the list.  A knot that does not fit raises the overflow flag (sticky until a cold start): the run then returns
+ * PTL_ERR_CAPACITY, and the scans that follow are not deskewed.
+ * Sweep times.  Per scan, absolute (t0, t1) on the IMU clock; column j (t01 = j / W) is at t_j = t0 + (j / W)(t1 - t0).
+ * Reference instant.  t_ref = the last knot's time = the filter's time at this scan's update (= res_t): column j is moved by
+ * M_j = T(t_ref)^-1 T(t_j), so the registered pose, the IMU-prediction guess and the filter update refer to one instant (the constant-
+ * velocity mode refers to mid-sweep).
+ * Interpolation.  T(t) = P_i Exp(a Log(P_i^-1 P_i+1)), a = (t - kt_i) / (kt_i+1 - kt_i), i the largest index with kt_i <= t clamped to
+ * [0, n - 2] (ptl_traj_poses_at's form); outside the knots the end segment's twist extrapolates, by at most the largest knot interval.
+ * Fallback.  Fewer than 2 knots, an overflowed list, or a column beyond that bound: no deskew for the scan (mode 0, like kiss-icp's first
+ * two scans).  ptl_*_deskew_modes give the mode per scan: 0 none, 1 constant velocity, 2 IMU.
+ * Refused (PTL_ERR_ARG / PTL_ERR_STATE, the handle stays usable): the mode without a filter (with_ekf = 0) or with deskew off, explicit
+ * per-point t01, a run without sweep times, a knot capacity below what the IMU samples between two scans need, and (ptl_seq) a scan
+ * without a new IMU sample (the driver loop would skip it).  Enable at a cold start: a reset keeps the mode, the knot list starts empty. */
+#define PTL_KNOT_STRIDE 8   /* doubles per knot: */
+#define PTL_KNOT_TS 0       /* the filter's time */
+#define PTL_KNOT_POS 1      /* pos[3], world */
+#define PTL_KNOT_Q 4        /* q xyzw[4], world <- body */
+#define PTL_DESKEW_NONE 0
+#define PTL_DESKEW_CV 1
+#define PTL_DESKEW_IMU 2
+/* capacity >= 2: a fresh, empty knot list (0 = off, frees it); the raw list, up to max_knots knots (n_knots: its length) */
+int ptl_ekf_knots_enable(ptl_ekf *h, int64_t capacity);
+int ptl_ekf_knots(ptl_ekf *h, double *knots, int64_t max_knots, int64_t *n_knots, int32_t *overflow);
+/* ptl_icp_ekf_step with the scan's table from the filter's knots (the filter needs ptl_ekf_knots_enable with capacity >= n_imu + 1):
+ * sweep times t0 <= t1 instead of t01; the prologue waits for the predicts instead of running beside them.  The handle's other entry
+ * points keep the constant-velocity deskew. */
+int ptl_icp_ekf_step_imu_deskew(ptl_icp *icp, ptl_ekf *ekf, const double *imu_rows, int64_t n_imu, const void *xyz, int dtype, int64_t n,
+                                double t0, double t1, const double *guess, int32_t use_imu_prediction, double kiss_pose[16],
+                                double ekf_pose[16], double *ekf_ts, ptl_icp_stats *stats);
+/* mode per registered scan of a per-call handle (n: scans written); the current column table, 12 x W doubles entry-major (R row-major 9,
+ * t 3; entry q of column j at [q W + j]), for tests */
+int ptl_icp_deskew_modes(ptl_icp *h, int32_t *modes, int64_t max_n, int64_t *n);
+int ptl_icp_column_table(ptl_icp *h, double *out);
+/* the sequence runner: on / off (knot_capacity for the filter's list), sweep times (n_scans x 2), modes of the scans run, raw knots */
+int ptl_seq_imu_deskew_enable(ptl_seq *s, int32_t on, int64_t knot_capacity);
+int ptl_seq_upload_sweep_times(ptl_seq *s, const double *t0t1);
+int ptl_seq_deskew_modes(ptl_seq *s, int32_t *modes, int64_t max_n, int64_t *n);
+int ptl_seq_knots(ptl_seq *s, double *knots, int64_t max_knots, int64_t *n_knots, int32_t *overflow);
+/* ... every sequence of a batch (sweep times stay resident for all n_scans, also with the sweep ring: 16 B per scan) */
+int ptl_batch_imu_deskew_enable(ptl_batch *b, int32_t on, int64_t knot_capacity);
+int ptl_batch_upload_sweep_times(ptl_batch *b, int32_t seq, const double *t0t1);
+int ptl_batch_deskew_modes(ptl_batch *b, int32_t seq, int32_t *modes, int64_t max_n, int64_t *n);
+int ptl_batch_knots(ptl_batch *b, int32_t seq, double *knots, int64_t max_knots, int64_t *n_knots, int32_t *overflow);
+
 #ifdef __cplusplus
 }
 #endif

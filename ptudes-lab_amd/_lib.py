@@ -154,6 +154,21 @@ PROTOTYPES = {
     "ptl_batch_smooth": (C.c_int, [_vp]),
     "ptl_batch_smoothed": (C.c_int, [_vp, C.c_int32, c_d_p, c_d_p, c_d_p, c_d_p, c_i64_p]),
     "ptl_batch_smoother_log": (C.c_int, [_vp, C.c_int32, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
+    # IMU deskew (include/ptudes_mi.h)
+    "ptl_ekf_knots_enable": (C.c_int, [_vp, C.c_int64]),
+    "ptl_ekf_knots": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_icp_ekf_step_imu_deskew": (C.c_int, [_vp, _vp, c_d_p, C.c_int64, _vp, C.c_int, C.c_int64, C.c_double, C.c_double, c_d_p, C.c_int32,
+                                              c_d_p, c_d_p, c_d_p, C.POINTER(IcpStats)]),
+    "ptl_icp_deskew_modes": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int64, c_i64_p]),
+    "ptl_icp_column_table": (C.c_int, [_vp, c_d_p]),
+    "ptl_seq_imu_deskew_enable": (C.c_int, [_vp, C.c_int32, C.c_int64]),
+    "ptl_seq_upload_sweep_times": (C.c_int, [_vp, c_d_p]),
+    "ptl_seq_deskew_modes": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int64, c_i64_p]),
+    "ptl_seq_knots": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_batch_imu_deskew_enable": (C.c_int, [_vp, C.c_int32, C.c_int64]),
+    "ptl_batch_upload_sweep_times": (C.c_int, [_vp, C.c_int32, c_d_p]),
+    "ptl_batch_deskew_modes": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, c_i64_p]),
+    "ptl_batch_knots": (C.c_int, [_vp, C.c_int32, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -227,14 +227,21 @@ def _synthetic_source(seed: int, n_scans: int):
 @click.option("--save-smoothed-poses", required=False, type=click.Path(exists=False, dir_okay=False),
               help="also run the fixed-interval RTS smoother over the whole run and write its poses to this file, Newer College "
                    "ground-truth format, with the timestamps of --save-nc-gt-poses; with -g, print its ATE")
+@click.option("--imu-deskew", is_flag=True,
+              help="deskew every sweep with the filter's IMU-propagated trajectory instead of KissICP's constant-velocity model "
+                   "(the fused loop only; the call-by-call form, e.g. with -p, stays constant-velocity); needs --synthetic: "
+                   "the sweep times of real recordings are not decoded here")
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
-                      kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None) -> None:
+                      kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None,
+                      imu_deskew: bool = False) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
     from ..utils import TrajectoryEvaluator, active_beam_rows
+    if imu_deskew and (synthetic is None or plot):
+        raise click.ClickException("--imu-deskew needs --synthetic and the fused loop (no -p)")
     if not gt_file and use_gt_guess:  # reference :416-418
         print("ERROR: --use-gt-guess requires the GT poses (--gt-file)")
         raise SystemExit(1)
@@ -311,7 +318,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
     stats = StreamStatsTracker(use_beams_num=32, metadata=info)  # reference :457
     out = run_events(feed(), info, kiss_min_range=kiss_min_range, kiss_max_range=kiss_max_range,
                      use_imu_prediction=use_imu_prediction, guess_fn=guess_fn, logging=log_metrics, stats=stats,
-                     smooth=bool(save_smoothed_poses))
+                     smooth=bool(save_smoothed_poses), imu_deskew=imu_deskew,
+                     sweep_time_fn=(lambda ts: (ts - seq.scan_dt, ts)) if imu_deskew else None)
     res_t, res_poses, kiss_poses = out["res_t"], out["res_poses"], out["kiss_poses"]
     header = display_header + f"(scans/updates num: {len(res_poses)})\n"
     header += "time: " + datetime.now().strftime("%Y%m%d_%H%M%S")

@@ -129,6 +129,21 @@ class Icp:
     def last_source(self):
         return self._cloud(L.lib().ptl_icp_last_source)
 
+    def deskew_modes(self):
+        """deskew mode per registered scan (0 none, 1 constant velocity, 2 IMU); include/ptudes_mi.h ptl_icp_deskew_modes"""
+        return _modes(self.num_poses, lambda p, m, w: L.lib().ptl_icp_deskew_modes(self._h, p, m, w))
+
+    def column_table(self):
+        """the current per-column deskew table as (W, 4, 4) transforms"""
+        W = self.cfg.scan_cols
+        raw = np.empty(12 * W)
+        L.check(L.lib().ptl_icp_column_table(self._h, L.dptr(raw)))
+        raw = raw.reshape(12, W)
+        T = np.tile(np.eye(4), (W, 1, 1))
+        T[:, :3, :3] = raw[:9].T.reshape(W, 3, 3)
+        T[:, :3, 3] = raw[9:].T
+        return T
+
     def deskew(self, xyz, t01):
         x, t = L.as_f64(xyz), L.as_f64(t01)
         out = np.empty_like(x)
@@ -281,6 +296,42 @@ class Ekf:
                          lambda p, t, n, c, w: L.lib().ptl_ekf_smooth(self._h, p, t, n, c, getattr(self, "_sm_cap", 0), w))
 
 
+    def enable_knots(self, capacity):
+        """a fresh, empty knot list of the IMU deskew for `capacity` knots (0 = off); include/ptudes_mi.h ptl_ekf_knots_enable"""
+        L.check(L.lib().ptl_ekf_knots_enable(self._h, int(capacity)))
+        self._knot_cap = int(capacity)
+
+    def knots(self):
+        """the raw knot list: ((n, 8) array [ts, pos(3), q xyzw(4)], overflow flag)"""
+        return _knots(getattr(self, "_knot_cap", 0), lambda p, m, n, o: L.lib().ptl_ekf_knots(self._h, p, m, n, o))
+
+
+# one knot of the IMU deskew (include/ptudes_mi.h PTL_KNOT_*)
+KNOT_STRIDE = 8
+DESKEW_NONE, DESKEW_CV, DESKEW_IMU = 0, 1, 2
+
+
+def _knots(cap, call):
+    raw = np.zeros((max(int(cap), 1), KNOT_STRIDE))
+    n, ovf = C.c_int64(), C.c_int32()
+    L.check(call(L.dptr(raw), raw.shape[0], C.byref(n), C.byref(ovf)))
+    return raw[:min(n.value, raw.shape[0])].copy(), bool(ovf.value)
+
+
+def _modes(n, call):
+    out = np.zeros(max(int(n), 1), dtype=np.int32)
+    w = C.c_int64()
+    L.check(call(out.ctypes.data_as(C.POINTER(C.c_int32)), len(out), C.byref(w)))
+    return out[:w.value].copy()
+
+
+def _sweep_times(t0t1, n_scans):
+    t = L.as_f64(t0t1).reshape(-1, 2)
+    if len(t) != n_scans:
+        raise ValueError("sweep times: one (t0, t1) row per scan")
+    return np.ascontiguousarray(t)
+
+
 def _smoothed(cap, nav, cov, call):
     """one smoothing call with `cap`-row host buffers -> dict(t, poses, nav?, cov?) of the rows written"""
     cap = max(int(cap), 1)
@@ -315,11 +366,13 @@ def _smoother_log(cap, call):
     return out
 
 
-def icp_ekf_step(icp: "Icp", ekf: "Ekf", imu_rows, xyz, t01=None, guess=None, use_imu_prediction=False):
+def icp_ekf_step(icp: "Icp", ekf: "Ekf", imu_rows, xyz, t01=None, guess=None, use_imu_prediction=False, sweep=None):
     """One scan of the reference's loop body (cli/ekf_bench.py:493-563) in one host round trip (include/ptudes_mi.h ptl_icp_ekf_step):
     the IMU rows [ts, lacc, avel] that precede the scan, the registration (guess: the filter's pose when use_imu_prediction, else
     `guess` / constant velocity), the filter's update with the new pose.  Returns (kiss_pose, ekf_pose, ekf_ts); the stats row is
-    appended to icp.stats like register_frame does."""
+    appended to icp.stats like register_frame does.
+    sweep=(t0, t1): IMU deskew - the scan's column table from the filter's knots (ekf.enable_knots first), sweep times on the IMU clock
+    instead of t01 (include/ptudes_mi.h ptl_icp_ekf_step_imu_deskew)."""
     rows = L.as_f64(imu_rows).reshape(-1, 7) if len(imu_rows) else np.zeros((0, 7))
     xyz = np.asarray(xyz)
     if xyz.dtype == np.float32:
@@ -333,6 +386,14 @@ def icp_ekf_step(icp: "Icp", ekf: "Ekf", imu_rows, xyz, t01=None, guess=None, us
         raise ValueError("t01 must have one entry per point")
     g = None if guess is None else L.as_f64(guess).reshape(16)
     kiss, pose, ts, st = np.empty((4, 4)), np.empty((4, 4)), C.c_double(), L.IcpStats()
+    if sweep is not None:
+        if t is not None:
+            raise ValueError("IMU deskew takes sweep times, not per-point t01")
+        L.check(L.lib().ptl_icp_ekf_step_imu_deskew(icp._h, ekf._h, L.dptr(rows) if len(rows) else None, len(rows), x.ctypes.data_as(C.c_void_p),
+                                                    dt, len(x), float(sweep[0]), float(sweep[1]), None if g is None else L.dptr(g),
+                                                    int(bool(use_imu_prediction)), L.dptr(kiss), L.dptr(pose), C.byref(ts), C.byref(st)))
+        icp.stats.append(st.as_dict())
+        return kiss, pose, ts.value
     L.check(L.lib().ptl_icp_ekf_step(icp._h, ekf._h, L.dptr(rows) if len(rows) else None, len(rows), x.ctypes.data_as(C.c_void_p), dt, len(x),
                                      None if t is None else L.dptr(t), None if g is None else L.dptr(g), int(bool(use_imu_prediction)),
                                      L.dptr(kiss), L.dptr(pose), C.byref(ts), C.byref(st)))
@@ -359,7 +420,9 @@ class SeqRunner:
     """Whole sequence in HBM, no host round trip per scan."""
 
     def __init__(self, n_scans, points_per_scan, n_imu, *, max_range=70.0, min_range=1.0, use_imu_prediction=False,
-                 with_ekf=True, device_id=0, ekf=None, **icp_over):
+                 with_ekf=True, device_id=0, ekf=None, imu_deskew=False, knot_capacity=None, **icp_over):
+        """imu_deskew: the column tables from the filter's IMU-propagated trajectory (upload_sweep_times before running; knot_capacity
+        defaults to n_imu + 1, enough for any split of the samples; include/ptudes_mi.h ptl_seq_imu_deskew_enable)"""
         cfg = L.SeqCfg()
         cfg.icp = icp_cfg(max_range, min_range, device_id=device_id, **icp_over)
         cfg.ekf = ekf if ekf is not None else ekf_cfg(device_id=device_id)
@@ -370,6 +433,29 @@ class SeqRunner:
         self._h = C.c_void_p()
         L.check(L.lib().ptl_seq_create(C.byref(cfg), C.byref(self._h)))
         self.n_scans = n_scans
+        self.knot_capacity = 0
+        if imu_deskew:
+            try:
+                self.imu_deskew(True, knot_capacity)
+            except Exception:
+                self.close()
+                raise
+
+    def imu_deskew(self, on=True, knot_capacity=None):
+        cap = int(self.cfg.n_imu) + 1 if knot_capacity is None else int(knot_capacity)
+        L.check(L.lib().ptl_seq_imu_deskew_enable(self._h, int(bool(on)), cap if on else 0))
+        self.knot_capacity = cap if on else 0
+
+    def upload_sweep_times(self, t0t1):
+        """(n_scans, 2) absolute (t0, t1) per sweep on the IMU clock"""
+        t = _sweep_times(t0t1, self.n_scans)
+        L.check(L.lib().ptl_seq_upload_sweep_times(self._h, L.dptr(t)))
+
+    def deskew_modes(self):
+        return _modes(self.n_scans, lambda p, m, w: L.lib().ptl_seq_deskew_modes(self._h, p, m, w))
+
+    def knots(self):
+        return _knots(self.knot_capacity, lambda p, m, n, o: L.lib().ptl_seq_knots(self._h, p, m, n, o))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -464,7 +550,7 @@ class BatchRunner:
 
     def __init__(self, n_sequences, n_scans, points_per_scan, n_imu, *, max_range=70.0, min_range=1.0,
                  use_imu_prediction=False, with_ekf=True, device_id=0, ekf=None, free_running=None, scans_per_launch=0,
-                 team_workgroups=0, range_input=False, resident_scans=0, **icp_over):
+                 team_workgroups=0, range_input=False, resident_scans=0, imu_deskew=False, knot_capacity=None, **icp_over):
         """range_input: every sweep will arrive as a raw range image (set_lut + upload_range) and stays one in HBM - 4 bytes per pixel
         resident instead of 12 (include/ptudes_mi.h ptl_seq_cfg.range_input).  resident_scans: R >= 2 = a ring of R sweep slots per sequence
         instead of all n_scans - sweeps are uploaded in order, later ones while a launch works on earlier ones (ptl_seq_cfg.resident_scans)"""
@@ -487,6 +573,29 @@ class BatchRunner:
             L.check(L.lib().ptl_batch_set_driver(self._h, int(self.free_running), int(scans_per_launch)))
         if team_workgroups:
             L.check(L.lib().ptl_batch_set_team_workgroups(self._h, int(team_workgroups)))
+        self.knot_capacity = 0
+        if imu_deskew:
+            try:
+                self.imu_deskew(True, knot_capacity)
+            except Exception:
+                self.close()
+                raise
+
+    def imu_deskew(self, on=True, knot_capacity=None):
+        """IMU deskew for every sequence (upload_sweep_times(s, ...) for each before running); include/ptudes_mi.h ptl_batch_imu_deskew_enable"""
+        cap = int(self.cfg.n_imu) + 1 if knot_capacity is None else int(knot_capacity)
+        L.check(L.lib().ptl_batch_imu_deskew_enable(self._h, int(bool(on)), cap if on else 0))
+        self.knot_capacity = cap if on else 0
+
+    def upload_sweep_times(self, s, t0t1):
+        t = _sweep_times(t0t1, self.n_scans)
+        L.check(L.lib().ptl_batch_upload_sweep_times(self._h, int(s), L.dptr(t)))
+
+    def deskew_modes(self, s):
+        return _modes(self.n_scans, lambda p, m, w: L.lib().ptl_batch_deskew_modes(self._h, int(s), p, m, w))
+
+    def knots(self, s):
+        return _knots(self.knot_capacity, lambda p, m, n, o: L.lib().ptl_batch_knots(self._h, int(s), p, m, n, o))
 
     def set_driver(self, free_running, scans_per_launch=0, team_workgroups=None):
         """choose the driver (and the team size) again for the same handle and sweeps: back to the cold start first"""

@@ -38,7 +38,15 @@ struct EkfState {
     double* log;
     long long log_cap, log_count;
     int log_overflow, log_pad;
+    // Knot list of the IMU deskew, off while `knots` is null: EKF_KNOT_STRIDE doubles per knot, (ts, pos[3], q xyzw[4])
+    // of the nominal state right after the last pose update (before the first update: after the first IMU sample), then after every
+    // later sample whose ts exceeds the previous knot's.  A pose update restarts the list; a knot that does not fit raises
+    // knot_overflow (sticky until a cold start) and is dropped.
+    double* knots;
+    long long knot_cap, knot_count;
+    int knot_overflow, knot_pad;
 };
+#define EKF_KNOT_STRIDE 8
 // one log entry (doubles): ts | nav before the update (19: pos, q xyzw, vel, bg, ba, grav) | P before | Phi since the previous
 // logged update | nav after (inject + PHI-block projection + reset) | P after; 1011 used, padded to 8 KB
 #define EKF_LOG_STRIDE 1024
@@ -52,6 +60,12 @@ struct EkfState {
 __device__ __forceinline__ void ekf_nav19(const EkfNav& n, double* o) {
     for (int k = 0; k < 3; ++k) { o[k] = n.pos[k]; o[7 + k] = n.vel[k]; o[10 + k] = n.bg[k]; o[13 + k] = n.ba[k]; o[16 + k] = n.grav[k]; }
     for (int k = 0; k < 4; ++k) o[3 + k] = n.q[k];
+}
+
+__device__ __forceinline__ void ekf_knot8(const EkfNav& n, double* o) {
+    o[0] = n.cur_ts;
+    for (int k = 0; k < 3; ++k) o[1 + k] = n.pos[k];
+    for (int k = 0; k < 4; ++k) o[4 + k] = n.q[k];
 }
 
 __device__ __forceinline__ void ekf_write_pose(EkfState* e) {
@@ -91,6 +105,7 @@ __global__ void k_ekf_init(EkfState* e, const double* grav, const double* bacc, 
     // a cold start empties the log (its buffer and capacity stay)
     for (int i = 0; i < EKF_N * EKF_N; ++i) e->Phi[i] = (i % (EKF_N + 1) == 0) ? 1.0 : 0.0;
     e->log_count = 0; e->log_overflow = 0;
+    e->knot_count = 0; e->knot_overflow = 0;  // ... and the knot list
     for (int i = 0; i < 3; ++i) { e->nav.cur_lacc[i] = 0.0; e->nav.cur_avel[i] = 0.0; }
     ekf_write_pose(e);
 }
@@ -155,6 +170,13 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
         if (cell) sPhi[tid] = e->Phi[tid];
     }
     double phin = 0.0;
+    double* const kn = e->knots;  // uniform: the IMU deskew's knot list, null = off
+    long long kcount = 0;         // (the mechanisation lane's copy is the one that counts; a pose update resets every copy)
+    double klast = 0.0;           // time of the last knot
+    if (kn) {
+        kcount = e->knot_count;
+        if (kcount > 0) klast = kn[EKF_KNOT_STRIDE * (kcount - 1)];
+    }
     if (tid == 0) s_lastbuf = 0;
     // the mechanisation (one lane) runs in a wavefront of its own when the launch has one to spare, so that it overlaps
     // the covariance products instead of preceding them
@@ -218,6 +240,15 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
                             R_to_quat(Rn, nv.q);
                         }
                         sAct[bj] = act_j;
+                        if (kn && (kcount == 0 || nv.cur_ts > klast)) {  // the knot of this sample
+                            if (kcount < e->knot_cap) {
+                                ekf_knot8(nv, kn + EKF_KNOT_STRIDE * kcount);
+                                kcount += 1;
+                                klast = nv.cur_ts;
+                            } else {
+                                e->knot_overflow = 1;
+                            }
+                        }
                     }
                     if (prev_active && cell) {
                         // P = Fx P Fx^T + W (:235), dense like the reference.  Only the structurally non-zero columns of
@@ -406,8 +437,10 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
                 for (int k = 0; k < 3; ++k) out_row8[1 + k] = nv.pos[k];
                 for (int k = 0; k < 4; ++k) out_row8[4 + k] = nv.q[k];
             }
+            if (kn) ekf_knot8(nv, kn);  // the knot list starts again with the state after the update
         }
         __syncthreads();
+        if (kn) { kcount = 1; klast = nv.cur_ts; }
         if (lg) {  // the state after the update; Phi starts again
             if (logit) {
                 if (cell) ent[EKF_LOG_P_POST + tid] = sP[tid];
@@ -425,6 +458,7 @@ __device__ __forceinline__ void d_ekf_step(EkfState* e, const double* imu, int i
         if (cell) e->Phi[tid] = sPhi[tid];
         if (tid == 0) e->log_count = lcount;
     }
+    if (kn && tid == TS) e->knot_count = kcount;
 }
 
 #define EKF_THREADS 448  /* 324 covariance cells (six wavefronts) + a seventh wavefront for the mechanisation lane */

@@ -111,7 +111,17 @@ struct DevState {
     // 8-lane Gauss-Newton loop, cumulative like exec_cnt: point-iterations settled as "nothing in reach" (the point's last search found its 27
     // voxels empty and it has not left its voxel since: no row evaluation, no search)
     unsigned long long empty_cnt;
+    // IMU deskew, off while dk_knots is null; a cold start (k_state_init) keeps these
+    const double* dk_knots;       // the filter's knot list, [cap][8]: ts, pos[3], q xyzw[4] (EkfState::knots)
+    const long long* dk_nknots;   // ... its length (EkfState::knot_count)
+    const int* dk_kovf;           // ... its overflow flag (EkfState::knot_overflow)
+    const double* dk_t0t1;        // [dk_n][2] absolute times of the first column and of the end of sweep k on the filter's clock
+    int* dk_modes;                // [dk_n] deskew of scan k: 0 none, 2 IMU (DK_MODE_*)
+    int dk_n, dk_pad;
 };
+#define DK_MODE_NONE 0
+#define DK_MODE_CV 1
+#define DK_MODE_IMU 2
 
 struct Ctx {
     // algorithm parameters
@@ -265,8 +275,71 @@ __device__ __forceinline__ void gn_ll_clear_on_wrap(const Ctx& c) {
     for (size_t i = threadIdx.x; i < n_rows; i += blockDim.x) c.gn_rows_ll[i] = 0ull;
     for (size_t i = threadIdx.x; i < n_xsum; i += blockDim.x) c.gn_xsum_ll[i] = 0ull;
 }
+// ------------------------------------------------------------------------------------------------ IMU deskew
+// The pose at time t on the knot list kn[0 .. n) (n >= 2): P_i Exp(a Log(P_i^-1 P_i+1)), a = (t - kt_i) / (kt_i+1 - kt_i), i the largest
+// index with kt_i <= t clamped to [0, n - 2] - k_traj_poses_at's form; outside the knots the end segment's twist extrapolates.
+__device__ __forceinline__ Rt dk_knot_pose(const double* k8) {
+    Rt o;
+    quat_to_R(k8 + 4, o.R);
+    for (int i = 0; i < 3; ++i) o.t[i] = k8[1 + i];
+    return o;
+}
+__device__ __forceinline__ Rt dk_pose_at(const double* kn, int n, double t) {
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (kn[8 * mid] <= t) lo = mid; else hi = mid;
+    }
+    const int i = lo < n - 1 ? lo : n - 2;
+    const double* a0 = kn + 8 * (size_t)i;
+    const double* a1 = a0 + 8;
+    const double alpha = (t - a0[0]) / (a1[0] - a0[0]);
+    const Rt P0 = dk_knot_pose(a0);
+    double xi[6];
+    se3_log(rt_mul(rt_inv(P0), dk_knot_pose(a1)), xi);
+    for (int k = 0; k < 6; ++k) xi[k] *= alpha;
+    return rt_mul(P0, se3_exp(xi));
+}
+// The column table of scan k from the filter's knots: column j at t_j = t0 + (j / W)(t1 - t0) gets M_j = T(t_ref)^-1 T(t_j), t_ref = the last
+// knot's time (the filter's time at this scan's update).  Fewer than 2 knots, a knot list that overflowed, no sweep times for scan k, a
+// column further than the largest knot interval outside the knots: no deskew (mode 0).  Every thread of the workgroup calls it; a
+// separate function so that the registers of the prologue's callers do not depend on it (scalar arguments only: a Ctx passed by
+// reference would have to live in the caller's scratch).
+__device__ __noinline__ void d_imu_coltab(DevState* st, double* coltab, int W, int deskew, int k) {
+    const double* kn = st->dk_knots;
+    const int n = (int)*st->dk_nknots;
+    bool on = deskew && k < st->dk_n && *st->dk_kovf == 0 && n >= 2;
+    double t0 = 0.0, t1 = 0.0;
+    const double inv_w = 1.0 / (double)W;
+    if (on) {
+        t0 = st->dk_t0t1[2 * (size_t)k]; t1 = st->dk_t0t1[2 * (size_t)k + 1];
+        double dmax = 0.0;
+        for (int i = 0; i + 1 < n; ++i) dmax = fmax(dmax, kn[8 * (i + 1)] - kn[8 * i]);
+        const double lo = kn[0] - dmax, hi = kn[8 * (n - 1)] + dmax;
+        const double ta = t0, tb = t0 + ((double)(W - 1) * inv_w) * (t1 - t0);
+        on = ta >= lo && ta <= hi && tb >= lo && tb <= hi;
+    }
+    if (on) {
+        const Rt Tinv = rt_inv(dk_pose_at(kn, n, kn[8 * (n - 1)]));
+        for (int j = threadIdx.x; j < W; j += blockDim.x) {
+            const double tj = t0 + ((double)j * inv_w) * (t1 - t0);
+            const Rt M = rt_mul(Tinv, dk_pose_at(kn, n, tj));
+            double* o = coltab + (size_t)j;
+            for (int q = 0; q < 9; ++q) o[(size_t)q * W] = M.R[q];
+            for (int q = 0; q < 3; ++q) o[(size_t)(9 + q) * W] = M.t[q];
+        }
+    }
+    if (threadIdx.x == 0) {
+        st->do_deskew = on ? 1 : 0;
+        if (k < st->dk_n) st->dk_modes[k] = on ? DK_MODE_IMU : DK_MODE_NONE;
+    }
+}
+
 // keep_abort: the caller runs beside workgroups that may still poll the sequence's abort word (the free-running kernel's filter
 // workgroup runs scan k + 1's prologue during scan k's map update): an abort raised there must not be erased
+// IMU: the IMU deskew may be wired (DevState::dk_knots, checked at run time); the per-stage kernels have an instance without it, so that a
+// prologue in constant-velocity mode carries no call (and none of its register and scratch cost)
+template <bool IMU = true>
 __device__ __forceinline__ void d_scan_prologue(const Ctx& c, const bool keep_abort = false) {
     DevState* st = c.st;
     // The pose block of the state (first, previous, last, new, model deviation: 80 doubles) is brought into LDS by 80
@@ -300,7 +373,7 @@ __device__ __forceinline__ void d_scan_prologue(const Ctx& c, const bool keep_ab
     st->gn_epoch = (st->gn_epoch + 1u) & 0x3FFFFFu;
     st->gn_iters = 0; st->gn_ncorr = 0; st->gn_cand = 0;
     if (!keep_abort) st->gn_abort = 0;
-    st->do_deskew = (c.deskew && n_poses >= 2) ? 1 : 0;
+    st->do_deskew = (c.deskew && n_poses >= 2 && !(IMU && st->dk_knots)) ? 1 : 0;  // (IMU deskew: d_imu_coltab decides)
     s_nposes = n_poses;
     __threadfence_block();
     }
@@ -353,6 +426,10 @@ __device__ __forceinline__ void d_scan_prologue(const Ctx& c, const bool keep_ab
     }
     __syncthreads();
     gn_ll_clear_on_wrap(c);
+    if (IMU && st->dk_knots) {  // (uniform) IMU deskew: the table from the filter's knots
+        d_imu_coltab(st, c.coltab, c.W, (c.deskew && c.t01 == nullptr) ? 1 : 0, n_poses);
+        return;
+    }
     // per-column deskew transforms Exp((j/W - 0.5) xi): only W distinct times exist in a sweep (kiss.py:34-35)
     if (st->do_deskew && c.t01 == nullptr) {
         double xi[6];
@@ -3161,10 +3238,15 @@ __device__ __forceinline__ Ctx load_seq_ctx(const SeqCtx* a, int s, int scan_k) 
     c.free_stack_s = uniform_ptr(c.free_stack_s); c.mig_list = uniform_ptr(c.mig_list);
     return c;
 }
-__global__ __launch_bounds__(1024) void k_scan_prologue(Ctx c) { d_scan_prologue(c); }
+__global__ __launch_bounds__(1024) void k_scan_prologue(Ctx c) { d_scan_prologue<false>(c); }
+__global__ __launch_bounds__(1024) void k_scan_prologue_imu(Ctx c) { d_scan_prologue<true>(c); }
 __global__ __launch_bounds__(1024) void kb_scan_prologue(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
-    d_scan_prologue(c);
+    d_scan_prologue<false>(c);
+}
+__global__ __launch_bounds__(1024) void kb_scan_prologue_imu(const SeqCtx* a, int scan_k) {
+    const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
+    d_scan_prologue<true>(c);
 }
 __global__ __launch_bounds__(256) void k_deskew_vds1(Ctx c) { d_deskew_vds1<1>(c, launch_slice()); }
 __global__ __launch_bounds__(256) void kb_deskew_vds1(const SeqCtx* a, int scan_k) {

@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
@@ -109,6 +110,14 @@ struct ptl_icp {
     double* fd_buf[2];
     double gn_ms;
     int64_t gn_launches;
+    // IMU deskew: the prologue waits for `pro_wait` (the filter's predicts through the sweep's samples); the per-call step's sweep times and
+    // recorded modes, one entry per scan (dk_cap entries, grown with the scans)
+    hipEvent_t pro_wait;
+    double* dk_t0t1;
+    int* dk_modes;
+    int64_t dk_cap;
+    bool dk_wired;                   // the device state holds the IMU deskew's wiring: the prologue runs its IMU instance
+    std::vector<signed char> dk_rec; // per registered scan (icp_enqueue_scan): its deskew mode, or -1 = IMU-wired (the device recorded it)
 };
 
 extern "C" int ptl_icp_default_cfg(ptl_icp_cfg* cfg, double max_range, double min_range) {
@@ -150,7 +159,7 @@ static int icp_free(ptl_icp* h) {
     Ctx& c = h->c;
     void* ptrs[] = {c.pts, c.slot1, c.slot2, c.vtab1, c.vtab2, c.bcnt1, c.bcnt2, h->fd_buf[0], h->fd_buf[1], c.src0,
                     c.src_cur, c.fdw, c.coltab, c.pslot, c.nxt, c.prank, c.plen, c.tab, c.blocks, c.bhdr, c.bfirst, c.free_stack, c.free_stack_s, c.mig_list, c.wg_clk, c.pc_key, c.pc_pb, c.pc_ans, c.gn_rows_ll, c.gn_xsum_ll,
-                    c.st, c.traj, c.sstats, h->d_in, h->d_t01, h->d_ext, h->d_counter, h->d_row_mask};
+                    c.st, c.traj, c.sstats, h->d_in, h->d_t01, h->d_ext, h->d_counter, h->d_row_mask, h->dk_t0t1, h->dk_modes};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -169,7 +178,13 @@ __global__ void k_fill_free_stack(int* fs, int n, int base) {
 }
 __global__ void k_state_init(DevState* st, int n_full, int n_small) {
     if (threadIdx.x || blockIdx.x) return;
+    const double *dk_knots = st->dk_knots, *dk_t0t1 = st->dk_t0t1;  // the IMU deskew's wiring survives a cold start
+    const long long* dk_nknots = st->dk_nknots;
+    const int* dk_kovf = st->dk_kovf;
+    int* dk_modes = st->dk_modes;
+    const int dk_n = st->dk_n;
     memset(st, 0, sizeof(DevState));
+    st->dk_knots = dk_knots; st->dk_t0t1 = dk_t0t1; st->dk_nknots = dk_nknots; st->dk_kovf = dk_kovf; st->dk_modes = dk_modes; st->dk_n = dk_n;
     Rt I = rt_identity();
     rt_to16(I, st->pose_first); rt_to16(I, st->pose_prev); rt_to16(I, st->pose_last);
     rt_to16(I, st->model_dev); rt_to16(I, st->guess); rt_to16(I, st->new_pose); rt_to16(I, st->T_icp);
@@ -214,6 +229,7 @@ static int icp_reset_device(ptl_icp* h) {
     h->ev_gn_valid = false; h->ev_map_valid = false;
     h->scans_done = 0;
     h->last_n = 0;
+    h->dk_rec.clear();
     return PTL_OK;
 }
 
@@ -266,6 +282,7 @@ static int icp_create_impl(const ptl_icp_cfg* cfg, hipStream_t shared_stream, pt
     h->ev_gn = nullptr;
     h->ev_gn_valid = false; h->fd_buf[0] = h->fd_buf[1] = nullptr;
     h->d_in = nullptr; h->d_t01 = nullptr; h->d_ext = nullptr; h->d_counter = nullptr; h->d_row_mask = nullptr;
+    h->pro_wait = nullptr; h->dk_t0t1 = nullptr; h->dk_modes = nullptr; h->dk_cap = 0; h->dk_wired = false;
     memset(&h->c, 0, sizeof(Ctx));
     if (h->own_stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
@@ -325,7 +342,7 @@ static int icp_create_impl(const ptl_icp_cfg* cfg, hipStream_t shared_stream, pt
     ok &= dalloc(&c.gn_rows_ll, (size_t)2 * c.G * 64) == hipSuccess && hipMemset(c.gn_rows_ll, 0, (size_t)2 * c.G * 64 * 8) == hipSuccess;
     ok &= dalloc(&c.gn_xsum_ll, (size_t)2 * 8 * 8 * 64) == hipSuccess && hipMemset(c.gn_xsum_ll, 0, (size_t)2 * 8 * 8 * 64 * 8) == hipSuccess;
     ok &= hipMalloc((void**)&c.wg_clk, (size_t)c.G * 16) == hipSuccess && hipMemset(c.wg_clk, 0, (size_t)c.G * 16) == hipSuccess;
-    ok &= dalloc(&c.st, 1) == hipSuccess;
+    ok &= dalloc(&c.st, 1) == hipSuccess && hipMemset(c.st, 0, sizeof(DevState)) == hipSuccess;  // (IMU deskew off: k_state_init keeps its wiring)
     ok &= dalloc(&c.traj, (size_t)h->traj_cap * 16) == hipSuccess;
     ok &= dalloc(&c.sstats, (size_t)h->traj_cap) == hipSuccess;
     ok &= hipMalloc(&h->d_in, (size_t)n * 3 * 8) == hipSuccess;
@@ -409,7 +426,10 @@ static int icp_enqueue_scan(ptl_icp* h, const float* in_f32, const double* in_f6
     // K0-K4 on the main stream, right behind the previous GN kernel (no hand-over: a stream that has to wait for another
     // pays ~20 us of wake-up latency); beside them run the previous scan's map update (map stream) and, in the sequence
     // runner, the EKF step (its own stream) - both are done before this chain is, so the waits below do not block
-    k_scan_prologue<<<1, 1024, 0, s>>>(c);
+    if (h->pro_wait) HIPCHK(hipStreamWaitEvent(s, h->pro_wait, 0));  // IMU deskew: the table needs the sweep's knots
+    if (h->dk_wired) k_scan_prologue_imu<<<1, 1024, 0, s>>>(c);
+    else k_scan_prologue<<<1, 1024, 0, s>>>(c);
+    h->dk_rec.push_back(h->dk_wired ? (signed char)-1 : (signed char)((c.deskew && h->scans_done >= 2) ? DK_MODE_CV : DK_MODE_NONE));
     k_deskew_vds1<<<nb1, 256, 0, s>>>(c);
     k_count_w1<<<nb, 256, 0, s>>>(c);
     k_compact_fd<<<nb, 256, 0, s>>>(c);
@@ -1050,6 +1070,9 @@ struct ptl_ekf {
     EkfSmoothJob job;
     EkfSmoothJob* d_job;
     long long* d_info;
+    // IMU deskew knot list (ptl_ekf_knots_enable)
+    double* d_knots;
+    int64_t knot_cap;
 };
 
 extern "C" int ptl_ekf_default_cfg(ptl_ekf_cfg* cfg) {
@@ -1077,6 +1100,7 @@ static int ekf_create_impl(const ptl_ekf_cfg* cfg, hipStream_t shared, ptl_ekf**
     h->own_stream = shared == nullptr;
     h->stream = shared;
     h->st = nullptr; h->d_buf = nullptr; h->buf_rows = 1024;
+    h->d_knots = nullptr; h->knot_cap = 0;
     if (h->own_stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return set_err(PTL_ERR_HIP, "stream"); }
     if (dalloc(&h->st, 1) != hipSuccess || dalloc(&h->d_buf, (size_t)h->buf_rows * 7 + 64) != hipSuccess) {
         if (h->st) (void)hipFree(h->st);
@@ -1096,7 +1120,7 @@ extern "C" int ptl_ekf_destroy(ptl_ekf* h) {
     if (!h) return PTL_OK;
     (void)hipSetDevice(h->cfg.device_id);
     (void)hipFree(h->st); (void)hipFree(h->d_buf);
-    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info})
+    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info, (void*)h->d_knots})
         if (p) (void)hipFree(p);
     if (h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1261,6 +1285,110 @@ extern "C" int ptl_ekf_smooth(ptl_ekf* h, double* poses16, double* ts, double* n
     return ekf_smooth_impl(h, "ptl_ekf_smooth", poses16, ts, nav19, cov324, max_rows, n_rows);
 }
 
+// ---- IMU deskew: the filter's knot list (ekf_kernels.h d_ekf_step) and the registration's wiring to it (d_imu_coltab)
+static_assert(EKF_KNOT_STRIDE == PTL_KNOT_STRIDE, "knot layout of include/ptudes_mi.h");
+__global__ void k_ekf_knots_set(EkfState* e, double* kn, long long cap) {
+    if (threadIdx.x || blockIdx.x) return;
+    e->knots = kn; e->knot_cap = cap; e->knot_count = 0; e->knot_overflow = 0;
+}
+// capacity >= 2: a fresh, empty knot list (the old one is dropped); 0: off.  The caller's other streams must be idle.
+static int ekf_knots_set(ptl_ekf* h, int64_t cap) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    k_ekf_knots_set<<<1, 64, 0, h->stream>>>(h->st, nullptr, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_knots) (void)hipFree(h->d_knots);
+    h->d_knots = nullptr; h->knot_cap = 0;
+    if (cap <= 0) return PTL_OK;
+    if (dalloc(&h->d_knots, (size_t)cap * EKF_KNOT_STRIDE) != hipSuccess) return set_err(PTL_ERR_HIP, "knot list allocation failed (%lld knots)", (long long)cap);
+    h->knot_cap = cap;
+    k_ekf_knots_set<<<1, 64, 0, h->stream>>>(h->st, h->d_knots, (long long)cap);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PTL_OK;
+}
+static int ekf_knots_read(ptl_ekf* h, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
+    if (!h->d_knots) return set_err(PTL_ERR_STATE, "the knot list is not enabled");
+    long long cnt = 0;
+    int ovf = 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(&cnt, (char*)h->st + offsetof(EkfState, knot_count), sizeof cnt, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ovf, (char*)h->st + offsetof(EkfState, knot_overflow), sizeof ovf, hipMemcpyDeviceToHost));
+    const int64_t n = cnt < max_knots ? cnt : max_knots;
+    if (knots && n > 0) HIPCHK(hipMemcpy(knots, h->d_knots, (size_t)n * EKF_KNOT_STRIDE * 8, hipMemcpyDeviceToHost));
+    if (n_knots) *n_knots = cnt;
+    if (overflow) *overflow = ovf;
+    return PTL_OK;
+}
+static int ekf_knot_overflow(ptl_ekf* h, int* ovf) {
+    HIPCHK(hipMemcpyAsync(ovf, (char*)h->st + offsetof(EkfState, knot_overflow), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PTL_OK;
+}
+extern "C" int ptl_ekf_knots_enable(ptl_ekf* h, int64_t capacity) {
+    if (!h || capacity < 0 || capacity == 1) return set_err(PTL_ERR_ARG, "bad argument (capacity: 0 = off, else >= 2 knots)");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    return ekf_knots_set(h, capacity);
+}
+extern "C" int ptl_ekf_knots(ptl_ekf* h, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
+    if (!h || max_knots < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    return ekf_knots_read(h, knots, max_knots, n_knots, overflow);
+}
+struct DkWire { const double* knots; const long long* nknots; const int* kovf; const double* t0t1; int* modes; int n; };
+__global__ void k_dk_set(DevState* st, DkWire w) {
+    if (threadIdx.x || blockIdx.x) return;
+    st->dk_knots = w.knots; st->dk_nknots = w.nknots; st->dk_kovf = w.kovf; st->dk_t0t1 = w.t0t1; st->dk_modes = w.modes; st->dk_n = w.n;
+}
+__global__ void k_dk_times(double* t0t1, double t0, double t1) {
+    if (threadIdx.x || blockIdx.x) return;
+    t0t1[0] = t0; t0t1[1] = t1;
+}
+// the registration `h` deskews from filter `e`'s knots with the sweep times / mode record t0t1 / modes (n scans); e == nullptr: off
+static int dk_wire(ptl_icp* h, ptl_ekf* e, const double* t0t1, int* modes, int64_t n) {
+    DkWire w;
+    memset(&w, 0, sizeof w);
+    if (e) {
+        w.knots = e->d_knots;
+        w.nknots = (const long long*)((char*)e->st + offsetof(EkfState, knot_count));
+        w.kovf = (const int*)((char*)e->st + offsetof(EkfState, knot_overflow));
+        w.t0t1 = t0t1; w.modes = modes; w.n = (int)n;
+    }
+    k_dk_set<<<1, 64, 0, h->stream>>>(h->c.st, w);
+    HIPCHK(hipGetLastError());
+    h->dk_wired = e != nullptr;
+    return PTL_OK;
+}
+// knots a filter needs when it consumes imu_end[0] samples before scan 0 and imu_end[k] - imu_end[k - 1] after the update of scan k - 1
+static int64_t dk_knots_needed(const std::vector<int64_t>& imu_end) {
+    int64_t need = imu_end.empty() ? 0 : imu_end[0];
+    for (size_t k = 1; k < imu_end.size(); ++k) need = std::max(need, 1 + imu_end[k] - imu_end[k - 1]);
+    return need;
+}
+extern "C" int ptl_icp_deskew_modes(ptl_icp* h, int32_t* modes, int64_t max_n, int64_t* n) {
+    if (!h || !modes || max_n < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    int64_t m = h->scans_done < max_n ? h->scans_done : max_n;
+    if (m > (int64_t)h->dk_rec.size()) m = (int64_t)h->dk_rec.size();
+    int64_t dev = 0;  // scans up to the last IMU-wired one: their modes come from the device record (which holds dk_cap >= those)
+    for (int64_t k = 0; k < m; ++k) if (h->dk_rec[(size_t)k] < 0) dev = k + 1;
+    if (dev > h->dk_cap) return set_err(PTL_ERR_STATE, "ptl_icp_deskew_modes: no device record for scan %lld", (long long)dev - 1);
+    if (dev > 0) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(modes, h->dk_modes, (size_t)dev * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    for (int64_t k = 0; k < m; ++k) if (h->dk_rec[(size_t)k] >= 0) modes[k] = h->dk_rec[(size_t)k];
+    if (n) *n = m;
+    return PTL_OK;
+}
+extern "C" int ptl_icp_column_table(ptl_icp* h, double* out) {
+    if (!h || !out) return set_err(PTL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, h->c.coltab, (size_t)h->c.W * 12 * 8, hipMemcpyDeviceToHost));
+    return PTL_OK;
+}
+
 // ================================================================================================ one scan of the driver loop, per-call handles
 // The reference's loop body (cli/ekf_bench.py:493-563) for host-fed data in ONE host round trip: the IMU samples that precede the scan
 // (processImu each), the registration with the filter's pose as its guess (--use-imu-prediction) or the caller's / the constant-velocity
@@ -1268,14 +1396,34 @@ extern "C" int ptl_ekf_smooth(ptl_ekf* h, double* poses16, double* ts, double* n
 // that is n + 2 launches and THREE synchronising read-backs per scan; here the filter's launches go to its own stream, the Gauss-Newton
 // kernel waits for the predicts on the device and reads the guess there, the update waits for the Gauss-Newton kernel on the device and
 // reads the pose there, and the host waits once.  Same kernels, same order of operations per handle: same bits.
-extern "C" int ptl_icp_ekf_step(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int64_t n_imu, const void* xyz, int dtype, int64_t n,
-                                const double* t01, const double* guess, int32_t use_imu_prediction, double kiss_pose[16],
-                                double ekf_pose[16], double* ekf_ts, ptl_icp_stats* stats) {
+// imu_deskew: the column table of this scan comes from the filter's knots (sweep times t0, t1); its prologue waits for the predicts.
+static int icp_ekf_step_impl(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int64_t n_imu, const void* xyz, int dtype, int64_t n,
+                             const double* t01, const double* guess, int32_t use_imu_prediction, double kiss_pose[16],
+                             double ekf_pose[16], double* ekf_ts, ptl_icp_stats* stats, bool imu_deskew, double t0, double t1) {
     if (!h || !e || (!imu_rows && n_imu > 0) || (!xyz && n > 0) || n < 0 || n_imu < 0) return set_err(PTL_ERR_ARG, "bad argument");
     if (dtype != PTL_F32 && dtype != PTL_F64) return set_err(PTL_ERR_ARG, "dtype must be PTL_F32 or PTL_F64");
     if (n > h->n_max) return set_err(PTL_ERR_CAPACITY, "scan has %lld points, capacity %lld", (long long)n, (long long)h->n_max);
     if (h->cfg.device_id != e->cfg.device_id) return set_err(PTL_ERR_ARG, "registration on device %d, filter on device %d", h->cfg.device_id, e->cfg.device_id);
     HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (imu_deskew) {
+        if (!h->cfg.deskew) return set_err(PTL_ERR_STATE, "IMU deskew: deskew is off in the registration's configuration");
+        if (!e->d_knots) return set_err(PTL_ERR_STATE, "IMU deskew: the filter keeps no knot list (ptl_ekf_knots_enable)");
+        if (n_imu + 1 > e->knot_cap) return set_err(PTL_ERR_ARG, "IMU deskew: %lld IMU samples need %lld knots, the filter's list holds %lld", (long long)n_imu, (long long)n_imu + 1, (long long)e->knot_cap);
+        if (!(t1 >= t0)) return set_err(PTL_ERR_ARG, "IMU deskew: sweep times must satisfy t0 <= t1");
+        if (h->scans_done >= h->dk_cap) {  // the per-scan sweep times and modes grow with the scans
+            const int64_t cap = h->dk_cap > 0 ? 2 * h->dk_cap : h->traj_cap;
+            double* nt = nullptr;
+            int* nm = nullptr;
+            HIPCHK(dalloc(&nt, (size_t)cap * 2));
+            HIPCHK(dalloc(&nm, (size_t)cap));
+            HIPCHK(hipMemset(nm, 0, (size_t)cap * sizeof(int)));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if (h->dk_modes) HIPCHK(hipMemcpy(nm, h->dk_modes, (size_t)h->dk_cap * sizeof(int), hipMemcpyDeviceToDevice));
+            if (h->dk_t0t1) (void)hipFree(h->dk_t0t1);
+            if (h->dk_modes) (void)hipFree(h->dk_modes);
+            h->dk_t0t1 = nt; h->dk_modes = nm; h->dk_cap = cap;
+        }
+    }
     if (!h->ev_step_guess) {
         HIPCHK(hipEventCreateWithFlags(&h->ev_step_guess, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->ev_step_gn, hipEventDisableTiming));
@@ -1298,18 +1446,28 @@ extern "C" int ptl_icp_ekf_step(ptl_icp* h, ptl_ekf* e, const double* imu_rows, 
     if (n) HIPCHK(hipMemcpyAsync(h->d_in, xyz, (size_t)n * 3 * esz, hipMemcpyHostToDevice, h->stream));
     if (t01 && n) HIPCHK(hipMemcpyAsync(h->d_t01, t01, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     const double* guess_ptr = nullptr;
+    if (use_imu_prediction || imu_deskew) HIPCHK(hipEventRecord(h->ev_step_guess, es));  // the predicts are through
     if (use_imu_prediction) {  // ekf.nav.pose_mat() as the guess, read on the device once the predicts are through
-        HIPCHK(hipEventRecord(h->ev_step_guess, es));
         h->gn_wait = h->ev_step_guess;
         guess_ptr = (const double*)((char*)e->st + offsetof(EkfState, pose));
     } else if (guess) {
         HIPCHK(hipMemcpyAsync(h->d_ext, guess, 16 * 8, hipMemcpyHostToDevice, h->stream));
         guess_ptr = h->d_ext;
     }
+    if (imu_deskew) {  // this scan's sweep times, the wiring to the filter's knots, and the prologue behind the predicts
+        k_dk_times<<<1, 64, 0, h->stream>>>(h->dk_t0t1 + 2 * h->scans_done, t0, t1);
+        int rc = dk_wire(h, e, h->dk_t0t1, h->dk_modes, h->dk_cap);
+        if (rc) return rc;
+        h->pro_wait = h->ev_step_guess;
+    }
     h->gn_done = h->ev_step_gn;
     int rc = icp_enqueue_scan(h, dtype == PTL_F32 ? (const float*)h->d_in : nullptr, dtype == PTL_F64 ? (const double*)h->d_in : nullptr,
                               t01 ? h->d_t01 : nullptr, n, guess_ptr);
-    h->gn_wait = nullptr; h->gn_done = nullptr;
+    h->gn_wait = nullptr; h->gn_done = nullptr; h->pro_wait = nullptr;
+    if (imu_deskew) {  // the handle's other entry points keep the constant-velocity deskew
+        const int rc2 = dk_wire(h, nullptr, nullptr, nullptr, 0);
+        if (!rc) rc = rc2;
+    }
     if (rc) return rc;
     // processPose(kiss pose): behind the Gauss-Newton kernel, on the filter's stream; its outputs (pose after the update, timestamp) land
     // in the tail of the filter's staging buffer
@@ -1321,9 +1479,25 @@ extern "C" int ptl_icp_ekf_step(ptl_icp* h, ptl_ekf* e, const double* imu_rows, 
     rc = icp_percall_finish(h, kiss_pose, stats);  // (synchronises the registration's stream: pose, statistics row, error flags)
     HIPCHK(hipStreamSynchronize(es));
     if (rc) return rc;
+    if (imu_deskew) {
+        int ovf = 0;
+        rc = ekf_knot_overflow(e, &ovf);
+        if (rc) return rc;
+        if (ovf) return set_err(PTL_ERR_CAPACITY, "IMU deskew: the filter's knot list overflowed (capacity %lld)", (long long)e->knot_cap);
+    }
     if (ekf_pose) memcpy(ekf_pose, out, 128);
     if (ekf_ts) *ekf_ts = out[16];
     return PTL_OK;
+}
+extern "C" int ptl_icp_ekf_step(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int64_t n_imu, const void* xyz, int dtype, int64_t n,
+                                const double* t01, const double* guess, int32_t use_imu_prediction, double kiss_pose[16],
+                                double ekf_pose[16], double* ekf_ts, ptl_icp_stats* stats) {
+    return icp_ekf_step_impl(h, e, imu_rows, n_imu, xyz, dtype, n, t01, guess, use_imu_prediction, kiss_pose, ekf_pose, ekf_ts, stats, false, 0.0, 0.0);
+}
+extern "C" int ptl_icp_ekf_step_imu_deskew(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int64_t n_imu, const void* xyz, int dtype, int64_t n,
+                                           double t0, double t1, const double* guess, int32_t use_imu_prediction, double kiss_pose[16],
+                                           double ekf_pose[16], double* ekf_ts, ptl_icp_stats* stats) {
+    return icp_ekf_step_impl(h, e, imu_rows, n_imu, xyz, dtype, n, nullptr, guess, use_imu_prediction, kiss_pose, ekf_pose, ekf_ts, stats, true, t0, t1);
 }
 
 // ================================================================================================ sequence runner
@@ -1348,6 +1522,11 @@ struct ptl_seq {
     int64_t next_scan, imu_pos, imus_per_scan;  // driver-loop position (ekf_bench.py:491-518)
     ptl_lut* lut;                    // non-null => sweeps were uploaded as u32 range images
     std::vector<unsigned char> is_range;
+    // IMU deskew (ptl_seq_imu_deskew_enable): sweep times and modes per scan, the event the prologue waits for
+    bool dk_on, dk_times;
+    double* d_dk_t0t1;   // [n_scans][2]
+    int* d_dk_modes;     // [n_scans]
+    hipEvent_t ev_pro;
 };
 
 extern "C" int ptl_seq_destroy(ptl_seq* s) {
@@ -1362,6 +1541,9 @@ extern "C" int ptl_seq_destroy(ptl_seq* s) {
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->ev_guess) (void)hipEventDestroy(s->ev_guess);
     if (s->ev_gn) (void)hipEventDestroy(s->ev_gn);
+    if (s->ev_pro) (void)hipEventDestroy(s->ev_pro);
+    if (s->d_dk_t0t1) (void)hipFree(s->d_dk_t0t1);
+    if (s->d_dk_modes) (void)hipFree(s->d_dk_modes);
     if (s->ekf_stream) (void)hipStreamDestroy(s->ekf_stream);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1380,6 +1562,7 @@ extern "C" int ptl_seq_create(const ptl_seq_cfg* cfg, ptl_seq** out) {
     s->icp = nullptr; s->ekf = nullptr; s->d_scans = nullptr; s->d_imu = nullptr;
     s->d_res_poses = nullptr; s->d_res_t = nullptr; s->d_rows = nullptr; s->n_out = 0; s->stream = nullptr;
     s->ekf_stream = nullptr; s->ev_guess = nullptr; s->ev_gn = nullptr;
+    s->dk_on = false; s->dk_times = false; s->d_dk_t0t1 = nullptr; s->d_dk_modes = nullptr; s->ev_pro = nullptr;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&s->ekf_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_guess, hipEventDisableTiming) != hipSuccess ||
@@ -1463,6 +1646,14 @@ extern "C" int ptl_seq_enqueue(ptl_seq* s, int64_t n) {
     const size_t pps = (size_t)s->cfg.points_per_scan;
     const int64_t end = s->next_scan + n;
     hipStream_t es = s->ekf_stream;  // used when the EKF does not feed the registration (no IMU prediction)
+    if (s->dk_on) {  // IMU deskew: sweep times, knots enough, and no scan the driver loop would skip (scan k's table is at index k)
+        if (!s->dk_times) return set_err(PTL_ERR_STATE, "IMU deskew: no sweep times (ptl_seq_upload_sweep_times)");
+        const int64_t need = dk_knots_needed(s->imu_end);
+        if (need > s->ekf->knot_cap) return set_err(PTL_ERR_ARG, "IMU deskew: the IMU samples between two scans need %lld knots, capacity %lld", (long long)need, (long long)s->ekf->knot_cap);
+        if (s->next_scan == 0 && end > 0 && s->imu_end[0] == 0) return set_err(PTL_ERR_ARG, "IMU deskew: scan 0 has no IMU sample before it");
+        for (int64_t k = s->next_scan > 0 ? s->next_scan : 1; k < end; ++k)
+            if (s->imu_end[(size_t)k] == s->imu_end[(size_t)k - 1]) return set_err(PTL_ERR_ARG, "IMU deskew: scan %lld has no IMU sample after scan %lld", (long long)k, (long long)k - 1);
+    }
     for (int64_t k = s->next_scan; k < end; ++k) {
         // IMU samples that precede scan k and were not consumed yet (only before the very first scan of a run,
         // or when the previous scan was skipped: otherwise the previous scan's EKF launch already ran them)
@@ -1484,6 +1675,10 @@ extern "C" int ptl_seq_enqueue(ptl_seq* s, int64_t n) {
             s->icp->gn_wait = s->ev_guess;
         }
         if (with_ekf) s->icp->gn_done = s->ev_gn;
+        if (s->dk_on) {  // the prologue (the column table) waits for the predicts through the sweep's samples: no overlap with them
+            HIPCHK(hipEventRecord(s->ev_pro, es));
+            s->icp->pro_wait = s->ev_pro;
+        }
         int rc;
         if (s->is_range[(size_t)k]) {
             if (!s->lut) rc = set_err(PTL_ERR_STATE, "scan %lld is a range image but no LUT was set", (long long)k);
@@ -1492,7 +1687,7 @@ extern "C" int ptl_seq_enqueue(ptl_seq* s, int64_t n) {
         } else {
             rc = icp_enqueue_scan(s->icp, s->d_scans + (size_t)k * pps * 3, nullptr, nullptr, (int64_t)pps, guess_ptr);
         }
-        s->icp->gn_wait = nullptr; s->icp->gn_done = nullptr;
+        s->icp->gn_wait = nullptr; s->icp->gn_done = nullptr; s->icp->pro_wait = nullptr;
         if (rc) return rc;
         const double* kiss_pose = s->icp->c.traj + 16 * (s->icp->scans_done - 1);
         if (with_ekf) {
@@ -1515,6 +1710,11 @@ extern "C" int ptl_seq_wait(ptl_seq* s) {
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     int rc = icp_check_flags(s->icp);
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
+    if (rc == PTL_OK && s->dk_on) {
+        int ovf = 0;
+        rc = ekf_knot_overflow(s->ekf, &ovf);
+        if (rc == PTL_OK && ovf) rc = set_err(PTL_ERR_CAPACITY, "IMU deskew: the filter's knot list overflowed (capacity %lld)", (long long)s->ekf->knot_cap);
+    }
     return rc;
 }
 extern "C" int ptl_seq_run(ptl_seq* s, int64_t n) {
@@ -1551,6 +1751,65 @@ extern "C" int ptl_seq_smoother_log(ptl_seq* s, double* entries, int64_t max_ent
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
     return ekf_log_read(s->ekf, entries, max_entries, n_entries, overflow);
+}
+// IMU deskew for the sequence's scans
+extern "C" int ptl_seq_imu_deskew_enable(ptl_seq* s, int32_t on, int64_t knot_capacity) {
+    if (!s) return set_err(PTL_ERR_ARG, "null argument");
+    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_imu_deskew_enable: an ICP-only sequence (with_ekf = 0) has no filter to deskew with");
+    if (on && !s->cfg.icp.deskew) return set_err(PTL_ERR_STATE, "ptl_seq_imu_deskew_enable: deskew is off in the configuration");
+    if (on && knot_capacity < 2) return set_err(PTL_ERR_ARG, "ptl_seq_imu_deskew_enable: knot_capacity must be >= 2");
+    if (on && dk_knots_needed(s->imu_end) > knot_capacity)
+        return set_err(PTL_ERR_ARG, "ptl_seq_imu_deskew_enable: the IMU samples between two scans need %lld knots, knot_capacity is %lld", (long long)dk_knots_needed(s->imu_end), (long long)knot_capacity);
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(s->icp->map_stream));
+    HIPCHK(hipStreamSynchronize(s->ekf_stream));
+    int rc = dk_wire(s->icp, nullptr, nullptr, nullptr, 0);
+    if (rc == PTL_OK) rc = ekf_knots_set(s->ekf, 0);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->dk_on = false; s->dk_times = false;
+    if (rc || !on) return rc;
+    const size_t n = (size_t)s->cfg.n_scans;
+    if (!s->d_dk_t0t1 && (dalloc(&s->d_dk_t0t1, 2 * n) != hipSuccess || dalloc(&s->d_dk_modes, n) != hipSuccess))
+        return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
+    if (!s->ev_pro) HIPCHK(hipEventCreateWithFlags(&s->ev_pro, hipEventDisableTiming));
+    HIPCHK(hipMemset(s->d_dk_modes, 0, n * sizeof(int)));
+    rc = ekf_knots_set(s->ekf, knot_capacity);
+    if (rc == PTL_OK) rc = dk_wire(s->icp, s->ekf, s->d_dk_t0t1, s->d_dk_modes, (int64_t)n);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (rc == PTL_OK) s->dk_on = true;
+    return rc;
+}
+extern "C" int ptl_seq_upload_sweep_times(ptl_seq* s, const double* t0t1) {
+    if (!s || !t0t1) return set_err(PTL_ERR_ARG, "null argument");
+    if (!s->dk_on) return set_err(PTL_ERR_STATE, "ptl_seq_upload_sweep_times: IMU deskew is not enabled");
+    for (int64_t k = 0; k < s->cfg.n_scans; ++k)
+        if (!(t0t1[2 * k + 1] >= t0t1[2 * k])) return set_err(PTL_ERR_ARG, "ptl_seq_upload_sweep_times: scan %lld has t1 < t0", (long long)k);
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(s->d_dk_t0t1, t0t1, (size_t)s->cfg.n_scans * 16, hipMemcpyHostToDevice));
+    s->dk_times = true;
+    return PTL_OK;
+}
+extern "C" int ptl_seq_deskew_modes(ptl_seq* s, int32_t* modes, int64_t max_n, int64_t* n) {
+    if (!s || !modes || max_n < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    const int64_t m = s->n_out < max_n ? s->n_out : max_n;
+    if (!s->dk_on) {
+        for (int64_t k = 0; k < m; ++k) modes[k] = (s->cfg.icp.deskew && k >= 2) ? DK_MODE_CV : DK_MODE_NONE;
+    } else {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (m > 0) HIPCHK(hipMemcpy(modes, s->d_dk_modes, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (n) *n = m;
+    return PTL_OK;
+}
+extern "C" int ptl_seq_knots(ptl_seq* s, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
+    if (!s || max_knots < 0) return set_err(PTL_ERR_ARG, "bad argument");
+    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only sequence has no filter");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return ekf_knots_read(s->ekf, knots, max_knots, n_knots, overflow);
 }
 extern "C" int ptl_seq_copy_traj(ptl_seq* s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!s || !dst_device) return set_err(PTL_ERR_ARG, "null argument");
@@ -1661,6 +1920,14 @@ struct ptl_batch {
     long long* d_sm_info;
     std::vector<long long> h_sm_info;
     bool sm_done;  // the last ptl_batch_smooth succeeded and nothing ran since
+    // IMU deskew (ptl_batch_imu_deskew_enable): sweep times and modes per sequence (all n_scans, also with the sweep ring); the lockstep
+    // driver's prologue waits for `ev_filter`, recorded behind the filter step
+    bool dk_on;
+    bool dk_times[GN_MAX_SEQ];
+    double* d_dk_t0t1[GN_MAX_SEQ];
+    int* d_dk_modes[GN_MAX_SEQ];
+    hipEvent_t ev_filter;
+    bool ev_filter_valid;
 };
 
 // launch geometry: workgroups per team.  Lockstep (kx_assign): one team per sequence, 1 / 2 / 4 per XCD.  Free-running: 1 / 2 / 4
@@ -1713,7 +1980,7 @@ extern "C" int ptl_batch_destroy(ptl_batch* b) {
     for (int s = 0; s < b->S; ++s) {
         if (b->icp[s]) icp_free(b->icp[s]);
         if (b->ekf[s]) ptl_ekf_destroy(b->ekf[s]);
-        void* ptrs[] = {b->d_scans[s], b->d_imu[s], b->d_res_poses[s], b->d_res_t[s], b->d_rows[s], b->d_imu_end[s]};
+        void* ptrs[] = {b->d_scans[s], b->d_imu[s], b->d_res_poses[s], b->d_res_t[s], b->d_rows[s], b->d_imu_end[s], b->d_dk_t0t1[s], b->d_dk_modes[s]};
         for (void* p : ptrs)
             if (p) (void)hipFree(p);
     }
@@ -1728,6 +1995,7 @@ extern "C" int ptl_batch_destroy(ptl_batch* b) {
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
     if (b->ev_gn) (void)hipEventDestroy(b->ev_gn);
     if (b->ev_side) (void)hipEventDestroy(b->ev_side);
+    if (b->ev_filter) (void)hipEventDestroy(b->ev_filter);
     if (b->side) (void)hipStreamDestroy(b->side);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -1782,7 +2050,9 @@ extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl
     for (int s = 0; s < GN_MAX_SEQ; ++s) {
         b->icp[s] = nullptr; b->ekf[s] = nullptr; b->d_scans[s] = nullptr; b->d_imu[s] = nullptr; b->d_imu_end[s] = nullptr;
         b->d_res_poses[s] = nullptr; b->d_res_t[s] = nullptr; b->d_rows[s] = nullptr; b->imu_pos[s] = 0;
+        b->dk_times[s] = false; b->d_dk_t0t1[s] = nullptr; b->d_dk_modes[s] = nullptr;
     }
+    b->dk_on = false; b->ev_filter = nullptr; b->ev_filter_valid = false;
     int rc = PTL_OK;
     b->side = nullptr; b->ev_gn = nullptr; b->ev_side = nullptr; b->ev_side_valid = false;
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { delete b; return set_err(PTL_ERR_HIP, "stream"); }
@@ -1921,6 +2191,17 @@ static int batch_reset(ptl_batch* b) {
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
     b->ev_side_valid = false;
+    b->ev_filter_valid = false;
+    return PTL_OK;
+}
+// IMU deskew: sweep times of every sequence, knots enough for the IMU samples between two scans
+static int batch_dk_check(ptl_batch* b) {
+    if (!b->dk_on) return PTL_OK;
+    for (int s = 0; s < b->S; ++s) {
+        if (!b->dk_times[s]) return set_err(PTL_ERR_STATE, "IMU deskew: sequence %d has no sweep times (ptl_batch_upload_sweep_times)", s);
+        const int64_t need = dk_knots_needed(b->imu_end[s]);
+        if (need > b->ekf[s]->knot_cap) return set_err(PTL_ERR_ARG, "IMU deskew: sequence %d: the IMU samples between two scans need %lld knots, capacity %lld", s, (long long)need, (long long)b->ekf[s]->knot_cap);
+    }
     return PTL_OK;
 }
 __global__ void k_ring_rebase(SeqCtx* a, int S, long long delta_floats) {
@@ -2049,6 +2330,7 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     b->sm_done = false;
     if (b->ctx_dirty) { int rc = batch_push_ctx(b); if (rc) return rc; }
+    { int rc = batch_dk_check(b); if (rc) return rc; }
     if (b->free_running) return batch_enqueue_free(b, n);
     if (b->S > 32) return set_err(PTL_ERR_ARG, "the lockstep driver serves up to 32 sequences (four per XCD); %d need the free-running one", b->S);
     if (b->cfg.icp.map_small_blocks > 0) return set_err(PTL_ERR_ARG, "map_small_blocks (two block classes) needs the free-running driver");
@@ -2076,7 +2358,9 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
             }
         }
         const int ki = (int)k;
-        kb_scan_prologue<<<dim3(1, S), 1024, 0, st>>>(b->d_ctx, ki);
+        if (b->dk_on && b->ev_filter_valid) HIPCHK(hipStreamWaitEvent(st, b->ev_filter, 0));  // IMU deskew: the table needs the sweep's knots
+        if (b->dk_on) kb_scan_prologue_imu<<<dim3(1, S), 1024, 0, st>>>(b->d_ctx, ki);
+        else kb_scan_prologue<<<dim3(1, S), 1024, 0, st>>>(b->d_ctx, ki);
         kb_deskew_vds1<<<dim3(nb, S), 256, 0, st>>>(b->d_ctx, ki);
         kb_count_w1<<<dim3(nb, S), 256, 0, st>>>(b->d_ctx, ki);
         kb_compact_fd<<<dim3(nb, S), 256, 0, st>>>(b->d_ctx, ki);
@@ -2119,6 +2403,7 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
             }
             ea.update_first = 1;
             kb_ekf_step<<<S, 384, 0, sd>>>(ea);
+            if (b->dk_on) { HIPCHK(hipEventRecord(b->ev_filter, sd)); b->ev_filter_valid = true; }
         }
         kb_map_insert_a<<<dim3(nb, S), 256, 0, sd>>>(b->d_ctx, ki);
         kb_map_insert_b<<<dim3(nb, S), 256, 0, sd>>>(b->d_ctx, ki);
@@ -2175,6 +2460,12 @@ extern "C" int ptl_batch_wait(ptl_batch* b) {
     // (a team that only ran out of its idle budget while the last sequences were in other teams' hands - bit 4 alone, every sequence at its last
     // scan - did no harm: the bit stays readable through ptl_batch_status, the wait does not fail on it)
     if (status & ~SEQ_EXIT_IDLE) return set_err(PTL_ERR_STATE, "free-running launch: teams left early, status 0x%x (1 head-of-launch barrier, 2 job barrier, 4 idle, 8 gave up on a sequence, 16 scans incomplete)", status);
+    for (int s = 0; b->dk_on && s < b->S; ++s) {  // IMU deskew: a truncated knot list is an error, not a quiet fallback
+        int ovf = 0;
+        const int rc = ekf_knot_overflow(b->ekf[s], &ovf);
+        if (rc) return rc;
+        if (ovf) return set_err(PTL_ERR_CAPACITY, "IMU deskew: sequence %d: the filter's knot list overflowed (capacity %lld)", s, (long long)b->ekf[s]->knot_cap);
+    }
     return PTL_OK;
 }
 extern "C" int ptl_batch_status(ptl_batch* b, uint32_t* status) {
@@ -2319,6 +2610,76 @@ extern "C" int ptl_batch_smoother_log(ptl_batch* b, int32_t seq, double* entries
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
     return ekf_log_read(b->ekf[seq], entries, max_entries, n_entries, overflow);
+}
+// IMU deskew for every sequence of the batch, either driver, resident or sweep ring
+extern "C" int ptl_batch_imu_deskew_enable(ptl_batch* b, int32_t on, int64_t knot_capacity) {
+    if (!b) return set_err(PTL_ERR_ARG, "null argument");
+    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_batch_imu_deskew_enable: an ICP-only batch (with_ekf = 0) has no filter to deskew with");
+    if (on && !b->cfg.icp.deskew) return set_err(PTL_ERR_STATE, "ptl_batch_imu_deskew_enable: deskew is off in the configuration");
+    if (on && knot_capacity < 2) return set_err(PTL_ERR_ARG, "ptl_batch_imu_deskew_enable: knot_capacity must be >= 2");
+    for (int s = 0; on && s < b->S; ++s)
+        if (dk_knots_needed(b->imu_end[s]) > knot_capacity)
+            return set_err(PTL_ERR_ARG, "ptl_batch_imu_deskew_enable: sequence %d: the IMU samples between two scans need %lld knots, knot_capacity is %lld", s,
+                           (long long)dk_knots_needed(b->imu_end[s]), (long long)knot_capacity);
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->side));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->dk_on = false;
+    b->ev_filter_valid = false;
+    for (int s = 0; s < b->S; ++s) {
+        b->dk_times[s] = false;
+        int rc = dk_wire(b->icp[s], nullptr, nullptr, nullptr, 0);
+        if (rc == PTL_OK) rc = ekf_knots_set(b->ekf[s], 0);
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (!on) return PTL_OK;
+    if (!b->ev_filter) HIPCHK(hipEventCreateWithFlags(&b->ev_filter, hipEventDisableTiming));
+    const size_t n = (size_t)b->cfg.n_scans;
+    for (int s = 0; s < b->S; ++s) {
+        if (!b->d_dk_t0t1[s] && (dalloc(&b->d_dk_t0t1[s], 2 * n) != hipSuccess || dalloc(&b->d_dk_modes[s], n) != hipSuccess))
+            return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
+        HIPCHK(hipMemset(b->d_dk_modes[s], 0, n * sizeof(int)));
+        int rc = ekf_knots_set(b->ekf[s], knot_capacity);
+        if (rc == PTL_OK) rc = dk_wire(b->icp[s], b->ekf[s], b->d_dk_t0t1[s], b->d_dk_modes[s], (int64_t)n);
+        if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->dk_on = true;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_upload_sweep_times(ptl_batch* b, int32_t seq, const double* t0t1) {
+    if (!b || !t0t1 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
+    if (!b->dk_on) return set_err(PTL_ERR_STATE, "ptl_batch_upload_sweep_times: IMU deskew is not enabled");
+    for (int64_t k = 0; k < b->cfg.n_scans; ++k)
+        if (!(t0t1[2 * k + 1] >= t0t1[2 * k])) return set_err(PTL_ERR_ARG, "ptl_batch_upload_sweep_times: scan %lld has t1 < t0", (long long)k);
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->side));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    HIPCHK(hipMemcpy(b->d_dk_t0t1[seq], t0t1, (size_t)b->cfg.n_scans * 16, hipMemcpyHostToDevice));
+    b->dk_times[seq] = true;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_deskew_modes(ptl_batch* b, int32_t seq, int32_t* modes, int64_t max_n, int64_t* n) {
+    if (!b || !modes || max_n < 0 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    const int64_t m = b->n_out < max_n ? b->n_out : max_n;
+    if (!b->dk_on) {
+        for (int64_t k = 0; k < m; ++k) modes[k] = (b->cfg.icp.deskew && k >= 2) ? DK_MODE_CV : DK_MODE_NONE;
+    } else {
+        HIPCHK(hipStreamSynchronize(b->side));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (m > 0) HIPCHK(hipMemcpy(modes, b->d_dk_modes[seq], (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (n) *n = m;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_knots(ptl_batch* b, int32_t seq, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
+    if (!b || max_knots < 0 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
+    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only batch has no filter");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->side));
+    return ekf_knots_read(b->ekf[seq], knots, max_knots, n_knots, overflow);
 }
 extern "C" int ptl_batch_copy_traj(ptl_batch* b, int32_t s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!b || !dst_device || s < 0 || s >= b->S) return set_err(PTL_ERR_ARG, "bad argument");

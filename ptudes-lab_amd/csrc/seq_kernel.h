@@ -105,6 +105,9 @@ __device__ __forceinline__ unsigned xcc_id() {
 #define SQ_CLK_DECL do { } while (0)
 #define SQ_CLK(i) do { } while (0)
 #endif
+// K0 of a scan whose prologue the filter workgroup has not run (the first scan after a cold start, or no filter): a call of its own, so
+// that the prologue's body (and the IMU deskew's call inside it) stays out of sq_prepare's registers
+__device__ __noinline__ void sq_prologue(const SeqCtx* a, int s, int k) { d_scan_prologue(load_seq_ctx(a, s, k), true); }
 // K0-K4 of scan k by the team's `nw` working workgroups (this one is number `wg`); returns the barrier target, SEQ_FAIL on abort
 __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int wg, int nw, unsigned target, unsigned* word, bool local) {
     const Ctx c = load_seq_ctx(a, s, k);
@@ -115,7 +118,7 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
     sl.nb = nbs; sl.clk = wg == 0 ? 1 : 0;
     const TeamEnv te = {word, &st->gn_abort, st, local};
     SQ_CLK_DECL;
-    if (wg == 0 && st->pro_next != k + 1) d_scan_prologue(c, true);  // (with a filter it has usually been run already: sq_filter)
+    if (wg == 0 && st->pro_next != k + 1) sq_prologue(a, s, k);  // (with a filter it has usually been run already: sq_filter)
     SQ_CLK(0);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
     SQ_CLK(1);

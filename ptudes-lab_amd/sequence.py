@@ -17,7 +17,8 @@ from .kiss import KissICPWrapper
 
 
 def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use_imu_prediction=False,
-               guess_fn=None, logging=False, device_id=0, stats=None, lazy_map_stats=True, fused=None, smooth=False):
+               guess_fn=None, logging=False, device_id=0, stats=None, lazy_map_stats=True, fused=None, smooth=False,
+               imu_deskew=False, sweep_time_fn=None, knot_capacity=4096):
     """Returns dict(res_t, res_poses, kiss_poses, kiss_icp, ekf, timings).  `guess_fn(ts)` (optional) supplies an
     external guess (the reference's --use-gt-guess, ekf_bench.py:536-542); `stats` (optional) is the StreamStatsTracker
     the loop feeds (ekf_bench.py:497-499, :522-524), its time goes into timings["track"].
@@ -31,7 +32,16 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
     `corr` only count the host's hold-back (about 0): the reference's three per-stage means (ekf_bench.py:590-595) exist
     separately only with fused=False; timings["fused"] says which form ran.
     smooth: the filter logs its history (the event stream is read into a list first, to size the log by its scans) and the result
-    gains smoothed_poses / smoothed_t - the fixed-interval RTS smoother at every update (ESEKF.smooth), aligned with res_poses / res_t."""
+    gains smoothed_poses / smoothed_t - the fixed-interval RTS smoother at every update (ESEKF.smooth), aligned with res_poses / res_t.
+    imu_deskew: the scans' column tables come from the filter's IMU-propagated trajectory instead of the constant-velocity
+    model; sweep_time_fn(ts) gives a scan's absolute (t0, t1) on the IMU clock from its timestamp.  Fused form only (the call-by-call
+    form stays constant-velocity): raises with fused=False or logging; point scans only (no per-point t01)."""
+    if imu_deskew:
+        if fused is False or logging:
+            raise ValueError("imu_deskew needs the fused form (fused=True, no per-sample logging): the call-by-call form stays constant-velocity")
+        if sweep_time_fn is None:
+            raise ValueError("imu_deskew needs sweep_time_fn(ts) -> (t0, t1)")
+        fused = True
     if smooth:
         events = list(events)
     if fused is None:
@@ -40,6 +50,8 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
     kiss_icp = KissICPWrapper(metadata, _use_extrinsics=True, _min_range=kiss_min_range, _max_range=kiss_max_range,
                               device_id=device_id, lazy_map_stats=lazy_map_stats)
     ekf = ESEKF(_logging=logging, device_id=device_id)
+    if imu_deskew:
+        ekf._ekf.enable_knots(int(knot_capacity))
     if smooth:
         ekf.enable_smoother(max(1, sum(1 for ev in events if ev[0] != "imu")))
     res_t, res_poses, kiss_poses = [], [], []
@@ -90,7 +102,13 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
                 guess = None  # constant velocity, formed on the device (kiss.py:102-105)
             t1 = time.monotonic()
             rows = np.array([[i.ts, *i.lacc, *i.avel] for i in held], dtype=np.float64).reshape(-1, 7)
-            kiss_pose, ekf_pose, ekf_ts = core.icp_ekf_step(kiss_icp._icp, ekf._ekf, rows, xyz, t01, guess, use_imu_prediction)
+            if imu_deskew:
+                if t01 is not None:
+                    raise ValueError("imu_deskew takes sweep times, not per-point t01")
+                kiss_pose, ekf_pose, ekf_ts = core.icp_ekf_step(kiss_icp._icp, ekf._ekf, rows, xyz, None, guess, use_imu_prediction,
+                                                                sweep=tuple(sweep_time_fn(ts)))
+            else:
+                kiss_pose, ekf_pose, ekf_ts = core.icp_ekf_step(kiss_icp._icp, ekf._ekf, rows, xyz, t01, guess, use_imu_prediction)
             kiss_icp._log_pose(kiss_pose, ts)
             ekf._after_fused_step(len(held), ekf_ts)
             held = []
@@ -100,6 +118,8 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
             res_poses.append(ekf_pose)
             res_t.append(ekf.ts)
             continue
+        if imu_deskew:
+            raise ValueError("imu_deskew: a scan type the fused step does not take")
         if held:  # (a scan type the fused entry does not take: flush the samples the call-by-call way)
             for i in held:
                 ekf.processImu(i)
@@ -146,9 +166,17 @@ def synthetic_events(seq, n_scans=None):
         yield ("scan", seq.scan(k), None, float(seq.t_base + (k + 1) * seq.scan_dt))
 
 
-def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, device_id=0, smooth=False, **icp_over):
+def sweep_times(seq, n_scans=None):
+    """(n, 2) absolute (t0, t1) of a synth.Sequence's sweeps on its IMU clock"""
+    n = seq.n_scans if n_scans is None else n_scans
+    k = np.arange(n)
+    return np.stack([seq.t_base + k * seq.scan_dt, seq.t_base + (k + 1) * seq.scan_dt], axis=1)
+
+
+def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, device_id=0, smooth=False, imu_deskew=False, **icp_over):
     """Upload a synth.Sequence and run the loop on device.  Returns the SeqRunner results dict + 'seconds'; smooth=True adds
-    smoothed_poses / smoothed_t (SeqRunner.smooth, rows aligned with res_poses / res_t)."""
+    smoothed_poses / smoothed_t (SeqRunner.smooth, rows aligned with res_poses / res_t); imu_deskew=True deskews with the filter's
+    IMU-propagated trajectory (sweep times from the sequence) and adds deskew_modes."""
     n = seq.n_scans if n_scans is None else n_scans
     n_imu = seq.imu_range_for_scan(n - 1)[1] if with_ekf else 0
     r = core.SeqRunner(n, seq.H * seq.W, n_imu, max_range=seq.max_range, min_range=seq.min_range,
@@ -160,11 +188,16 @@ def run_resident(seq, n_scans=None, *, use_imu_prediction=False, with_ekf=True, 
     r.upload_imu(seq.imu[:n_imu] if with_ekf else np.zeros((0, 7)), ends)
     if smooth:
         r.enable_smoother(True)
+    if imu_deskew:
+        r.imu_deskew(True)
+        r.upload_sweep_times(sweep_times(seq, n))
     t0 = time.perf_counter()
     r.run()
     out = r.results()
     out["seconds"] = time.perf_counter() - t0
     out["runner"] = r
+    if imu_deskew:
+        out["deskew_modes"] = r.deskew_modes()
     if smooth:
         sm = r.smooth(nav=False, cov=False)
         out.update(smoothed_poses=sm["poses"], smoothed_t=sm["t"])
