@@ -366,6 +366,56 @@ def _smoother_log(cap, call):
     return out
 
 
+# ---- what SeqRunner and BatchRunner share (they differ only by the batch's sequence index, which `call` carries)
+def _seq_cfg(n_scans, points_per_scan, n_imu, max_range, min_range, use_imu_prediction, with_ekf, device_id, ekf, icp_over, **fields):
+    """the runner's ptl_seq_cfg; fields: further ones by name (range_input, resident_scans)"""
+    cfg = L.SeqCfg()
+    for k, v in fields.items():
+        setattr(cfg, k, v)
+    cfg.icp = icp_cfg(max_range, min_range, device_id=device_id, **icp_over)
+    cfg.ekf = ekf if ekf is not None else ekf_cfg(device_id=device_id)
+    cfg.n_scans, cfg.points_per_scan, cfg.n_imu = n_scans, points_per_scan, n_imu
+    cfg.use_imu_prediction = int(bool(use_imu_prediction))
+    cfg.with_ekf = int(bool(with_ekf))
+    return cfg
+
+
+def _scan_f32(cfg, xyz_f32):
+    x = np.ascontiguousarray(xyz_f32, dtype=np.float32)
+    if x.size != cfg.points_per_scan * 3:
+        raise ValueError("scan size mismatch")
+    return x.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _range_u32(cfg, range_mm):
+    r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+    if r.size != cfg.points_per_scan:
+        raise ValueError("range image size mismatch")
+    return r.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _imu_args(n_scans, imu_rows, imu_end):
+    """(rows or None, imu_end) pointers of an IMU upload"""
+    r = L.as_f64(imu_rows).reshape(-1, 7) if len(imu_rows) else np.zeros((0, 7))
+    e = np.ascontiguousarray(imu_end, dtype=np.int64)
+    if len(e) != n_scans:
+        raise ValueError("imu_end needs one entry per scan")
+    return L.dptr(r) if len(r) else None, e.ctypes.data_as(L.c_i64_p)
+
+
+def _results(n, with_ekf, call):
+    """one results read-out with `n`-row host buffers -> dict(kiss_poses, stats[, res_poses, res_t]) of the rows written"""
+    res_poses, res_t, kiss = np.empty((n, 4, 4)), np.empty(n), np.empty((n, 4, 4))
+    stats = (L.IcpStats * n)()
+    w = C.c_int64()
+    L.check(call(L.dptr(res_poses), L.dptr(res_t), L.dptr(kiss), stats, n, C.byref(w)))
+    m = w.value
+    out = dict(kiss_poses=kiss[:m], stats=[stats[i].as_dict() for i in range(m)])
+    if with_ekf:
+        out.update(res_poses=res_poses[:m], res_t=res_t[:m])
+    return out
+
+
 def icp_ekf_step(icp: "Icp", ekf: "Ekf", imu_rows, xyz, t01=None, guess=None, use_imu_prediction=False, sweep=None):
     """One scan of the reference's loop body (cli/ekf_bench.py:493-563) in one host round trip (include/ptudes_mi.h ptl_icp_ekf_step):
     the IMU rows [ts, lacc, avel] that precede the scan, the registration (guess: the filter's pose when use_imu_prediction, else
@@ -416,23 +466,15 @@ def host_unpin(array):
     L.check(L.lib().ptl_host_unpin(C.c_void_p(array.ctypes.data)))
 
 
-class SeqRunner:
-    """Whole sequence in HBM, no host round trip per scan."""
+class _Runner:
+    """What SeqRunner and BatchRunner share: the entry points without a sequence index (ptl_seq_* / ptl_batch_* by _PREFIX)."""
+    _PREFIX = ""
 
-    def __init__(self, n_scans, points_per_scan, n_imu, *, max_range=70.0, min_range=1.0, use_imu_prediction=False,
-                 with_ekf=True, device_id=0, ekf=None, imu_deskew=False, knot_capacity=None, **icp_over):
-        """imu_deskew: the column tables from the filter's IMU-propagated trajectory (upload_sweep_times before running; knot_capacity
-        defaults to n_imu + 1, enough for any split of the samples; include/ptudes_mi.h ptl_seq_imu_deskew_enable)"""
-        cfg = L.SeqCfg()
-        cfg.icp = icp_cfg(max_range, min_range, device_id=device_id, **icp_over)
-        cfg.ekf = ekf if ekf is not None else ekf_cfg(device_id=device_id)
-        cfg.n_scans, cfg.points_per_scan, cfg.n_imu = n_scans, points_per_scan, n_imu
-        cfg.use_imu_prediction = int(bool(use_imu_prediction))
-        cfg.with_ekf = int(bool(with_ekf))
-        self.cfg = cfg
-        self._h = C.c_void_p()
-        L.check(L.lib().ptl_seq_create(C.byref(cfg), C.byref(self._h)))
-        self.n_scans = n_scans
+    def _c(self, name):
+        return getattr(L.lib(), self._PREFIX + name)
+
+    def _init_imu_deskew(self, imu_deskew, knot_capacity):
+        """the constructor's imu_deskew: a handle it fails for is closed, not leaked"""
         self.knot_capacity = 0
         if imu_deskew:
             try:
@@ -442,9 +484,55 @@ class SeqRunner:
                 raise
 
     def imu_deskew(self, on=True, knot_capacity=None):
+        """the column tables from the filter's IMU-propagated trajectory, for every sequence (upload_sweep_times before running;
+        knot_capacity defaults to n_imu + 1, enough for any split of the samples; include/ptudes_mi.h ptl_*_imu_deskew_enable)"""
         cap = int(self.cfg.n_imu) + 1 if knot_capacity is None else int(knot_capacity)
-        L.check(L.lib().ptl_seq_imu_deskew_enable(self._h, int(bool(on)), cap if on else 0))
+        L.check(self._c("imu_deskew_enable")(self._h, int(bool(on)), cap if on else 0))
         self.knot_capacity = cap if on else 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._c("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_lut(self, lut, active_beams=0):
+        self._lut = lut  # keep alive
+        L.check(self._c("set_lut")(self._h, lut._h, int(active_beams)))
+
+    def run(self, n=None):
+        L.check(self._c("run")(self._h, self.n_scans if n is None else n))
+
+    def enqueue(self, n):
+        L.check(self._c("enqueue")(self._h, n))
+
+    def wait(self):
+        L.check(self._c("wait")(self._h))
+
+    def profile(self, enable=True, reset=False):
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._c("profile")(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+    def enable_smoother(self, on=True):
+        """log the filter history of every sequence (capacity n_scans each) for smooth(); include/ptudes_mi.h ptl_*_smoother_enable"""
+        L.check(self._c("smoother_enable")(self._h, int(bool(on))))
+
+
+class SeqRunner(_Runner):
+    """Whole sequence in HBM, no host round trip per scan."""
+    _PREFIX = "ptl_seq_"
+
+    def __init__(self, n_scans, points_per_scan, n_imu, *, max_range=70.0, min_range=1.0, use_imu_prediction=False,
+                 with_ekf=True, device_id=0, ekf=None, imu_deskew=False, knot_capacity=None, **icp_over):
+        """imu_deskew: the column tables from the filter's IMU-propagated trajectory (upload_sweep_times before running; knot_capacity
+        defaults to n_imu + 1, enough for any split of the samples; include/ptudes_mi.h ptl_seq_imu_deskew_enable)"""
+        self.cfg = _seq_cfg(n_scans, points_per_scan, n_imu, max_range, min_range, use_imu_prediction, with_ekf, device_id, ekf, icp_over)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_seq_create(C.byref(self.cfg), C.byref(self._h)))
+        self.n_scans = n_scans
+        self._init_imu_deskew(imu_deskew, knot_capacity)
 
     def upload_sweep_times(self, t0t1):
         """(n_scans, 2) absolute (t0, t1) per sweep on the IMU clock"""
@@ -457,47 +545,17 @@ class SeqRunner:
     def knots(self):
         return _knots(self.knot_capacity, lambda p, m, n, o: L.lib().ptl_seq_knots(self._h, p, m, n, o))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().ptl_seq_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def upload_scan(self, k, xyz_f32):
-        x = np.ascontiguousarray(xyz_f32, dtype=np.float32)
-        if x.size != self.cfg.points_per_scan * 3:
-            raise ValueError("scan size mismatch")
-        L.check(L.lib().ptl_seq_upload_scan(self._h, k, x.ctypes.data_as(C.POINTER(C.c_float))))
+        L.check(L.lib().ptl_seq_upload_scan(self._h, k, _scan_f32(self.cfg, xyz_f32)))
 
     def upload_range(self, k, range_mm):
-        r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
-        if r.size != self.cfg.points_per_scan:
-            raise ValueError("range image size mismatch")
-        L.check(L.lib().ptl_seq_upload_range(self._h, k, r.ctypes.data_as(C.POINTER(C.c_uint32))))
-
-    def set_lut(self, lut, active_beams=0):
-        self._lut = lut  # keep alive
-        L.check(L.lib().ptl_seq_set_lut(self._h, lut._h, int(active_beams)))
+        L.check(L.lib().ptl_seq_upload_range(self._h, k, _range_u32(self.cfg, range_mm)))
 
     def upload_imu(self, imu_rows, imu_end):
-        r = L.as_f64(imu_rows).reshape(-1, 7) if len(imu_rows) else np.zeros((0, 7))
-        e = np.ascontiguousarray(imu_end, dtype=np.int64)
-        if len(e) != self.n_scans:
-            raise ValueError("imu_end needs one entry per scan")
-        L.check(L.lib().ptl_seq_upload_imu(self._h, L.dptr(r) if len(r) else None, e.ctypes.data_as(L.c_i64_p)))
-
-    def run(self, n=None):
-        L.check(L.lib().ptl_seq_run(self._h, self.n_scans if n is None else n))
+        L.check(L.lib().ptl_seq_upload_imu(self._h, *_imu_args(self.n_scans, imu_rows, imu_end)))
 
     def advance(self, n):
         L.check(L.lib().ptl_seq_advance(self._h, n))
-
-    def enqueue(self, n):
-        L.check(L.lib().ptl_seq_enqueue(self._h, n))
-
-    def wait(self):
-        L.check(L.lib().ptl_seq_wait(self._h))
 
     def copy_traj(self, dst_device_ptr, max_rows):
         rows = C.c_int64()
@@ -505,31 +563,12 @@ class SeqRunner:
         return rows.value
 
     def results(self):
-        n = self.n_scans
-        res_poses, res_t, kiss = np.empty((n, 4, 4)), np.empty(n), np.empty((n, 4, 4))
-        stats = (L.IcpStats * n)()
-        w = C.c_int64()
-        L.check(L.lib().ptl_seq_results(self._h, L.dptr(res_poses), L.dptr(res_t), L.dptr(kiss), stats, n,
-                                        C.byref(w)))
-        m = w.value
-        out = dict(kiss_poses=kiss[:m], stats=[stats[i].as_dict() for i in range(m)])
-        if self.cfg.with_ekf:
-            out.update(res_poses=res_poses[:m], res_t=res_t[:m])
-        return out
+        return _results(self.n_scans, self.cfg.with_ekf, lambda *a: L.lib().ptl_seq_results(self._h, *a))
 
     def traj_device(self):
         p, rows = C.c_void_p(), C.c_int64()
         L.check(L.lib().ptl_seq_traj_device(self._h, C.byref(p), C.byref(rows)))
         return p.value, rows.value
-
-    def profile(self, enable=True, reset=False):
-        ms, n = C.c_double(), C.c_int64()
-        L.check(L.lib().ptl_seq_profile(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
-        return ms.value, n.value
-
-    def enable_smoother(self, on=True):
-        """log the filter's history (capacity n_scans) for smooth(); include/ptudes_mi.h ptl_seq_smoother_enable"""
-        L.check(L.lib().ptl_seq_smoother_enable(self._h, int(bool(on))))
 
     def smoother_log(self):
         """the raw history log of the sequence's filter (dict of per-entry arrays; core._LOG_FIELDS)"""
@@ -540,13 +579,14 @@ class SeqRunner:
         return _smoothed(self.n_scans, nav, cov, lambda p, t, n, c, w: L.lib().ptl_seq_smooth(self._h, p, t, n, c, w))
 
 
-class BatchRunner:
+class BatchRunner(_Runner):
     """Up to 256 independent sequences on one GPU (lockstep: 32); sequence s lives on XCD s & 7 (the workgroups with
     blockIdx & 7 == s & 7).  Two drivers (`free_running`): True (the default with the 8-lane Gauss-Newton kernel) - one
     persistent launch carries up to `scans_per_launch` scans of every sequence, teams of `team_workgroups` workgroups take
     the scans of their XCD's sequences as they come free; False - lockstep, one launch per stage for all sequences, a step
     lasts as long as its slowest sequence.  Either way the per-sequence results are bit-identical to
     `SeqRunner(..., gn_workgroups=<workgroups per team>, gn_lanes_per_point=<the batch's>)`."""
+    _PREFIX = "ptl_batch_"
 
     def __init__(self, n_sequences, n_scans, points_per_scan, n_imu, *, max_range=70.0, min_range=1.0,
                  use_imu_prediction=False, with_ekf=True, device_id=0, ekf=None, free_running=None, scans_per_launch=0,
@@ -554,17 +594,11 @@ class BatchRunner:
         """range_input: every sweep will arrive as a raw range image (set_lut + upload_range) and stays one in HBM - 4 bytes per pixel
         resident instead of 12 (include/ptudes_mi.h ptl_seq_cfg.range_input).  resident_scans: R >= 2 = a ring of R sweep slots per sequence
         instead of all n_scans - sweeps are uploaded in order, later ones while a launch works on earlier ones (ptl_seq_cfg.resident_scans)"""
-        cfg = L.SeqCfg()
-        cfg.range_input = int(bool(range_input))
-        cfg.resident_scans = int(resident_scans)
         icp_over.setdefault("gn_lanes_per_point", 8)  # a workgroup walks ~200 points per iteration here: the throughput form
         if icp_over["gn_lanes_per_point"] == 8:
             icp_over.setdefault("gn_threads", 512)
-        cfg.icp = icp_cfg(max_range, min_range, device_id=device_id, **icp_over)
-        cfg.ekf = ekf if ekf is not None else ekf_cfg(device_id=device_id)
-        cfg.n_scans, cfg.points_per_scan, cfg.n_imu = n_scans, points_per_scan, n_imu
-        cfg.use_imu_prediction = int(bool(use_imu_prediction))
-        cfg.with_ekf = int(bool(with_ekf))
+        cfg = _seq_cfg(n_scans, points_per_scan, n_imu, max_range, min_range, use_imu_prediction, with_ekf, device_id, ekf, icp_over,
+                       range_input=int(bool(range_input)), resident_scans=int(resident_scans))
         self.cfg, self.S, self.n_scans = cfg, int(n_sequences), n_scans
         self._h = C.c_void_p()
         L.check(L.lib().ptl_batch_create(C.byref(cfg), self.S, C.byref(self._h)))
@@ -573,19 +607,7 @@ class BatchRunner:
             L.check(L.lib().ptl_batch_set_driver(self._h, int(self.free_running), int(scans_per_launch)))
         if team_workgroups:
             L.check(L.lib().ptl_batch_set_team_workgroups(self._h, int(team_workgroups)))
-        self.knot_capacity = 0
-        if imu_deskew:
-            try:
-                self.imu_deskew(True, knot_capacity)
-            except Exception:
-                self.close()
-                raise
-
-    def imu_deskew(self, on=True, knot_capacity=None):
-        """IMU deskew for every sequence (upload_sweep_times(s, ...) for each before running); include/ptudes_mi.h ptl_batch_imu_deskew_enable"""
-        cap = int(self.cfg.n_imu) + 1 if knot_capacity is None else int(knot_capacity)
-        L.check(L.lib().ptl_batch_imu_deskew_enable(self._h, int(bool(on)), cap if on else 0))
-        self.knot_capacity = cap if on else 0
+        self._init_imu_deskew(imu_deskew, knot_capacity)
 
     def upload_sweep_times(self, s, t0t1):
         t = _sweep_times(t0t1, self.n_scans)
@@ -641,55 +663,17 @@ class BatchRunner:
         L.check(L.lib().ptl_batch_debug_set_map_points_per_thread(self._h, int(points), C.byref(v)))
         return v.value
 
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().ptl_batch_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def upload_scan(self, s, k, xyz_f32):
-        x = np.ascontiguousarray(xyz_f32, dtype=np.float32)
-        if x.size != self.cfg.points_per_scan * 3:
-            raise ValueError("scan size mismatch")
-        L.check(L.lib().ptl_batch_upload_scan(self._h, s, k, x.ctypes.data_as(C.POINTER(C.c_float))))
-
-    def set_lut(self, lut, active_beams=0):
-        self._lut = lut
-        L.check(L.lib().ptl_batch_set_lut(self._h, lut._h, int(active_beams)))
+        L.check(L.lib().ptl_batch_upload_scan(self._h, s, k, _scan_f32(self.cfg, xyz_f32)))
 
     def upload_range(self, s, k, range_mm):
-        r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
-        L.check(L.lib().ptl_batch_upload_range(self._h, s, k, r.ctypes.data_as(C.POINTER(C.c_uint32))))
+        L.check(L.lib().ptl_batch_upload_range(self._h, s, k, _range_u32(self.cfg, range_mm)))
 
     def upload_imu(self, s, imu_rows, imu_end):
-        r = L.as_f64(imu_rows).reshape(-1, 7) if len(imu_rows) else np.zeros((0, 7))
-        e = np.ascontiguousarray(imu_end, dtype=np.int64)
-        if len(e) != self.n_scans:
-            raise ValueError("imu_end needs one entry per scan")
-        L.check(L.lib().ptl_batch_upload_imu(self._h, s, L.dptr(r) if len(r) else None, e.ctypes.data_as(L.c_i64_p)))
-
-    def run(self, n=None):
-        L.check(L.lib().ptl_batch_run(self._h, self.n_scans if n is None else n))
-
-    def enqueue(self, n):
-        L.check(L.lib().ptl_batch_enqueue(self._h, n))
-
-    def wait(self):
-        L.check(L.lib().ptl_batch_wait(self._h))
+        L.check(L.lib().ptl_batch_upload_imu(self._h, s, *_imu_args(self.n_scans, imu_rows, imu_end)))
 
     def results(self, s):
-        n = self.n_scans
-        res_poses, res_t, kiss = np.empty((n, 4, 4)), np.empty(n), np.empty((n, 4, 4))
-        stats = (L.IcpStats * n)()
-        w = C.c_int64()
-        L.check(L.lib().ptl_batch_results(self._h, s, L.dptr(res_poses), L.dptr(res_t), L.dptr(kiss), stats, n,
-                                          C.byref(w)))
-        m = w.value
-        out = dict(kiss_poses=kiss[:m], stats=[stats[i].as_dict() for i in range(m)])
-        if self.cfg.with_ekf:
-            out.update(res_poses=res_poses[:m], res_t=res_t[:m])
-        return out
+        return _results(self.n_scans, self.cfg.with_ekf, lambda *a: L.lib().ptl_batch_results(self._h, s, *a))
 
     def copy_traj(self, s, dst_device_ptr, max_rows):
         rows = C.c_int64()
@@ -709,15 +693,6 @@ class BatchRunner:
         out = (C.c_int64 * 8)()
         L.check(L.lib().ptl_batch_seq_clocks(self._h, s, out))
         return tuple(int(out[i]) for i in range(6)), int(out[6])
-
-    def profile(self, enable=True, reset=False):
-        ms, n = C.c_double(), C.c_int64()
-        L.check(L.lib().ptl_batch_profile(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
-        return ms.value, n.value
-
-    def enable_smoother(self, on=True):
-        """log every sequence's filter history (capacity n_scans each); include/ptudes_mi.h ptl_batch_smoother_enable"""
-        L.check(L.lib().ptl_batch_smoother_enable(self._h, int(bool(on))))
 
     def smooth(self):
         """the backward pass of every sequence in one launch (waits); smoothed(s) then gives sequence s's rows"""

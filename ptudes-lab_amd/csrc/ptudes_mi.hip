@@ -1126,15 +1126,22 @@ extern "C" int ptl_ekf_destroy(ptl_ekf* h) {
     delete h;
     return PTL_OK;
 }
-extern "C" int ptl_ekf_process_imu_batch(ptl_ekf* h, const double* imu, int64_t n) {
-    if (!h || (!imu && n > 0)) return set_err(PTL_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+// n IMU rows -> the filter's predicts, staged through d_buf buf_rows at a time with a wait for the buffer's reuse; wait_last = false leaves
+// the last buf_rows or fewer in flight for the caller's own wait
+static int ekf_stage_imu(ptl_ekf* h, const double* imu, int64_t n, bool wait_last) {
     for (int64_t off = 0; off < n; off += h->buf_rows) {
         const int m = (int)((n - off) < h->buf_rows ? (n - off) : h->buf_rows);
         HIPCHK(hipMemcpyAsync(h->d_buf, imu + 7 * off, (size_t)m * 56, hipMemcpyHostToDevice, h->stream));
         k_ekf_step<<<1, EKF_THREADS, 0, h->stream>>>(h->st, h->d_buf, 0, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        HIPCHK(hipStreamSynchronize(h->stream));  // staging buffer reuse
+        if (wait_last || off + m < n) HIPCHK(hipStreamSynchronize(h->stream));
     }
+    return PTL_OK;
+}
+extern "C" int ptl_ekf_process_imu_batch(ptl_ekf* h, const double* imu, int64_t n) {
+    if (!h || (!imu && n > 0)) return set_err(PTL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    const int rc = ekf_stage_imu(h, imu, n, true);
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return PTL_OK;
 }
@@ -1432,16 +1439,8 @@ static int icp_ekf_step_impl(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int
     // processImu x n_imu (ptl_ekf_process_imu_batch's kernel).  Any count is served, like the call-by-call loop (a long IMU-only prefix,
     // dropped lidar frames, a 1 kHz IMU): what does not fit the staging buffer goes first, buf_rows samples at a time with a wait for
     // the buffer's reuse; the last buf_rows or fewer ride on this step's single wait.
-    int64_t off = 0;
-    for (; n_imu - off > e->buf_rows; off += e->buf_rows) {
-        HIPCHK(hipMemcpyAsync(e->d_buf, imu_rows + 7 * off, (size_t)e->buf_rows * 56, hipMemcpyHostToDevice, es));
-        k_ekf_step<<<1, EKF_THREADS, 0, es>>>(e->st, e->d_buf, 0, (int)e->buf_rows, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        HIPCHK(hipStreamSynchronize(es));
-    }
-    if (n_imu > off) {
-        HIPCHK(hipMemcpyAsync(e->d_buf, imu_rows + 7 * off, (size_t)(n_imu - off) * 56, hipMemcpyHostToDevice, es));
-        k_ekf_step<<<1, EKF_THREADS, 0, es>>>(e->st, e->d_buf, 0, (int)(n_imu - off), nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-    }
+    int rc = ekf_stage_imu(e, imu_rows, n_imu, false);
+    if (rc) return rc;
     const size_t esz = dtype == PTL_F32 ? 4 : 8;
     if (n) HIPCHK(hipMemcpyAsync(h->d_in, xyz, (size_t)n * 3 * esz, hipMemcpyHostToDevice, h->stream));
     if (t01 && n) HIPCHK(hipMemcpyAsync(h->d_t01, t01, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
@@ -1456,13 +1455,13 @@ static int icp_ekf_step_impl(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int
     }
     if (imu_deskew) {  // this scan's sweep times, the wiring to the filter's knots, and the prologue behind the predicts
         k_dk_times<<<1, 64, 0, h->stream>>>(h->dk_t0t1 + 2 * h->scans_done, t0, t1);
-        int rc = dk_wire(h, e, h->dk_t0t1, h->dk_modes, h->dk_cap);
+        rc = dk_wire(h, e, h->dk_t0t1, h->dk_modes, h->dk_cap);
         if (rc) return rc;
         h->pro_wait = h->ev_step_guess;
     }
     h->gn_done = h->ev_step_gn;
-    int rc = icp_enqueue_scan(h, dtype == PTL_F32 ? (const float*)h->d_in : nullptr, dtype == PTL_F64 ? (const double*)h->d_in : nullptr,
-                              t01 ? h->d_t01 : nullptr, n, guess_ptr);
+    rc = icp_enqueue_scan(h, dtype == PTL_F32 ? (const float*)h->d_in : nullptr, dtype == PTL_F64 ? (const double*)h->d_in : nullptr,
+                          t01 ? h->d_t01 : nullptr, n, guess_ptr);
     h->gn_wait = nullptr; h->gn_done = nullptr; h->pro_wait = nullptr;
     if (imu_deskew) {  // the handle's other entry points keep the constant-velocity deskew
         const int rc2 = dk_wire(h, nullptr, nullptr, nullptr, 0);
@@ -1500,50 +1499,207 @@ extern "C" int ptl_icp_ekf_step_imu_deskew(ptl_icp* h, ptl_ekf* e, const double*
     return icp_ekf_step_impl(h, e, imu_rows, n_imu, xyz, dtype, n, nullptr, guess, use_imu_prediction, kiss_pose, ekf_pose, ekf_ts, stats, true, t0, t1);
 }
 
+// ================================================================================================ one sequence of a runner
+// What the sequence runner keeps once and the batched runner once per sequence: the registration and the filter, the sweep slots, the IMU
+// rows and their split over the scans, the result rows, and the IMU deskew's sweep times and mode record.  The streams, events and the
+// driver's position stay with the runner: the helpers below enqueue nothing on a stream of their own and leave synchronising to the caller.
+struct SeqLane {
+    ptl_icp* icp = nullptr;
+    ptl_ekf* ekf = nullptr;
+    float* d_scans = nullptr;       // sweep slots
+    double* d_imu = nullptr;        // [n_imu][7]
+    std::vector<int64_t> imu_end;   // [n_scans] IMU samples before scan k
+    int* d_imu_end = nullptr;       // [n_scans] the same on the device (batched runner: its kernels read it)
+    int64_t imu_pos = 0;            // IMU samples the filter has been given
+    double* d_res_poses = nullptr;  // [n_scans][16]
+    double* d_res_t = nullptr;      // [n_scans]
+    double* d_rows = nullptr;       // [n_scans][8]
+    // IMU deskew: sweep times and modes of all n_scans (also with the sweep ring), and whether the times came since it was enabled
+    double* d_dk_t0t1 = nullptr;    // [n_scans][2]
+    int* d_dk_modes = nullptr;      // [n_scans]
+    bool dk_times = false;
+};
+
+// what ptl_seq_create and ptl_batch_create check and settle alike: `out` = *cfg with room for a whole sweep in the registration and the
+// filter on the registration's device
+static int seq_cfg_settle(const ptl_seq_cfg* cfg, ptl_seq_cfg* out) {
+    ABI_CHECK(ptl_seq_cfg, cfg);
+    ABI_CHECK(ptl_icp_cfg, &cfg->icp);
+    ABI_CHECK(ptl_ekf_cfg, &cfg->ekf);
+    if (cfg->n_scans < 1 || cfg->points_per_scan < 1) return set_err(PTL_ERR_ARG, "empty sequence");
+    if (ptl_device_count() <= cfg->icp.device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", cfg->icp.device_id);
+    HIPCHK(hipSetDevice(cfg->icp.device_id));
+    *out = *cfg;
+    if (out->icp.max_points_per_scan < cfg->points_per_scan) out->icp.max_points_per_scan = cfg->points_per_scan;
+    out->ekf.device_id = cfg->icp.device_id;
+    return PTL_OK;
+}
+static void lane_free(SeqLane& l) {
+    if (l.icp) icp_free(l.icp);
+    if (l.ekf) ptl_ekf_destroy(l.ekf);
+    for (void* p : {(void*)l.d_scans, (void*)l.d_imu, (void*)l.d_imu_end, (void*)l.d_res_poses, (void*)l.d_res_t, (void*)l.d_rows,
+                    (void*)l.d_dk_t0t1, (void*)l.d_dk_modes})
+        if (p) (void)hipFree(p);
+}
+// the registration (on `stream`), the filter (on `ekf_stream`), `slots` sweep slots of `slot_bytes` each, the IMU rows and the result rows of
+// a settled configuration.  batch: a member of a batch (icp_create_impl's batch_member, the whole trajectory up front, the IMU split on the device)
+static int lane_create(SeqLane& l, const ptl_seq_cfg& cfg, hipStream_t stream, hipStream_t ekf_stream, size_t slot_bytes, size_t slots, bool batch,
+                       const char* who) {
+    int rc = icp_create_impl(&cfg.icp, stream, &l.icp, batch);
+    if (rc == PTL_OK) rc = ekf_create_impl(&cfg.ekf, ekf_stream, &l.ekf);
+    while (batch && rc == PTL_OK && l.icp->traj_cap < cfg.n_scans) rc = icp_grow_traj(l.icp);
+    if (rc) return rc;
+    const size_t n = (size_t)cfg.n_scans, nim = cfg.n_imu > 0 ? (size_t)cfg.n_imu : 1;
+    if (hipMalloc((void**)&l.d_scans, slots * slot_bytes) != hipSuccess || dalloc(&l.d_imu, nim * 7) != hipSuccess ||
+        dalloc(&l.d_res_poses, n * 16) != hipSuccess || dalloc(&l.d_res_t, n) != hipSuccess || dalloc(&l.d_rows, n * 8) != hipSuccess ||
+        (batch && (dalloc(&l.d_imu_end, n) != hipSuccess || hipMemset(l.d_imu_end, 0, n * sizeof(int)) != hipSuccess)))
+        return set_err(PTL_ERR_HIP, "%s: allocation failed (%.1f MB of sweeps per sequence)", who, slots * slot_bytes / 1e6);
+    l.imu_end.assign(n, 0);
+    return PTL_OK;
+}
+// the IMU rows and their split over the scans.  one_per_scan: at least one sample between consecutive scans - lockstep batching cannot
+// skip a scan of one sequence only (ekf_bench.py:512-518)
+static int lane_upload_imu(SeqLane& l, const ptl_seq_cfg& cfg, const double* imu, const int64_t* imu_end, bool one_per_scan) {
+    if (cfg.n_imu > 0) HIPCHK(hipMemcpy(l.d_imu, imu, (size_t)cfg.n_imu * 56, hipMemcpyHostToDevice));
+    for (int64_t k = 0; k < cfg.n_scans; ++k) {
+        if (imu_end[k] < 0 || imu_end[k] > cfg.n_imu || (k && imu_end[k] < imu_end[k - 1])) return set_err(PTL_ERR_ARG, "imu_end must be non-decreasing within [0, n_imu]");
+        if (one_per_scan && k && imu_end[k] == imu_end[k - 1]) return set_err(PTL_ERR_ARG, "batched runs need at least one IMU sample between consecutive scans (scan %lld)", (long long)k);
+        l.imu_end[(size_t)k] = imu_end[k];
+    }
+    if (!l.d_imu_end) return PTL_OK;
+    const std::vector<int> e32(l.imu_end.begin(), l.imu_end.end());
+    HIPCHK(hipMemcpy(l.d_imu_end, e32.data(), e32.size() * sizeof(int), hipMemcpyHostToDevice));
+    return PTL_OK;
+}
+// the first min(n_out, max_n) rows of the lane's results -> host; the caller has synchronised its streams
+static int lane_results(const SeqLane& l, bool with_ekf, int64_t n_out, double* res_poses, double* res_t, double* kiss_poses, ptl_icp_stats* stats,
+                        int64_t max_n, int64_t* n_written) {
+    const int64_t n = n_out < max_n ? n_out : max_n;
+    if (n > 0) {
+        if (res_poses && with_ekf) HIPCHK(hipMemcpy(res_poses, l.d_res_poses, (size_t)n * 128, hipMemcpyDeviceToHost));
+        if (res_t && with_ekf) HIPCHK(hipMemcpy(res_t, l.d_res_t, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (kiss_poses) HIPCHK(hipMemcpy(kiss_poses, l.icp->c.traj, (size_t)n * 128, hipMemcpyDeviceToHost));
+        if (stats) {
+            std::vector<ScanStats> tmp((size_t)n);
+            HIPCHK(hipMemcpy(tmp.data(), l.icp->c.sstats, (size_t)n * sizeof(ScanStats), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < n; ++i) stats_out(tmp[(size_t)i], &stats[i]);
+        }
+    }
+    if (n_written) *n_written = n;
+    return PTL_OK;
+}
+// the first min(n_out, max_rows) trajectory rows -> device memory, on `stream` (the caller has synchronised its other streams)
+static int lane_copy_traj(const SeqLane& l, const ptl_seq_cfg& cfg, int64_t n_out, hipStream_t stream, void* dst_device, int64_t max_rows, int64_t* rows) {
+    if (!cfg.with_ekf) return set_err(PTL_ERR_STATE, "trajectory rows need with_ekf");
+    const int64_t n = n_out < max_rows ? n_out : max_rows;
+    if (n > 0) HIPCHK(hipMemcpyAsync(dst_device, l.d_rows, (size_t)n * 64, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (rows) *rows = n;
+    return PTL_OK;
+}
+// the filter's smoother log and knot list (the caller has synchronised its streams)
+static int lane_smoother_log(const SeqLane& l, const ptl_seq_cfg& cfg, const char* who, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
+    if (!cfg.with_ekf) return set_err(PTL_ERR_STATE, "%s: an ICP-only run has no filter log", who);
+    return ekf_log_read(l.ekf, entries, max_entries, n_entries, overflow);
+}
+static int lane_knots(const SeqLane& l, const ptl_seq_cfg& cfg, const char* who, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
+    if (!cfg.with_ekf) return set_err(PTL_ERR_STATE, "%s: an ICP-only run has no filter", who);
+    return ekf_knots_read(l.ekf, knots, max_knots, n_knots, overflow);
+}
+
+// ---- IMU deskew of a lane
+// knots the filter needs for the lane's IMU split, against `cap`
+static int lane_dk_knots_check(const SeqLane& l, int64_t cap, const char* who, int seq) {
+    const int64_t need = dk_knots_needed(l.imu_end);
+    if (need > cap) return set_err(PTL_ERR_ARG, "%s: IMU deskew: sequence %d: the IMU samples between two scans need %lld knots, capacity %lld", who, seq, (long long)need, (long long)cap);
+    return PTL_OK;
+}
+// ptl_*_imu_deskew_enable's arguments against the configuration and the IMU split of each of the n lanes
+static int dk_enable_check(const ptl_seq_cfg& cfg, const SeqLane* lanes, int n, int32_t on, int64_t knot_capacity, const char* who) {
+    if (!cfg.with_ekf) return set_err(PTL_ERR_STATE, "%s: an ICP-only run (with_ekf = 0) has no filter to deskew with", who);
+    if (!on) return PTL_OK;
+    if (!cfg.icp.deskew) return set_err(PTL_ERR_STATE, "%s: deskew is off in the configuration", who);
+    if (knot_capacity < 2) return set_err(PTL_ERR_ARG, "%s: knot_capacity must be >= 2", who);
+    for (int s = 0; s < n; ++s) {
+        const int rc = lane_dk_knots_check(lanes[s], knot_capacity, who, s);
+        if (rc) return rc;
+    }
+    return PTL_OK;
+}
+// knot_capacity > 0: a fresh knot list, an empty mode record and the registration wired to both (the sweep times follow); 0: off, the
+// constant-velocity deskew.  The caller's streams are idle.
+static int lane_dk_set(SeqLane& l, int64_t n_scans, int64_t knot_capacity) {
+    const size_t n = (size_t)n_scans;
+    l.dk_times = false;
+    int rc = dk_wire(l.icp, nullptr, nullptr, nullptr, 0);
+    if (rc == PTL_OK) rc = ekf_knots_set(l.ekf, 0);
+    if (rc || knot_capacity <= 0) return rc;
+    if ((!l.d_dk_t0t1 && dalloc(&l.d_dk_t0t1, 2 * n) != hipSuccess) || (!l.d_dk_modes && dalloc(&l.d_dk_modes, n) != hipSuccess))
+        return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
+    HIPCHK(hipMemset(l.d_dk_modes, 0, n * sizeof(int)));
+    rc = ekf_knots_set(l.ekf, knot_capacity);
+    return rc ? rc : dk_wire(l.icp, l.ekf, l.d_dk_t0t1, l.d_dk_modes, (int64_t)n);
+}
+// before an enqueue: sweep times there, knots enough
+static int lane_dk_ready(const SeqLane& l, const char* who, int seq) {
+    if (!l.dk_times) return set_err(PTL_ERR_STATE, "%s: IMU deskew: sequence %d has no sweep times (upload_sweep_times)", who, seq);
+    return lane_dk_knots_check(l, l.ekf->knot_cap, who, seq);
+}
+// after a wait: a truncated knot list is an error, not a quiet fallback
+static int lane_dk_overflow(const SeqLane& l, const char* who, int seq) {
+    int ovf = 0;
+    const int rc = ekf_knot_overflow(l.ekf, &ovf);
+    if (rc) return rc;
+    if (ovf) return set_err(PTL_ERR_CAPACITY, "%s: IMU deskew: sequence %d: the filter's knot list overflowed (capacity %lld)", who, seq, (long long)l.ekf->knot_cap);
+    return PTL_OK;
+}
+// (t0, t1) of every scan, t1 >= t0 (the caller has synchronised its streams)
+static int lane_upload_sweep_times(SeqLane& l, int64_t n_scans, const double* t0t1, const char* who) {
+    for (int64_t k = 0; k < n_scans; ++k)
+        if (!(t0t1[2 * k + 1] >= t0t1[2 * k])) return set_err(PTL_ERR_ARG, "%s: scan %lld has t1 < t0", who, (long long)k);
+    HIPCHK(hipMemcpy(l.d_dk_t0t1, t0t1, (size_t)n_scans * 16, hipMemcpyHostToDevice));
+    l.dk_times = true;
+    return PTL_OK;
+}
+// modes of the first min(n_out, max_n) scans: the device record with IMU deskew on, else the constant-velocity deskew's (none for the first
+// two scans); the caller has synchronised its streams
+static int lane_deskew_modes(const SeqLane& l, const ptl_seq_cfg& cfg, bool dk_on, int64_t n_out, int32_t* modes, int64_t max_n, int64_t* n) {
+    const int64_t m = n_out < max_n ? n_out : max_n;
+    if (!dk_on) {
+        for (int64_t k = 0; k < m; ++k) modes[k] = (cfg.icp.deskew && k >= 2) ? DK_MODE_CV : DK_MODE_NONE;
+    } else if (m > 0) {
+        HIPCHK(hipMemcpy(modes, l.d_dk_modes, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (n) *n = m;
+    return PTL_OK;
+}
+
 // ================================================================================================ sequence runner
 struct ptl_seq {
     ptl_seq_cfg cfg;
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
     // The EKF launches run on their own stream: the update with scan k's pose and the IMU predicts up to scan k+1
     // overlap scan k's map update and scan k+1's deskew / downsampling; only the GN kernel waits for the EKF
     // (its guess), and the EKF waits for the GN kernel (the pose measurement).
-    hipStream_t ekf_stream;
-    hipEvent_t ev_guess, ev_gn;
-    ptl_icp* icp;
-    ptl_ekf* ekf;
-    float* d_scans;      // [n_scans][pps][3] f32
-    double* d_imu;       // [n_imu][7]
-    std::vector<int64_t> imu_end;
-    double* d_res_poses; // [n_scans][16]
-    double* d_res_t;     // [n_scans]
-    double* d_rows;      // [n_scans][8]
+    hipStream_t ekf_stream = nullptr;
+    hipEvent_t ev_guess = nullptr, ev_gn = nullptr;
+    SeqLane lane;  // sweep slots: [n_scans][pps][3] f32
     std::vector<int64_t> scan_of_out;  // scan index of each processed output
-    int64_t n_out;
-    int64_t next_scan, imu_pos, imus_per_scan;  // driver-loop position (ekf_bench.py:491-518)
-    ptl_lut* lut;                    // non-null => sweeps were uploaded as u32 range images
+    int64_t n_out = 0;
+    int64_t next_scan = 0, imus_per_scan = 0;  // driver-loop position (ekf_bench.py:491-518)
+    ptl_lut* lut = nullptr;          // non-null => sweeps were uploaded as u32 range images
     std::vector<unsigned char> is_range;
-    // IMU deskew (ptl_seq_imu_deskew_enable): sweep times and modes per scan, the event the prologue waits for
-    bool dk_on, dk_times;
-    double* d_dk_t0t1;   // [n_scans][2]
-    int* d_dk_modes;     // [n_scans]
-    hipEvent_t ev_pro;
+    // IMU deskew (ptl_seq_imu_deskew_enable): on, and the event the prologue waits for
+    bool dk_on = false;
+    hipEvent_t ev_pro = nullptr;
 };
 
 extern "C" int ptl_seq_destroy(ptl_seq* s) {
     if (!s) return PTL_OK;
     (void)hipSetDevice(s->cfg.icp.device_id);
-    if (s->icp) icp_free(s->icp);
-    if (s->ekf) ptl_ekf_destroy(s->ekf);
-    if (s->d_scans) (void)hipFree(s->d_scans);
-    if (s->d_imu) (void)hipFree(s->d_imu);
-    if (s->d_res_poses) (void)hipFree(s->d_res_poses);
-    if (s->d_res_t) (void)hipFree(s->d_res_t);
-    if (s->d_rows) (void)hipFree(s->d_rows);
-    if (s->ev_guess) (void)hipEventDestroy(s->ev_guess);
-    if (s->ev_gn) (void)hipEventDestroy(s->ev_gn);
-    if (s->ev_pro) (void)hipEventDestroy(s->ev_pro);
-    if (s->d_dk_t0t1) (void)hipFree(s->d_dk_t0t1);
-    if (s->d_dk_modes) (void)hipFree(s->d_dk_modes);
+    lane_free(s->lane);
+    for (hipEvent_t e : {s->ev_guess, s->ev_gn, s->ev_pro})
+        if (e) (void)hipEventDestroy(e);
     if (s->ekf_stream) (void)hipStreamDestroy(s->ekf_stream);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1551,18 +1707,11 @@ extern "C" int ptl_seq_destroy(ptl_seq* s) {
 }
 extern "C" int ptl_seq_create(const ptl_seq_cfg* cfg, ptl_seq** out) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
-    ABI_CHECK(ptl_seq_cfg, cfg);
-    ABI_CHECK(ptl_icp_cfg, &cfg->icp);
-    ABI_CHECK(ptl_ekf_cfg, &cfg->ekf);
-    if (cfg->n_scans < 1 || cfg->points_per_scan < 1) return set_err(PTL_ERR_ARG, "empty sequence");
-    if (ptl_device_count() <= cfg->icp.device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", cfg->icp.device_id);
-    HIPCHK(hipSetDevice(cfg->icp.device_id));
+    ptl_seq_cfg c;
+    int rc = seq_cfg_settle(cfg, &c);
+    if (rc) return rc;
     ptl_seq* s = new ptl_seq();
-    s->cfg = *cfg;
-    s->icp = nullptr; s->ekf = nullptr; s->d_scans = nullptr; s->d_imu = nullptr;
-    s->d_res_poses = nullptr; s->d_res_t = nullptr; s->d_rows = nullptr; s->n_out = 0; s->stream = nullptr;
-    s->ekf_stream = nullptr; s->ev_guess = nullptr; s->ev_gn = nullptr;
-    s->dk_on = false; s->dk_times = false; s->d_dk_t0t1 = nullptr; s->d_dk_modes = nullptr; s->ev_pro = nullptr;
+    s->cfg = c;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&s->ekf_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_guess, hipEventDisableTiming) != hipSuccess ||
@@ -1570,23 +1719,9 @@ extern "C" int ptl_seq_create(const ptl_seq_cfg* cfg, ptl_seq** out) {
         ptl_seq_destroy(s);
         return set_err(PTL_ERR_HIP, "stream / event creation failed");
     }
-    ptl_icp_cfg ic = cfg->icp;
-    if (ic.max_points_per_scan < cfg->points_per_scan) ic.max_points_per_scan = cfg->points_per_scan;
-    s->cfg.icp = ic;
-    ptl_ekf_cfg ec = cfg->ekf;
-    ec.device_id = ic.device_id;
-    int rc = icp_create_impl(&ic, s->stream, &s->icp);
-    if (rc == PTL_OK) rc = ekf_create_impl(&ec, s->ekf_stream, &s->ekf);
-    const size_t nim = cfg->n_imu > 0 ? (size_t)cfg->n_imu : 1;
-    if (rc == PTL_OK &&
-        (hipMalloc((void**)&s->d_scans, (size_t)cfg->n_scans * cfg->points_per_scan * 12) != hipSuccess ||
-         dalloc(&s->d_imu, nim * 7) != hipSuccess || dalloc(&s->d_res_poses, (size_t)cfg->n_scans * 16) != hipSuccess ||
-         dalloc(&s->d_res_t, (size_t)cfg->n_scans) != hipSuccess || dalloc(&s->d_rows, (size_t)cfg->n_scans * 8) != hipSuccess))
-        rc = set_err(PTL_ERR_HIP, "sequence allocation failed (%.1f MB of scans)", cfg->n_scans * cfg->points_per_scan * 12 / 1e6);
+    rc = lane_create(s->lane, c, s->stream, s->ekf_stream, (size_t)c.points_per_scan * 12, (size_t)c.n_scans, false, "ptl_seq_create");
     if (rc) { ptl_seq_destroy(s); return rc; }
-    s->imu_end.assign((size_t)cfg->n_scans, 0);
-    s->is_range.assign((size_t)cfg->n_scans, 0);
-    s->lut = nullptr;
+    s->is_range.assign((size_t)c.n_scans, 0);
     *out = s;
     return PTL_OK;
 }
@@ -1594,7 +1729,7 @@ extern "C" int ptl_seq_upload_scan(ptl_seq* s, int64_t k, const float* xyz) {
     if (!s || !xyz || k < 0 || k >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     const size_t bytes = (size_t)s->cfg.points_per_scan * 12;
-    HIPCHK(hipMemcpy((char*)s->d_scans + (size_t)k * bytes, xyz, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char*)s->lane.d_scans + (size_t)k * bytes, xyz, bytes, hipMemcpyHostToDevice));
     return PTL_OK;
 }
 // sweep k as a raw range image (H*W u32 mm); needs ptl_seq_set_lut before running
@@ -1602,7 +1737,7 @@ extern "C" int ptl_seq_upload_range(ptl_seq* s, int64_t k, const uint32_t* range
     if (!s || !range_mm || k < 0 || k >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     const size_t slot = (size_t)s->cfg.points_per_scan * 12;
-    HIPCHK(hipMemcpy((char*)s->d_scans + (size_t)k * slot, range_mm, (size_t)s->cfg.points_per_scan * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char*)s->lane.d_scans + (size_t)k * slot, range_mm, (size_t)s->cfg.points_per_scan * 4, hipMemcpyHostToDevice));
     s->is_range[(size_t)k] = 1;
     return PTL_OK;
 }
@@ -1610,28 +1745,23 @@ extern "C" int ptl_seq_set_lut(ptl_seq* s, ptl_lut* lut, int32_t active_beams) {
     if (!s || !lut) return set_err(PTL_ERR_ARG, "null argument");
     if ((int64_t)lut->H * lut->W != s->cfg.points_per_scan) return set_err(PTL_ERR_ARG, "LUT size does not match points_per_scan");
     s->lut = lut;
-    return ptl_icp_set_active_beams(s->icp, lut->H, active_beams);
+    return ptl_icp_set_active_beams(s->lane.icp, lut->H, active_beams);
 }
 extern "C" int ptl_seq_upload_imu(ptl_seq* s, const double* imu, const int64_t* imu_end) {
     if (!s || !imu_end || (!imu && s->cfg.n_imu > 0)) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
-    if (s->cfg.n_imu > 0) HIPCHK(hipMemcpy(s->d_imu, imu, (size_t)s->cfg.n_imu * 56, hipMemcpyHostToDevice));
-    for (int64_t k = 0; k < s->cfg.n_scans; ++k) {
-        if (imu_end[k] < 0 || imu_end[k] > s->cfg.n_imu || (k && imu_end[k] < imu_end[k - 1])) return set_err(PTL_ERR_ARG, "imu_end must be non-decreasing within [0, n_imu]");
-        s->imu_end[(size_t)k] = imu_end[k];
-    }
-    return PTL_OK;
+    return lane_upload_imu(s->lane, s->cfg, imu, imu_end, false);
 }
 static int seq_reset(ptl_seq* s) {
-    int rc = icp_reset_device(s->icp);
+    int rc = icp_reset_device(s->lane.icp);
     if (rc) return rc;
-    rc = ekf_reset(s->ekf);
+    rc = ekf_reset(s->lane.ekf);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s->ekf_stream));  // EKF launches may go to either stream afterwards
     s->scan_of_out.clear();
     s->n_out = 0;
     s->next_scan = 0;
-    s->imu_pos = 0;
+    s->lane.imu_pos = 0;
     s->imus_per_scan = 1;  // ekf_bench.py:491
     return PTL_OK;
 }
@@ -1641,63 +1771,63 @@ static int seq_reset(ptl_seq* s) {
 extern "C" int ptl_seq_enqueue(ptl_seq* s, int64_t n) {
     if (!s || n < 0 || s->next_scan + n > s->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    SeqLane& l = s->lane;
     const bool with_ekf = s->cfg.with_ekf != 0;
-    const double* guess_ptr = (with_ekf && s->cfg.use_imu_prediction) ? (const double*)((char*)s->ekf->st + offsetof(EkfState, pose)) : nullptr;
+    const double* guess_ptr = (with_ekf && s->cfg.use_imu_prediction) ? (const double*)((char*)l.ekf->st + offsetof(EkfState, pose)) : nullptr;
     const size_t pps = (size_t)s->cfg.points_per_scan;
     const int64_t end = s->next_scan + n;
     hipStream_t es = s->ekf_stream;  // used when the EKF does not feed the registration (no IMU prediction)
     if (s->dk_on) {  // IMU deskew: sweep times, knots enough, and no scan the driver loop would skip (scan k's table is at index k)
-        if (!s->dk_times) return set_err(PTL_ERR_STATE, "IMU deskew: no sweep times (ptl_seq_upload_sweep_times)");
-        const int64_t need = dk_knots_needed(s->imu_end);
-        if (need > s->ekf->knot_cap) return set_err(PTL_ERR_ARG, "IMU deskew: the IMU samples between two scans need %lld knots, capacity %lld", (long long)need, (long long)s->ekf->knot_cap);
-        if (s->next_scan == 0 && end > 0 && s->imu_end[0] == 0) return set_err(PTL_ERR_ARG, "IMU deskew: scan 0 has no IMU sample before it");
+        const int rc = lane_dk_ready(l, "ptl_seq_enqueue", 0);
+        if (rc) return rc;
+        if (s->next_scan == 0 && end > 0 && l.imu_end[0] == 0) return set_err(PTL_ERR_ARG, "IMU deskew: scan 0 has no IMU sample before it");
         for (int64_t k = s->next_scan > 0 ? s->next_scan : 1; k < end; ++k)
-            if (s->imu_end[(size_t)k] == s->imu_end[(size_t)k - 1]) return set_err(PTL_ERR_ARG, "IMU deskew: scan %lld has no IMU sample after scan %lld", (long long)k, (long long)k - 1);
+            if (l.imu_end[(size_t)k] == l.imu_end[(size_t)k - 1]) return set_err(PTL_ERR_ARG, "IMU deskew: scan %lld has no IMU sample after scan %lld", (long long)k, (long long)k - 1);
     }
     for (int64_t k = s->next_scan; k < end; ++k) {
         // IMU samples that precede scan k and were not consumed yet (only before the very first scan of a run,
         // or when the previous scan was skipped: otherwise the previous scan's EKF launch already ran them)
-        const int64_t e = with_ekf ? s->imu_end[(size_t)k] : s->imu_pos;
-        if (e > s->imu_pos) {
-            k_ekf_step<<<1, EKF_THREADS, 0, es>>>(s->ekf->st, s->d_imu, (int)s->imu_pos, (int)e, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-            s->imus_per_scan += e - s->imu_pos;
-            s->imu_pos = e;
+        const int64_t e = with_ekf ? l.imu_end[(size_t)k] : l.imu_pos;
+        if (e > l.imu_pos) {
+            k_ekf_step<<<1, EKF_THREADS, 0, es>>>(l.ekf->st, l.d_imu, (int)l.imu_pos, (int)e, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+            s->imus_per_scan += e - l.imu_pos;
+            l.imu_pos = e;
         }
         s->next_scan = k + 1;
         if (with_ekf && !s->imus_per_scan) continue;  // ekf_bench.py:512-518
         s->imus_per_scan = 0;
         const int64_t o = s->n_out;
-        const int64_t e2 = (k + 1 < s->cfg.n_scans) ? s->imu_end[(size_t)k + 1] : s->imu_pos;
+        const int64_t e2 = (k + 1 < s->cfg.n_scans) ? l.imu_end[(size_t)k + 1] : l.imu_pos;
         if (with_ekf && guess_ptr) {
             // the EKF step (update with scan k-1's pose, IMU predicts up to scan k) runs on its own stream beside K0-K4 and
             // the map update; the GN launch of scan k waits for its pose - by then (K0-K4 take longer) it is there
             HIPCHK(hipEventRecord(s->ev_guess, es));
-            s->icp->gn_wait = s->ev_guess;
+            l.icp->gn_wait = s->ev_guess;
         }
-        if (with_ekf) s->icp->gn_done = s->ev_gn;
+        if (with_ekf) l.icp->gn_done = s->ev_gn;
         if (s->dk_on) {  // the prologue (the column table) waits for the predicts through the sweep's samples: no overlap with them
             HIPCHK(hipEventRecord(s->ev_pro, es));
-            s->icp->pro_wait = s->ev_pro;
+            l.icp->pro_wait = s->ev_pro;
         }
         int rc;
         if (s->is_range[(size_t)k]) {
             if (!s->lut) rc = set_err(PTL_ERR_STATE, "scan %lld is a range image but no LUT was set", (long long)k);
-            else rc = icp_enqueue_scan(s->icp, nullptr, nullptr, nullptr, (int64_t)pps, guess_ptr,
-                                       (const unsigned*)(s->d_scans + (size_t)k * pps * 3), s->lut);
+            else rc = icp_enqueue_scan(l.icp, nullptr, nullptr, nullptr, (int64_t)pps, guess_ptr,
+                                       (const unsigned*)(l.d_scans + (size_t)k * pps * 3), s->lut);
         } else {
-            rc = icp_enqueue_scan(s->icp, s->d_scans + (size_t)k * pps * 3, nullptr, nullptr, (int64_t)pps, guess_ptr);
+            rc = icp_enqueue_scan(l.icp, l.d_scans + (size_t)k * pps * 3, nullptr, nullptr, (int64_t)pps, guess_ptr);
         }
-        s->icp->gn_wait = nullptr; s->icp->gn_done = nullptr; s->icp->pro_wait = nullptr;
+        l.icp->gn_wait = nullptr; l.icp->gn_done = nullptr; l.icp->pro_wait = nullptr;
         if (rc) return rc;
-        const double* kiss_pose = s->icp->c.traj + 16 * (s->icp->scans_done - 1);
+        const double* kiss_pose = l.icp->c.traj + 16 * (l.icp->scans_done - 1);
         if (with_ekf) {
             HIPCHK(hipStreamWaitEvent(es, s->ev_gn, 0));  // recorded right after the GN launch
-            k_ekf_step<<<1, EKF_THREADS, 0, es>>>(s->ekf->st, s->d_imu, (int)s->imu_pos, (int)e2, kiss_pose, nullptr,
-                                                 s->d_res_poses + 16 * o, s->d_res_t + o, s->d_rows + 8 * o, 1);
+            k_ekf_step<<<1, EKF_THREADS, 0, es>>>(l.ekf->st, l.d_imu, (int)l.imu_pos, (int)e2, kiss_pose, nullptr,
+                                                 l.d_res_poses + 16 * o, l.d_res_t + o, l.d_rows + 8 * o, 1);
         }
         if (with_ekf) {
-            s->imus_per_scan += e2 - s->imu_pos;
-            s->imu_pos = e2;
+            s->imus_per_scan += e2 - l.imu_pos;
+            l.imu_pos = e2;
         }
         s->scan_of_out.push_back(k);
         s->n_out++;
@@ -1708,13 +1838,9 @@ extern "C" int ptl_seq_enqueue(ptl_seq* s, int64_t n) {
 extern "C" int ptl_seq_wait(ptl_seq* s) {
     if (!s) return set_err(PTL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
-    int rc = icp_check_flags(s->icp);
+    int rc = icp_check_flags(s->lane.icp);
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
-    if (rc == PTL_OK && s->dk_on) {
-        int ovf = 0;
-        rc = ekf_knot_overflow(s->ekf, &ovf);
-        if (rc == PTL_OK && ovf) rc = set_err(PTL_ERR_CAPACITY, "IMU deskew: the filter's knot list overflowed (capacity %lld)", (long long)s->ekf->knot_cap);
-    }
+    if (rc == PTL_OK && s->dk_on) rc = lane_dk_overflow(s->lane, "ptl_seq_wait", 0);
     return rc;
 }
 extern "C" int ptl_seq_run(ptl_seq* s, int64_t n) {
@@ -1736,91 +1862,61 @@ extern "C" int ptl_seq_smoother_enable(ptl_seq* s, int32_t on) {
     if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_smoother_enable: an ICP-only sequence (with_ekf = 0) has no filter to smooth");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return ekf_log_set(s->ekf, on ? s->cfg.n_scans : 0);
+    return ekf_log_set(s->lane.ekf, on ? s->cfg.n_scans : 0);
 }
 extern "C" int ptl_seq_smooth(ptl_seq* s, double* poses16, double* ts, double* nav19, double* cov324, int64_t* n_rows) {
     if (!s || !poses16) return set_err(PTL_ERR_ARG, "null argument");
     if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_smooth: an ICP-only sequence has no filter to smooth");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return ekf_smooth_impl(s->ekf, "ptl_seq_smooth", poses16, ts, nav19, cov324, s->cfg.n_scans, n_rows);
+    return ekf_smooth_impl(s->lane.ekf, "ptl_seq_smooth", poses16, ts, nav19, cov324, s->cfg.n_scans, n_rows);
 }
 extern "C" int ptl_seq_smoother_log(ptl_seq* s, double* entries, int64_t max_entries, int64_t* n_entries, int32_t* overflow) {
     if (!s || max_entries < 0) return set_err(PTL_ERR_ARG, "bad argument");
-    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only sequence has no filter log");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return ekf_log_read(s->ekf, entries, max_entries, n_entries, overflow);
+    return lane_smoother_log(s->lane, s->cfg, "ptl_seq_smoother_log", entries, max_entries, n_entries, overflow);
 }
 // IMU deskew for the sequence's scans
 extern "C" int ptl_seq_imu_deskew_enable(ptl_seq* s, int32_t on, int64_t knot_capacity) {
     if (!s) return set_err(PTL_ERR_ARG, "null argument");
-    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_seq_imu_deskew_enable: an ICP-only sequence (with_ekf = 0) has no filter to deskew with");
-    if (on && !s->cfg.icp.deskew) return set_err(PTL_ERR_STATE, "ptl_seq_imu_deskew_enable: deskew is off in the configuration");
-    if (on && knot_capacity < 2) return set_err(PTL_ERR_ARG, "ptl_seq_imu_deskew_enable: knot_capacity must be >= 2");
-    if (on && dk_knots_needed(s->imu_end) > knot_capacity)
-        return set_err(PTL_ERR_ARG, "ptl_seq_imu_deskew_enable: the IMU samples between two scans need %lld knots, knot_capacity is %lld", (long long)dk_knots_needed(s->imu_end), (long long)knot_capacity);
+    int rc = dk_enable_check(s->cfg, &s->lane, 1, on, knot_capacity, "ptl_seq_imu_deskew_enable");
+    if (rc) return rc;
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipStreamSynchronize(s->icp->map_stream));
+    HIPCHK(hipStreamSynchronize(s->lane.icp->map_stream));
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
-    int rc = dk_wire(s->icp, nullptr, nullptr, nullptr, 0);
-    if (rc == PTL_OK) rc = ekf_knots_set(s->ekf, 0);
+    s->dk_on = false;
+    if (on && !s->ev_pro) HIPCHK(hipEventCreateWithFlags(&s->ev_pro, hipEventDisableTiming));
+    rc = lane_dk_set(s->lane, s->cfg.n_scans, on ? knot_capacity : 0);
     HIPCHK(hipStreamSynchronize(s->stream));
-    s->dk_on = false; s->dk_times = false;
-    if (rc || !on) return rc;
-    const size_t n = (size_t)s->cfg.n_scans;
-    if (!s->d_dk_t0t1 && (dalloc(&s->d_dk_t0t1, 2 * n) != hipSuccess || dalloc(&s->d_dk_modes, n) != hipSuccess))
-        return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
-    if (!s->ev_pro) HIPCHK(hipEventCreateWithFlags(&s->ev_pro, hipEventDisableTiming));
-    HIPCHK(hipMemset(s->d_dk_modes, 0, n * sizeof(int)));
-    rc = ekf_knots_set(s->ekf, knot_capacity);
-    if (rc == PTL_OK) rc = dk_wire(s->icp, s->ekf, s->d_dk_t0t1, s->d_dk_modes, (int64_t)n);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (rc == PTL_OK) s->dk_on = true;
+    s->dk_on = on && rc == PTL_OK;
     return rc;
 }
 extern "C" int ptl_seq_upload_sweep_times(ptl_seq* s, const double* t0t1) {
     if (!s || !t0t1) return set_err(PTL_ERR_ARG, "null argument");
     if (!s->dk_on) return set_err(PTL_ERR_STATE, "ptl_seq_upload_sweep_times: IMU deskew is not enabled");
-    for (int64_t k = 0; k < s->cfg.n_scans; ++k)
-        if (!(t0t1[2 * k + 1] >= t0t1[2 * k])) return set_err(PTL_ERR_ARG, "ptl_seq_upload_sweep_times: scan %lld has t1 < t0", (long long)k);
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipMemcpy(s->d_dk_t0t1, t0t1, (size_t)s->cfg.n_scans * 16, hipMemcpyHostToDevice));
-    s->dk_times = true;
-    return PTL_OK;
+    return lane_upload_sweep_times(s->lane, s->cfg.n_scans, t0t1, "ptl_seq_upload_sweep_times");
 }
 extern "C" int ptl_seq_deskew_modes(ptl_seq* s, int32_t* modes, int64_t max_n, int64_t* n) {
     if (!s || !modes || max_n < 0) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
-    const int64_t m = s->n_out < max_n ? s->n_out : max_n;
-    if (!s->dk_on) {
-        for (int64_t k = 0; k < m; ++k) modes[k] = (s->cfg.icp.deskew && k >= 2) ? DK_MODE_CV : DK_MODE_NONE;
-    } else {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (m > 0) HIPCHK(hipMemcpy(modes, s->d_dk_modes, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    if (n) *n = m;
-    return PTL_OK;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return lane_deskew_modes(s->lane, s->cfg, s->dk_on, s->n_out, modes, max_n, n);
 }
 extern "C" int ptl_seq_knots(ptl_seq* s, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
     if (!s || max_knots < 0) return set_err(PTL_ERR_ARG, "bad argument");
-    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only sequence has no filter");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return ekf_knots_read(s->ekf, knots, max_knots, n_knots, overflow);
+    return lane_knots(s->lane, s->cfg, "ptl_seq_knots", knots, max_knots, n_knots, overflow);
 }
 extern "C" int ptl_seq_copy_traj(ptl_seq* s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!s || !dst_device) return set_err(PTL_ERR_ARG, "null argument");
-    if (!s->cfg.with_ekf) return set_err(PTL_ERR_STATE, "trajectory rows need with_ekf");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
-    const int64_t n = s->n_out < max_rows ? s->n_out : max_rows;
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
-    if (n > 0) HIPCHK(hipMemcpyAsync(dst_device, s->d_rows, (size_t)n * 64, hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (rows) *rows = n;
-    return PTL_OK;
+    return lane_copy_traj(s->lane, s->cfg, s->n_out, s->stream, dst_device, max_rows, rows);
 }
 extern "C" int ptl_device_sync(int device_id) {
     HIPCHK(hipSetDevice(device_id));
@@ -1831,36 +1927,24 @@ extern "C" int ptl_seq_results(ptl_seq* s, double* res_poses, double* res_t, dou
                                int64_t max_n, int64_t* n_out) {
     if (!s) return set_err(PTL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(s->cfg.icp.device_id));
-    const int64_t n = s->n_out < max_n ? s->n_out : max_n;
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
-    if (n > 0) {
-        if (res_poses && s->cfg.with_ekf) HIPCHK(hipMemcpy(res_poses, s->d_res_poses, (size_t)n * 128, hipMemcpyDeviceToHost));
-        if (res_t && s->cfg.with_ekf) HIPCHK(hipMemcpy(res_t, s->d_res_t, (size_t)n * 8, hipMemcpyDeviceToHost));
-        if (kiss_poses) HIPCHK(hipMemcpy(kiss_poses, s->icp->c.traj, (size_t)n * 128, hipMemcpyDeviceToHost));
-        if (stats) {
-            std::vector<ScanStats> tmp((size_t)n);
-            HIPCHK(hipMemcpy(tmp.data(), s->icp->c.sstats, (size_t)n * sizeof(ScanStats), hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < n; ++i) stats_out(tmp[(size_t)i], &stats[i]);
-        }
-    }
-    if (n_out) *n_out = n;
-    return PTL_OK;
+    return lane_results(s->lane, s->cfg.with_ekf != 0, s->n_out, res_poses, res_t, kiss_poses, stats, max_n, n_out);
 }
 extern "C" int ptl_seq_traj_device(ptl_seq* s, void** dev_ptr, int64_t* rows) {
     if (!s || !dev_ptr || !rows) return set_err(PTL_ERR_ARG, "null argument");
-    *dev_ptr = s->d_rows;
+    *dev_ptr = s->lane.d_rows;
     *rows = s->n_out;
     return PTL_OK;
 }
 extern "C" int ptl_seq_icp(ptl_seq* s, ptl_icp** icp) {
     if (!s || !icp) return set_err(PTL_ERR_ARG, "null argument");
-    *icp = s->icp;
+    *icp = s->lane.icp;
     return PTL_OK;
 }
 extern "C" int ptl_seq_profile(ptl_seq* s, int enable, double* gn_ms_total, int64_t* gn_launches, int reset) {
     if (!s) return set_err(PTL_ERR_ARG, "null argument");
-    return ptl_icp_profile(s->icp, enable, gn_ms_total, gn_launches, reset);
+    return ptl_icp_profile(s->lane.icp, enable, gn_ms_total, gn_launches, reset);
 }
 
 // ================================================================================================ batched runner
@@ -1871,63 +1955,53 @@ extern "C" int ptl_seq_profile(ptl_seq* s, int enable, double* gn_ms_total, int6
 //     persistent launch, and a step lasts as long as its slowest sequence.
 struct ptl_batch {
     ptl_seq_cfg cfg;
-    int S;
-    hipStream_t stream;
+    int S = 0;
+    hipStream_t stream = nullptr;
     // the map update and the filter step of scan k run on `side` beside K0-K4 of scan k + 1 (both need only the GN result);
     // the GN launch of scan k + 1 waits for them
-    hipStream_t side;
-    hipEvent_t ev_gn, ev_side;
-    bool ev_side_valid;
-    ptl_icp* icp[GN_MAX_SEQ];
-    ptl_ekf* ekf[GN_MAX_SEQ];
-    float* d_scans[GN_MAX_SEQ];
-    double* d_imu[GN_MAX_SEQ];
-    int* d_imu_end[GN_MAX_SEQ];
-    unsigned* d_bar;            // [SEQ_MAX_TEAMS][64] barrier counters and job words of the free-running kernel's teams
-    SeqSched* d_sched;          // [8] its per-XCD scan schedulers
-    int *d_flags, *h_flags;     // [GN_MAX_SEQ + 1] error flags of every sequence + the status word, gathered by k_finish_all (h_flags: pinned)
-    unsigned* d_status;         // one sticky word: why teams of the free-running kernel left a launch early (SEQ_EXIT_*), cleared by a reset
-    int force_agent;            // PTL_TEAM_SYNC=agent in the environment when the batch was created: no XCD-local barrier shortcut
-    int balance_margin;         // PTL_SCHED_MARGIN (default 1; -1 = a team looks abroad only when its own XCD has nothing for it): seq_kernel.h SeqRun
-    int dbg_dead_block, dbg_dead_round;  // test hook: ptl_batch_debug_stall_block
-    int um_alt;                 // test hook: ptl_batch_debug_set_map_points_per_thread
-    bool free_running;
-    int team_wgs;               // workgroups per team of the free-running kernel (0 = by the number of sequences, batch_gseq)
-    bool seq_run_checked;
-    int64_t scans_per_launch;
-    std::vector<int64_t> imu_end[GN_MAX_SEQ];
-    double *d_res_poses[GN_MAX_SEQ], *d_res_t[GN_MAX_SEQ], *d_rows[GN_MAX_SEQ];
-    unsigned char is_range;
-    ptl_lut* lut;
-    SeqCtx* d_ctx;
-    int64_t next_scan, n_out;
+    hipStream_t side = nullptr;
+    hipEvent_t ev_gn = nullptr, ev_side = nullptr;
+    bool ev_side_valid = false;
+    SeqLane lane[GN_MAX_SEQ];    // sweep slots: [ring][pps][3] f32, or [ring][pps] u32 with range_input
+    unsigned* d_bar = nullptr;   // [SEQ_MAX_TEAMS][64] barrier counters and job words of the free-running kernel's teams
+    SeqSched* d_sched = nullptr; // [8] its per-XCD scan schedulers
+    int *d_flags = nullptr, *h_flags = nullptr;  // [GN_MAX_SEQ + 1] error flags of every sequence + the status word, gathered by k_finish_all (h_flags: pinned)
+    unsigned* d_status = nullptr;  // one sticky word: why teams of the free-running kernel left a launch early (SEQ_EXIT_*), cleared by a reset
+    int force_agent = 0;         // PTL_TEAM_SYNC=agent in the environment when the batch was created: no XCD-local barrier shortcut
+    int balance_margin = 1;      // PTL_SCHED_MARGIN (default 1; -1 = a team looks abroad only when its own XCD has nothing for it): seq_kernel.h SeqRun
+    int dbg_dead_block = -1, dbg_dead_round = -1;  // test hook: ptl_batch_debug_stall_block
+    int um_alt = 0;              // test hook: ptl_batch_debug_set_map_points_per_thread
+    bool free_running = false;
+    int team_wgs = 0;            // workgroups per team of the free-running kernel (0 = by the number of sequences, batch_gseq)
+    bool seq_run_checked = false;
+    int64_t scans_per_launch = 256;
+    unsigned char is_range = 0;
+    ptl_lut* lut = nullptr;
+    SeqCtx* d_ctx = nullptr;
+    int64_t next_scan = 0, n_out = 0;
     // Sweep ring (ptl_seq_cfg.resident_scans, round 6): the batch keeps `ring` sweep slots per sequence (ring == n_scans: every sweep resident, as
     // before); scan k lives in slot k % ring.  ring_lap = the lap d_ctx's scan_base is set for (a launch never crosses a lap: enqueue splits there).
     // up_hi[s] = sweeps of sequence s uploaded so far (in order); done_scans = scans whose launches are known complete (ptl_batch_wait).  Both are
     // atomics: uploads may run on another host thread while ptl_batch_wait blocks.
-    int64_t ring, ring_lap;
-    std::atomic<int64_t> up_hi[GN_MAX_SEQ];
-    std::atomic<int64_t> done_scans;
-    int64_t imu_pos[GN_MAX_SEQ];
-    bool ctx_dirty;
-    bool prof;
+    int64_t ring = 0, ring_lap = 0;
+    std::atomic<int64_t> up_hi[GN_MAX_SEQ] = {};
+    std::atomic<int64_t> done_scans{0};
+    bool ctx_dirty = true;
+    bool prof = false;
     std::vector<hipEvent_t> ev;
-    size_t ev_used;
-    double gn_ms;
-    int64_t gn_launches;
+    size_t ev_used = 0;
+    double gn_ms = 0;
+    int64_t gn_launches = 0;
     // fixed-interval smoother (ptl_batch_smoother_enable): one k_ekf_smooth job per sequence, their status words side by side
-    EkfSmoothJob* d_sm_jobs;
-    long long* d_sm_info;
+    EkfSmoothJob* d_sm_jobs = nullptr;
+    long long* d_sm_info = nullptr;
     std::vector<long long> h_sm_info;
-    bool sm_done;  // the last ptl_batch_smooth succeeded and nothing ran since
-    // IMU deskew (ptl_batch_imu_deskew_enable): sweep times and modes per sequence (all n_scans, also with the sweep ring); the lockstep
-    // driver's prologue waits for `ev_filter`, recorded behind the filter step
-    bool dk_on;
-    bool dk_times[GN_MAX_SEQ];
-    double* d_dk_t0t1[GN_MAX_SEQ];
-    int* d_dk_modes[GN_MAX_SEQ];
-    hipEvent_t ev_filter;
-    bool ev_filter_valid;
+    bool sm_done = false;  // the last ptl_batch_smooth succeeded and nothing ran since
+    // IMU deskew (ptl_batch_imu_deskew_enable): on for every sequence (their sweep times and modes: the lanes); the lockstep driver's prologue
+    // waits for `ev_filter`, recorded behind the filter step
+    bool dk_on = false;
+    hipEvent_t ev_filter = nullptr;
+    bool ev_filter_valid = false;
 };
 
 // launch geometry: workgroups per team.  Lockstep (kx_assign): one team per sequence, 1 / 2 / 4 per XCD.  Free-running: 1 / 2 / 4
@@ -1977,25 +2051,13 @@ static int batch_check_seq_run(ptl_batch* b) {
 extern "C" int ptl_batch_destroy(ptl_batch* b) {
     if (!b) return PTL_OK;
     (void)hipSetDevice(b->cfg.icp.device_id);
-    for (int s = 0; s < b->S; ++s) {
-        if (b->icp[s]) icp_free(b->icp[s]);
-        if (b->ekf[s]) ptl_ekf_destroy(b->ekf[s]);
-        void* ptrs[] = {b->d_scans[s], b->d_imu[s], b->d_res_poses[s], b->d_res_t[s], b->d_rows[s], b->d_imu_end[s], b->d_dk_t0t1[s], b->d_dk_modes[s]};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-    if (b->d_ctx) (void)hipFree(b->d_ctx);
-    if (b->d_bar) (void)hipFree(b->d_bar);
-    if (b->d_sched) (void)hipFree(b->d_sched);
-    if (b->d_status) (void)hipFree(b->d_status);
-    if (b->d_flags) (void)hipFree(b->d_flags);
+    for (int s = 0; s < b->S; ++s) lane_free(b->lane[s]);
+    for (void* p : {(void*)b->d_ctx, (void*)b->d_bar, (void*)b->d_sched, (void*)b->d_status, (void*)b->d_flags, (void*)b->d_sm_jobs, (void*)b->d_sm_info})
+        if (p) (void)hipFree(p);
     if (b->h_flags) (void)hipHostFree(b->h_flags);
-    if (b->d_sm_jobs) (void)hipFree(b->d_sm_jobs);
-    if (b->d_sm_info) (void)hipFree(b->d_sm_info);
     for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
-    if (b->ev_gn) (void)hipEventDestroy(b->ev_gn);
-    if (b->ev_side) (void)hipEventDestroy(b->ev_side);
-    if (b->ev_filter) (void)hipEventDestroy(b->ev_filter);
+    for (hipEvent_t e : {b->ev_gn, b->ev_side, b->ev_filter})
+        if (e) (void)hipEventDestroy(e);
     if (b->side) (void)hipStreamDestroy(b->side);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -2003,34 +2065,31 @@ extern "C" int ptl_batch_destroy(ptl_batch* b) {
 }
 extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl_batch** out) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
-    ABI_CHECK(ptl_seq_cfg, cfg);
-    ABI_CHECK(ptl_icp_cfg, &cfg->icp);
-    ABI_CHECK(ptl_ekf_cfg, &cfg->ekf);
     if (n_sequences < 1 || n_sequences > GN_MAX_SEQ) return set_err(PTL_ERR_ARG, "n_sequences must be in [1, %d]", GN_MAX_SEQ);
-    if (cfg->n_scans < 1 || cfg->points_per_scan < 1) return set_err(PTL_ERR_ARG, "empty sequence");
-    if ((cfg->icp.gn_workgroups & 31) || cfg->icp.gn_workgroups > 512) return set_err(PTL_ERR_ARG, "batched runs need gn_workgroups = a multiple of 32 (8 XCDs x up to 4 sequences each), at most 512");
-    if (ptl_device_count() <= cfg->icp.device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", cfg->icp.device_id);
-    HIPCHK(hipSetDevice(cfg->icp.device_id));
+    ptl_seq_cfg c;
+    int rc = seq_cfg_settle(cfg, &c);
+    if (rc) return rc;
+    if ((c.icp.gn_workgroups & 31) || c.icp.gn_workgroups > 512) return set_err(PTL_ERR_ARG, "batched runs need gn_workgroups = a multiple of 32 (8 XCDs x up to 4 sequences each), at most 512");
+    if (c.resident_scans < 0 || c.resident_scans == 1) return set_err(PTL_ERR_ARG, "resident_scans must be 0 (every sweep resident) or >= 2 sweep slots per sequence");
+    const int64_t ring = (c.resident_scans > 0 && c.resident_scans < c.n_scans) ? c.resident_scans : c.n_scans;
+    const size_t slot = (size_t)c.points_per_scan * (c.range_input ? 4 : 12);  // resident bytes of a sweep
     {   // the whole batch has to fit the device: say so here, with numbers, instead of failing part-way through the allocations
-        ptl_icp_cfg ic0 = cfg->icp;
-        if (ic0.max_points_per_scan < cfg->points_per_scan) ic0.max_points_per_scan = cfg->points_per_scan;
-        const size_t slot0 = cfg->range_input ? 4 : 12;  // resident bytes per pixel of a sweep
-        if (cfg->resident_scans < 0 || cfg->resident_scans == 1) return set_err(PTL_ERR_ARG, "resident_scans must be 0 (every sweep resident) or >= 2 sweep slots per sequence");
-        const size_t res0 = (cfg->resident_scans > 0 && cfg->resident_scans < cfg->n_scans) ? (size_t)cfg->resident_scans : (size_t)cfg->n_scans;
-        const size_t per_seq = icp_footprint_bytes(&ic0) + res0 * (size_t)cfg->points_per_scan * slot0 +
-                               (size_t)(cfg->n_imu > 0 ? cfg->n_imu : 1) * 56 + (size_t)cfg->n_scans * (128 + 8 + 64 + 4) + (64u << 10);
+        const size_t per_seq = icp_footprint_bytes(&c.icp) + (size_t)ring * slot + (size_t)(c.n_imu > 0 ? c.n_imu : 1) * 56 + (size_t)c.n_scans * (128 + 8 + 64 + 4) + (64u << 10);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * (size_t)n_sequences > free_b)
             return set_err(PTL_ERR_CAPACITY, "batch of %d sequences needs %.1f GB of device memory (%.0f MB per sequence: %.0f MB of work buffers, map table "
                            "and block pool, %.0f MB of sweeps), %.1f GB are free of %.1f GB: fewer sequences, fewer resident sweeps or a smaller map_block_capacity",
-                           n_sequences, per_seq * (double)n_sequences / 1e9, per_seq / 1e6, icp_footprint_bytes(&ic0) / 1e6,
-                           (double)res0 * cfg->points_per_scan * slot0 / 1e6, free_b / 1e9, total_b / 1e9);
+                           n_sequences, per_seq * (double)n_sequences / 1e9, per_seq / 1e6, icp_footprint_bytes(&c.icp) / 1e6,
+                           (double)ring * slot / 1e6, free_b / 1e9, total_b / 1e9);
     }
+    const bool free_running = c.icp.gn_lanes_per_point == 8;
+    if (!free_running && c.icp.map_small_blocks > 0) return set_err(PTL_ERR_ARG, "map_small_blocks (two block classes) needs the free-running driver (gn_lanes_per_point = 8)");
+    if (ring < c.n_scans && !free_running) return set_err(PTL_ERR_ARG, "resident_scans (the sweep ring) is served by the free-running driver (gn_lanes_per_point = 8)");
     ptl_batch* b = new ptl_batch();
-    b->cfg = *cfg;
+    b->cfg = c;
     b->S = n_sequences;
-    b->stream = nullptr; b->d_ctx = nullptr; b->lut = nullptr; b->is_range = 0; b->d_bar = nullptr; b->d_sched = nullptr; b->d_status = nullptr; b->d_flags = nullptr; b->h_flags = nullptr;
-    b->dbg_dead_block = -1; b->dbg_dead_round = -1; b->um_alt = 0;
+    b->free_running = free_running;
+    b->ring = ring;
     {   // PTL_TEAM_SYNC=agent: the teams of the free-running kernel keep the agent-scope release at every barrier (seq_kernel.h team_sync)
         const char* e = getenv("PTL_TEAM_SYNC");
         b->force_agent = (e && strcmp(e, "agent") == 0) ? 1 : 0;
@@ -2038,45 +2097,12 @@ extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl
         b->balance_margin = (m && *m) ? atoi(m) : 1;
         if (b->balance_margin < -1 || b->balance_margin > 4096) b->balance_margin = 1;
     }
-    b->free_running = cfg->icp.gn_lanes_per_point == 8;
-    if (!b->free_running && cfg->icp.map_small_blocks > 0) { ptl_batch_destroy(b); return set_err(PTL_ERR_ARG, "map_small_blocks (two block classes) needs the free-running driver (gn_lanes_per_point = 8)"); }
-    b->team_wgs = 0; b->seq_run_checked = false;
-    b->scans_per_launch = 256;
-    b->next_scan = 0; b->n_out = 0; b->ctx_dirty = true; b->prof = false; b->ev_used = 0; b->gn_ms = 0; b->gn_launches = 0;
-    b->ring = (cfg->resident_scans > 0 && cfg->resident_scans < cfg->n_scans) ? cfg->resident_scans : cfg->n_scans;
-    b->ring_lap = 0; b->done_scans = 0;
-    for (int s = 0; s < GN_MAX_SEQ; ++s) b->up_hi[s] = 0;
-    if (b->ring < cfg->n_scans && !b->free_running) { delete b; return set_err(PTL_ERR_ARG, "resident_scans (the sweep ring) is served by the free-running driver (gn_lanes_per_point = 8)"); }
-    for (int s = 0; s < GN_MAX_SEQ; ++s) {
-        b->icp[s] = nullptr; b->ekf[s] = nullptr; b->d_scans[s] = nullptr; b->d_imu[s] = nullptr; b->d_imu_end[s] = nullptr;
-        b->d_res_poses[s] = nullptr; b->d_res_t[s] = nullptr; b->d_rows[s] = nullptr; b->imu_pos[s] = 0;
-        b->dk_times[s] = false; b->d_dk_t0t1[s] = nullptr; b->d_dk_modes[s] = nullptr;
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&b->ev_gn, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b->ev_side, hipEventDisableTiming) != hipSuccess) {
+        ptl_batch_destroy(b);
+        return set_err(PTL_ERR_HIP, "stream / event creation failed");
     }
-    b->dk_on = false; b->ev_filter = nullptr; b->ev_filter_valid = false;
-    int rc = PTL_OK;
-    b->side = nullptr; b->ev_gn = nullptr; b->ev_side = nullptr; b->ev_side_valid = false;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { delete b; return set_err(PTL_ERR_HIP, "stream"); }
-    if (hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&b->ev_gn, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->ev_side, hipEventDisableTiming) != hipSuccess) { ptl_batch_destroy(b); return set_err(PTL_ERR_HIP, "stream / event creation failed"); }
-    ptl_icp_cfg ic = cfg->icp;
-    if (ic.max_points_per_scan < cfg->points_per_scan) ic.max_points_per_scan = cfg->points_per_scan;
-    b->cfg.icp = ic;
-    ptl_ekf_cfg ec = cfg->ekf;
-    ec.device_id = ic.device_id;
-    const size_t nim = cfg->n_imu > 0 ? (size_t)cfg->n_imu : 1;
-    for (int s = 0; s < b->S && rc == PTL_OK; ++s) {
-        rc = icp_create_impl(&ic, b->stream, &b->icp[s], true);
-        if (rc == PTL_OK) rc = ekf_create_impl(&ec, b->stream, &b->ekf[s]);
-        while (rc == PTL_OK && b->icp[s]->traj_cap < cfg->n_scans) rc = icp_grow_traj(b->icp[s]);
-        if (rc == PTL_OK &&
-            (hipMalloc((void**)&b->d_scans[s], (size_t)b->ring * cfg->points_per_scan * (cfg->range_input ? 4 : 12)) != hipSuccess ||
-             dalloc(&b->d_imu[s], nim * 7) != hipSuccess || dalloc(&b->d_res_poses[s], (size_t)cfg->n_scans * 16) != hipSuccess ||
-             dalloc(&b->d_res_t[s], (size_t)cfg->n_scans) != hipSuccess || dalloc(&b->d_rows[s], (size_t)cfg->n_scans * 8) != hipSuccess ||
-             dalloc(&b->d_imu_end[s], (size_t)cfg->n_scans) != hipSuccess))
-            rc = set_err(PTL_ERR_HIP, "batch allocation failed");
-        if (rc == PTL_OK && hipMemset(b->d_imu_end[s], 0, (size_t)cfg->n_scans * sizeof(int)) != hipSuccess) rc = set_err(PTL_ERR_HIP, "memset failed");
-        b->imu_end[s].assign((size_t)cfg->n_scans, 0);
-    }
+    for (int s = 0; s < b->S && rc == PTL_OK; ++s) rc = lane_create(b->lane[s], c, b->stream, b->stream, slot, (size_t)ring, true, "ptl_batch_create");
     if (rc == PTL_OK && (dalloc(&b->d_ctx, (size_t)GN_MAX_SEQ) != hipSuccess || dalloc(&b->d_bar, (size_t)SEQ_MAX_TEAMS * 64) != hipSuccess || dalloc(&b->d_sched, (size_t)8) != hipSuccess ||
                          dalloc(&b->d_status, (size_t)16) != hipSuccess || hipMemset(b->d_status, 0, 16 * sizeof(unsigned)) != hipSuccess ||
                          dalloc(&b->d_flags, (size_t)GN_MAX_SEQ + 1) != hipSuccess || hipHostMalloc((void**)&b->h_flags, (size_t)(GN_MAX_SEQ + 1) * sizeof(int)) != hipSuccess))
@@ -2106,7 +2132,7 @@ extern "C" int ptl_batch_upload_scan(ptl_batch* b, int32_t s, int64_t k, const f
     int rc = batch_ring_slot_free(b, s, k);
     if (rc) return rc;
     const size_t bytes = (size_t)b->cfg.points_per_scan * 12;
-    HIPCHK(hipMemcpy((char*)b->d_scans[s] + (size_t)(k % b->ring) * bytes, xyz, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char*)b->lane[s].d_scans + (size_t)(k % b->ring) * bytes, xyz, bytes, hipMemcpyHostToDevice));
     if (b->ring < b->cfg.n_scans) b->up_hi[s] = k + 1;
     return PTL_OK;
 }
@@ -2117,7 +2143,7 @@ extern "C" int ptl_batch_upload_range(ptl_batch* b, int32_t s, int64_t k, const 
     int rc = batch_ring_slot_free(b, s, k);
     if (rc) return rc;
     const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
-    HIPCHK(hipMemcpy((char*)b->d_scans[s] + (size_t)(k % b->ring) * slot, range_mm, (size_t)b->cfg.points_per_scan * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char*)b->lane[s].d_scans + (size_t)(k % b->ring) * slot, range_mm, (size_t)b->cfg.points_per_scan * 4, hipMemcpyHostToDevice));
     if (b->ring < b->cfg.n_scans) b->up_hi[s] = k + 1;
     return PTL_OK;
 }
@@ -2127,23 +2153,13 @@ extern "C" int ptl_batch_set_lut(ptl_batch* b, ptl_lut* lut, int32_t active_beam
     b->lut = lut;
     b->is_range = 1;
     b->ctx_dirty = true;
-    for (int s = 0; s < b->S; ++s) { int rc = ptl_icp_set_active_beams(b->icp[s], lut->H, active_beams); if (rc) return rc; }
+    for (int s = 0; s < b->S; ++s) { int rc = ptl_icp_set_active_beams(b->lane[s].icp, lut->H, active_beams); if (rc) return rc; }
     return PTL_OK;
 }
 extern "C" int ptl_batch_upload_imu(ptl_batch* b, int32_t s, const double* imu, const int64_t* imu_end) {
     if (!b || !imu_end || s < 0 || s >= b->S || (!imu && b->cfg.n_imu > 0)) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
-    if (b->cfg.n_imu > 0) HIPCHK(hipMemcpy(b->d_imu[s], imu, (size_t)b->cfg.n_imu * 56, hipMemcpyHostToDevice));
-    for (int64_t k = 0; k < b->cfg.n_scans; ++k) {
-        if (imu_end[k] < 0 || imu_end[k] > b->cfg.n_imu || (k && imu_end[k] < imu_end[k - 1])) return set_err(PTL_ERR_ARG, "imu_end must be non-decreasing within [0, n_imu]");
-        // lockstep batching cannot skip a scan of one sequence only (ekf_bench.py:512-518): demand >= 1 IMU per scan
-        if (b->cfg.with_ekf && k && imu_end[k] == imu_end[k - 1]) return set_err(PTL_ERR_ARG, "batched runs need at least one IMU sample between consecutive scans (scan %lld)", (long long)k);
-        b->imu_end[s][(size_t)k] = imu_end[k];
-    }
-    std::vector<int> e32((size_t)b->cfg.n_scans);
-    for (int64_t k = 0; k < b->cfg.n_scans; ++k) e32[(size_t)k] = (int)imu_end[k];
-    HIPCHK(hipMemcpy(b->d_imu_end[s], e32.data(), e32.size() * sizeof(int), hipMemcpyHostToDevice));
-    return PTL_OK;
+    return lane_upload_imu(b->lane[s], b->cfg, imu, imu_end, b->cfg.with_ekf != 0);
 }
 static int batch_push_ctx(ptl_batch* b) {
     std::vector<SeqCtx> hv((size_t)GN_MAX_SEQ);
@@ -2151,21 +2167,21 @@ static int batch_push_ctx(ptl_batch* b) {
     memset(h, 0, sizeof(SeqCtx) * GN_MAX_SEQ);
     const bool with_ekf = b->cfg.with_ekf != 0;
     for (int s = 0; s < b->S; ++s) {
-        Ctx c = b->icp[s]->c;
+        Ctx c = b->lane[s].icp->c;
         c.in_f32 = nullptr; c.in_f64 = nullptr; c.in_range = nullptr; c.t01 = nullptr;
         c.n_in = (int)b->cfg.points_per_scan;
         c.overlap_pre = 1;  // the prologue of scan k + 1 runs beside the map update of scan k (side stream)
-        c.ext_guess = (with_ekf && b->cfg.use_imu_prediction) ? (const double*)((char*)b->ekf[s]->st + offsetof(EkfState, pose)) : nullptr;
-        if (b->is_range) { c.lut_dir = b->lut->dir; c.lut_off = b->lut->off; c.row_mask = b->icp[s]->d_row_mask; }
+        c.ext_guess = (with_ekf && b->cfg.use_imu_prediction) ? (const double*)((char*)b->lane[s].ekf->st + offsetof(EkfState, pose)) : nullptr;
+        if (b->is_range) { c.lut_dir = b->lut->dir; c.lut_off = b->lut->off; c.row_mask = b->lane[s].icp->d_row_mask; }
         h[s].c = c;
         h[s].scan_stride_floats = (long long)b->cfg.points_per_scan * (b->cfg.range_input ? 1 : 3);
         // (sweep ring: scan k of lap L = k / ring sits in slot k - L ring; the kernel addresses scan_base + k stride, so the base moves back a ring per lap)
-        h[s].scan_base = b->d_scans[s] - (long long)b->ring_lap * (long long)b->ring * h[s].scan_stride_floats;
+        h[s].scan_base = b->lane[s].d_scans - (long long)b->ring_lap * (long long)b->ring * h[s].scan_stride_floats;
         h[s].input_is_range = b->is_range;
         h[s].n_scans = (int)b->cfg.n_scans;
-        h[s].fd_buf[0] = b->icp[s]->fd_buf[0]; h[s].fd_buf[1] = b->icp[s]->fd_buf[1];
-        h[s].ekf = b->ekf[s]->st; h[s].imu = b->d_imu[s]; h[s].imu_end = b->d_imu_end[s];
-        h[s].res_poses = b->d_res_poses[s]; h[s].res_t = b->d_res_t[s]; h[s].rows = b->d_rows[s];
+        h[s].fd_buf[0] = b->lane[s].icp->fd_buf[0]; h[s].fd_buf[1] = b->lane[s].icp->fd_buf[1];
+        h[s].ekf = b->lane[s].ekf->st; h[s].imu = b->lane[s].d_imu; h[s].imu_end = b->lane[s].d_imu_end;
+        h[s].res_poses = b->lane[s].d_res_poses; h[s].res_t = b->lane[s].d_res_t; h[s].rows = b->lane[s].d_rows;
     }
     HIPCHK(hipMemcpyAsync(b->d_ctx, h, sizeof(SeqCtx) * GN_MAX_SEQ, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -2174,11 +2190,11 @@ static int batch_push_ctx(ptl_batch* b) {
 }
 static int batch_reset(ptl_batch* b) {
     for (int s = 0; s < b->S; ++s) {
-        int rc = icp_reset_device(b->icp[s]);
+        int rc = icp_reset_device(b->lane[s].icp);
         if (rc) return rc;
-        rc = ekf_reset(b->ekf[s]);
+        rc = ekf_reset(b->lane[s].ekf);
         if (rc) return rc;
-        b->imu_pos[s] = 0;
+        b->lane[s].imu_pos = 0;
     }
     b->next_scan = 0;
     b->n_out = 0;
@@ -2196,11 +2212,9 @@ static int batch_reset(ptl_batch* b) {
 }
 // IMU deskew: sweep times of every sequence, knots enough for the IMU samples between two scans
 static int batch_dk_check(ptl_batch* b) {
-    if (!b->dk_on) return PTL_OK;
-    for (int s = 0; s < b->S; ++s) {
-        if (!b->dk_times[s]) return set_err(PTL_ERR_STATE, "IMU deskew: sequence %d has no sweep times (ptl_batch_upload_sweep_times)", s);
-        const int64_t need = dk_knots_needed(b->imu_end[s]);
-        if (need > b->ekf[s]->knot_cap) return set_err(PTL_ERR_ARG, "IMU deskew: sequence %d: the IMU samples between two scans need %lld knots, capacity %lld", s, (long long)need, (long long)b->ekf[s]->knot_cap);
+    for (int s = 0; b->dk_on && s < b->S; ++s) {
+        const int rc = lane_dk_ready(b->lane[s], "ptl_batch_enqueue", s);
+        if (rc) return rc;
     }
     return PTL_OK;
 }
@@ -2239,10 +2253,10 @@ static int batch_enqueue_free(ptl_batch* b, int64_t n) {
                 const int ns = S - s0 < EKF_MAX_SEQ ? S - s0 : EKF_MAX_SEQ;
                 for (int q = 0; q < ns; ++q) {
                     const int s = s0 + q;
-                    ea.e[q] = b->ekf[s]->st; ea.imu[q] = b->d_imu[s];
-                    ea.i0[q] = (int)b->imu_pos[s]; ea.i1[q] = (int)b->imu_end[s][(size_t)k0];
+                    ea.e[q] = b->lane[s].ekf->st; ea.imu[q] = b->lane[s].d_imu;
+                    ea.i0[q] = (int)b->lane[s].imu_pos; ea.i1[q] = (int)b->lane[s].imu_end[(size_t)k0];
                     any = any || ea.i1[q] > ea.i0[q];
-                    if (b->imu_end[s][(size_t)k0] > b->imu_pos[s]) b->imu_pos[s] = b->imu_end[s][(size_t)k0];
+                    if (b->lane[s].imu_end[(size_t)k0] > b->lane[s].imu_pos) b->lane[s].imu_pos = b->lane[s].imu_end[(size_t)k0];
                 }
                 if (any) kb_ekf_step<<<ns, 384, 0, st>>>(ea);
             }
@@ -2272,9 +2286,9 @@ static int batch_enqueue_free(ptl_batch* b, int64_t n) {
         // did every sequence reach scan k1?  (a team may have left the launch while holding one: no exit is silent)
         k_sched_check<<<1, 8 * SEQ_SLOTS, 0, st>>>(b->d_ctx, b->d_sched, S, (int)k1, b->d_status);
         for (int s = 0; s < S; ++s) {
-            if (with_ekf) b->imu_pos[s] = (k1 < b->cfg.n_scans) ? b->imu_end[s][(size_t)k1] : b->imu_end[s][(size_t)k1 - 1];
-            b->icp[s]->scans_done += (k1 - k0);
-            b->icp[s]->last_n = b->cfg.points_per_scan;
+            if (with_ekf) b->lane[s].imu_pos = (k1 < b->cfg.n_scans) ? b->lane[s].imu_end[(size_t)k1] : b->lane[s].imu_end[(size_t)k1 - 1];
+            b->lane[s].icp->scans_done += (k1 - k0);
+            b->lane[s].icp->last_n = b->cfg.points_per_scan;
         }
         b->n_out += k1 - k0;
         b->next_scan = k1;
@@ -2347,10 +2361,10 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
             memset(&ea, 0, sizeof ea);
             bool any = false;
             for (int s = 0; s < S; ++s) {
-                ea.e[s] = b->ekf[s]->st; ea.imu[s] = b->d_imu[s];
-                ea.i0[s] = (int)b->imu_pos[s]; ea.i1[s] = (int)b->imu_end[s][(size_t)k];
+                ea.e[s] = b->lane[s].ekf->st; ea.imu[s] = b->lane[s].d_imu;
+                ea.i0[s] = (int)b->lane[s].imu_pos; ea.i1[s] = (int)b->lane[s].imu_end[(size_t)k];
                 any = any || ea.i1[s] > ea.i0[s];
-                b->imu_pos[s] = b->imu_end[s][(size_t)k] > b->imu_pos[s] ? b->imu_end[s][(size_t)k] : b->imu_pos[s];
+                b->lane[s].imu_pos = b->lane[s].imu_end[(size_t)k] > b->lane[s].imu_pos ? b->lane[s].imu_end[(size_t)k] : b->lane[s].imu_pos;
             }
             if (any) {
                 if (b->ev_side_valid) HIPCHK(hipStreamWaitEvent(st, b->ev_side, 0));
@@ -2394,12 +2408,12 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
             EkfBatchArgs ea;
             memset(&ea, 0, sizeof ea);
             for (int s = 0; s < S; ++s) {
-                const int64_t e2 = (k + 1 < b->cfg.n_scans) ? b->imu_end[s][(size_t)k + 1] : b->imu_pos[s];
-                ea.e[s] = b->ekf[s]->st; ea.imu[s] = b->d_imu[s];
-                ea.i0[s] = (int)b->imu_pos[s]; ea.i1[s] = (int)e2;
-                ea.pose[s] = b->icp[s]->c.traj + 16 * o;
-                ea.out_pose[s] = b->d_res_poses[s] + 16 * o; ea.out_t[s] = b->d_res_t[s] + o; ea.out_row8[s] = b->d_rows[s] + 8 * o;
-                b->imu_pos[s] = e2;
+                const int64_t e2 = (k + 1 < b->cfg.n_scans) ? b->lane[s].imu_end[(size_t)k + 1] : b->lane[s].imu_pos;
+                ea.e[s] = b->lane[s].ekf->st; ea.imu[s] = b->lane[s].d_imu;
+                ea.i0[s] = (int)b->lane[s].imu_pos; ea.i1[s] = (int)e2;
+                ea.pose[s] = b->lane[s].icp->c.traj + 16 * o;
+                ea.out_pose[s] = b->lane[s].d_res_poses + 16 * o; ea.out_t[s] = b->lane[s].d_res_t + o; ea.out_row8[s] = b->lane[s].d_rows + 8 * o;
+                b->lane[s].imu_pos = e2;
             }
             ea.update_first = 1;
             kb_ekf_step<<<S, 384, 0, sd>>>(ea);
@@ -2409,13 +2423,13 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
         kb_map_insert_b<<<dim3(nb, S), 256, 0, sd>>>(b->d_ctx, ki);
         kb_map_insert_c<<<dim3(nb, S), 256, 0, sd>>>(b->d_ctx, ki);
         kb_map_prune<<<dim3((unsigned)((ic.map_block_capacity + 255) / 256), S), 256, 0, sd>>>(b->d_ctx, ki);
-        for (int s = 0; s < S; ++s) { b->icp[s]->scans_done++; b->icp[s]->last_n = pps; }
+        for (int s = 0; s < S; ++s) { b->lane[s].icp->scans_done++; b->lane[s].icp->last_n = pps; }
         b->n_out++;
         b->next_scan = k + 1;
         if (ic.rebuild_every > 0 && (b->n_out % ic.rebuild_every) == 0) {
             for (int s = 0; s < S; ++s) {
-                HIPCHK(hipMemsetAsync(b->icp[s]->c.tab, 0xFF, ((size_t)b->icp[s]->c.tmask + 1) * sizeof(TabEnt), sd));
-                HIPCHK(hipMemsetAsync(&b->icp[s]->c.st->tab_used, 0, sizeof(unsigned), sd));
+                HIPCHK(hipMemsetAsync(b->lane[s].icp->c.tab, 0xFF, ((size_t)b->lane[s].icp->c.tmask + 1) * sizeof(TabEnt), sd));
+                HIPCHK(hipMemsetAsync(&b->lane[s].icp->c.st->tab_used, 0, sizeof(unsigned), sd));
             }
             kb_map_rebuild<<<dim3((unsigned)((ic.map_block_capacity + 255) / 256), S), 256, 0, sd>>>(b->d_ctx, ki);
         }
@@ -2460,11 +2474,9 @@ extern "C" int ptl_batch_wait(ptl_batch* b) {
     // (a team that only ran out of its idle budget while the last sequences were in other teams' hands - bit 4 alone, every sequence at its last
     // scan - did no harm: the bit stays readable through ptl_batch_status, the wait does not fail on it)
     if (status & ~SEQ_EXIT_IDLE) return set_err(PTL_ERR_STATE, "free-running launch: teams left early, status 0x%x (1 head-of-launch barrier, 2 job barrier, 4 idle, 8 gave up on a sequence, 16 scans incomplete)", status);
-    for (int s = 0; b->dk_on && s < b->S; ++s) {  // IMU deskew: a truncated knot list is an error, not a quiet fallback
-        int ovf = 0;
-        const int rc = ekf_knot_overflow(b->ekf[s], &ovf);
+    for (int s = 0; b->dk_on && s < b->S; ++s) {
+        const int rc = lane_dk_overflow(b->lane[s], "ptl_batch_wait", s);
         if (rc) return rc;
-        if (ovf) return set_err(PTL_ERR_CAPACITY, "IMU deskew: sequence %d: the filter's knot list overflowed (capacity %lld)", s, (long long)b->ekf[s]->knot_cap);
     }
     return PTL_OK;
 }
@@ -2498,7 +2510,7 @@ extern "C" int ptl_batch_sched_counters(ptl_batch* b, int32_t s, uint64_t out[4]
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipMemcpy(out, (char*)b->icp[s]->c.st + offsetof(DevState, sched_cnt), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, (char*)b->lane[s].icp->c.st + offsetof(DevState, sched_cnt), 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PTL_OK;
 }
 // compile-time constants of this build that callers' byte models depend on (bench.py EXEC_COST):
@@ -2532,21 +2544,9 @@ extern "C" int ptl_batch_results(ptl_batch* b, int32_t s, double* res_poses, dou
                                  ptl_icp_stats* stats, int64_t max_n, int64_t* n_out) {
     if (!b || s < 0 || s >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
-    const int64_t n = b->n_out < max_n ? b->n_out : max_n;
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (n > 0) {
-        if (res_poses && b->cfg.with_ekf) HIPCHK(hipMemcpy(res_poses, b->d_res_poses[s], (size_t)n * 128, hipMemcpyDeviceToHost));
-        if (res_t && b->cfg.with_ekf) HIPCHK(hipMemcpy(res_t, b->d_res_t[s], (size_t)n * 8, hipMemcpyDeviceToHost));
-        if (kiss_poses) HIPCHK(hipMemcpy(kiss_poses, b->icp[s]->c.traj, (size_t)n * 128, hipMemcpyDeviceToHost));
-        if (stats) {
-            std::vector<ScanStats> tmp((size_t)n);
-            HIPCHK(hipMemcpy(tmp.data(), b->icp[s]->c.sstats, (size_t)n * sizeof(ScanStats), hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < n; ++i) stats_out(tmp[(size_t)i], &stats[i]);
-        }
-    }
-    if (n_out) *n_out = n;
-    return PTL_OK;
+    return lane_results(b->lane[s], b->cfg.with_ekf != 0, b->n_out, res_poses, res_t, kiss_poses, stats, max_n, n_out);
 }
 extern "C" int ptl_batch_smoother_enable(ptl_batch* b, int32_t on) {
     if (!b) return set_err(PTL_ERR_ARG, "null argument");
@@ -2558,20 +2558,20 @@ extern "C" int ptl_batch_smoother_enable(ptl_batch* b, int32_t on) {
     if (b->d_sm_jobs) { (void)hipFree(b->d_sm_jobs); b->d_sm_jobs = nullptr; }
     if (b->d_sm_info) { (void)hipFree(b->d_sm_info); b->d_sm_info = nullptr; }
     for (int s = 0; s < b->S; ++s) {
-        int rc = ekf_log_set(b->ekf[s], on ? b->cfg.n_scans : 0);
+        int rc = ekf_log_set(b->lane[s].ekf, on ? b->cfg.n_scans : 0);
         if (rc) {
-            for (int q = 0; q < s; ++q) (void)ekf_log_set(b->ekf[q], 0);
+            for (int q = 0; q < s; ++q) (void)ekf_log_set(b->lane[q].ekf, 0);
             return rc;
         }
     }
     if (!on) return PTL_OK;
     if (dalloc(&b->d_sm_jobs, (size_t)b->S) != hipSuccess || dalloc(&b->d_sm_info, (size_t)b->S * 2) != hipSuccess) {
-        for (int q = 0; q < b->S; ++q) (void)ekf_log_set(b->ekf[q], 0);
+        for (int q = 0; q < b->S; ++q) (void)ekf_log_set(b->lane[q].ekf, 0);
         return set_err(PTL_ERR_HIP, "smoother job allocation failed");
     }
     std::vector<EkfSmoothJob> jobs((size_t)b->S);
     for (int s = 0; s < b->S; ++s) {
-        jobs[(size_t)s] = b->ekf[s]->job;
+        jobs[(size_t)s] = b->lane[s].ekf->job;
         jobs[(size_t)s].info = b->d_sm_info + 2 * s;  // every status word in one copy
     }
     b->h_sm_info.assign((size_t)b->S * 2, 0);
@@ -2589,7 +2589,7 @@ extern "C" int ptl_batch_smooth(ptl_batch* b) {
     HIPCHK(hipMemcpyAsync(b->h_sm_info.data(), b->d_sm_info, (size_t)b->S * 2 * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     for (int s = 0; s < b->S; ++s) {
-        const int rc = smooth_status(b->ekf[s], &b->h_sm_info[2 * (size_t)s], "ptl_batch_smooth", s);
+        const int rc = smooth_status(b->lane[s].ekf, &b->h_sm_info[2 * (size_t)s], "ptl_batch_smooth", s);
         if (rc) return rc;
     }
     b->sm_done = true;
@@ -2600,7 +2600,7 @@ extern "C" int ptl_batch_smoothed(ptl_batch* b, int32_t seq, double* poses16, do
     if (!b->sm_done) return set_err(PTL_ERR_STATE, "ptl_batch_smoothed: no backward pass since the last run (ptl_batch_smooth)");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     const int64_t n = b->h_sm_info[2 * (size_t)seq + 1];
-    int rc = smooth_copy_out(b->ekf[seq], n, poses16, ts, nav19, cov324);
+    int rc = smooth_copy_out(b->lane[seq].ekf, n, poses16, ts, nav19, cov324);
     if (rc) return rc;
     if (n_rows) *n_rows = n;
     return PTL_OK;
@@ -2609,92 +2609,58 @@ extern "C" int ptl_batch_smoother_log(ptl_batch* b, int32_t seq, double* entries
     if (!b || seq < 0 || seq >= b->S || max_entries < 0) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
-    return ekf_log_read(b->ekf[seq], entries, max_entries, n_entries, overflow);
+    return lane_smoother_log(b->lane[seq], b->cfg, "ptl_batch_smoother_log", entries, max_entries, n_entries, overflow);
 }
 // IMU deskew for every sequence of the batch, either driver, resident or sweep ring
 extern "C" int ptl_batch_imu_deskew_enable(ptl_batch* b, int32_t on, int64_t knot_capacity) {
     if (!b) return set_err(PTL_ERR_ARG, "null argument");
-    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "ptl_batch_imu_deskew_enable: an ICP-only batch (with_ekf = 0) has no filter to deskew with");
-    if (on && !b->cfg.icp.deskew) return set_err(PTL_ERR_STATE, "ptl_batch_imu_deskew_enable: deskew is off in the configuration");
-    if (on && knot_capacity < 2) return set_err(PTL_ERR_ARG, "ptl_batch_imu_deskew_enable: knot_capacity must be >= 2");
-    for (int s = 0; on && s < b->S; ++s)
-        if (dk_knots_needed(b->imu_end[s]) > knot_capacity)
-            return set_err(PTL_ERR_ARG, "ptl_batch_imu_deskew_enable: sequence %d: the IMU samples between two scans need %lld knots, knot_capacity is %lld", s,
-                           (long long)dk_knots_needed(b->imu_end[s]), (long long)knot_capacity);
+    int rc = dk_enable_check(b->cfg, b->lane, b->S, on, knot_capacity, "ptl_batch_imu_deskew_enable");
+    if (rc) return rc;
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
     b->dk_on = false;
     b->ev_filter_valid = false;
-    for (int s = 0; s < b->S; ++s) {
-        b->dk_times[s] = false;
-        int rc = dk_wire(b->icp[s], nullptr, nullptr, nullptr, 0);
-        if (rc == PTL_OK) rc = ekf_knots_set(b->ekf[s], 0);
+    if (on && !b->ev_filter) HIPCHK(hipEventCreateWithFlags(&b->ev_filter, hipEventDisableTiming));
+    for (int s = 0; s < b->S; ++s) {  // every sequence off first: a failure leaves none half on
+        rc = lane_dk_set(b->lane[s], b->cfg.n_scans, 0);
         if (rc) return rc;
     }
+    for (int s = 0; on && s < b->S && rc == PTL_OK; ++s) rc = lane_dk_set(b->lane[s], b->cfg.n_scans, knot_capacity);
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (!on) return PTL_OK;
-    if (!b->ev_filter) HIPCHK(hipEventCreateWithFlags(&b->ev_filter, hipEventDisableTiming));
-    const size_t n = (size_t)b->cfg.n_scans;
-    for (int s = 0; s < b->S; ++s) {
-        if (!b->d_dk_t0t1[s] && (dalloc(&b->d_dk_t0t1[s], 2 * n) != hipSuccess || dalloc(&b->d_dk_modes[s], n) != hipSuccess))
-            return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
-        HIPCHK(hipMemset(b->d_dk_modes[s], 0, n * sizeof(int)));
-        int rc = ekf_knots_set(b->ekf[s], knot_capacity);
-        if (rc == PTL_OK) rc = dk_wire(b->icp[s], b->ekf[s], b->d_dk_t0t1[s], b->d_dk_modes[s], (int64_t)n);
-        if (rc) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->dk_on = true;
-    return PTL_OK;
+    b->dk_on = on && rc == PTL_OK;
+    return rc;
 }
 extern "C" int ptl_batch_upload_sweep_times(ptl_batch* b, int32_t seq, const double* t0t1) {
     if (!b || !t0t1 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
     if (!b->dk_on) return set_err(PTL_ERR_STATE, "ptl_batch_upload_sweep_times: IMU deskew is not enabled");
-    for (int64_t k = 0; k < b->cfg.n_scans; ++k)
-        if (!(t0t1[2 * k + 1] >= t0t1[2 * k])) return set_err(PTL_ERR_ARG, "ptl_batch_upload_sweep_times: scan %lld has t1 < t0", (long long)k);
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipMemcpy(b->d_dk_t0t1[seq], t0t1, (size_t)b->cfg.n_scans * 16, hipMemcpyHostToDevice));
-    b->dk_times[seq] = true;
-    return PTL_OK;
+    return lane_upload_sweep_times(b->lane[seq], b->cfg.n_scans, t0t1, "ptl_batch_upload_sweep_times");
 }
 extern "C" int ptl_batch_deskew_modes(ptl_batch* b, int32_t seq, int32_t* modes, int64_t max_n, int64_t* n) {
     if (!b || !modes || max_n < 0 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
-    const int64_t m = b->n_out < max_n ? b->n_out : max_n;
-    if (!b->dk_on) {
-        for (int64_t k = 0; k < m; ++k) modes[k] = (b->cfg.icp.deskew && k >= 2) ? DK_MODE_CV : DK_MODE_NONE;
-    } else {
-        HIPCHK(hipStreamSynchronize(b->side));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        if (m > 0) HIPCHK(hipMemcpy(modes, b->d_dk_modes[seq], (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    if (n) *n = m;
-    return PTL_OK;
+    HIPCHK(hipStreamSynchronize(b->side));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return lane_deskew_modes(b->lane[seq], b->cfg, b->dk_on, b->n_out, modes, max_n, n);
 }
 extern "C" int ptl_batch_knots(ptl_batch* b, int32_t seq, double* knots, int64_t max_knots, int64_t* n_knots, int32_t* overflow) {
     if (!b || max_knots < 0 || seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
-    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "an ICP-only batch has no filter");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->side));
-    return ekf_knots_read(b->ekf[seq], knots, max_knots, n_knots, overflow);
+    return lane_knots(b->lane[seq], b->cfg, "ptl_batch_knots", knots, max_knots, n_knots, overflow);
 }
 extern "C" int ptl_batch_copy_traj(ptl_batch* b, int32_t s, void* dst_device, int64_t max_rows, int64_t* rows) {
     if (!b || !dst_device || s < 0 || s >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
-    if (!b->cfg.with_ekf) return set_err(PTL_ERR_STATE, "trajectory rows need with_ekf");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
-    const int64_t n = b->n_out < max_rows ? b->n_out : max_rows;
     HIPCHK(hipStreamSynchronize(b->side));
-    if (n > 0) HIPCHK(hipMemcpyAsync(dst_device, b->d_rows[s], (size_t)n * 64, hipMemcpyDeviceToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (rows) *rows = n;
-    return PTL_OK;
+    return lane_copy_traj(b->lane[s], b->cfg, b->n_out, b->stream, dst_device, max_rows, rows);
 }
 extern "C" int ptl_batch_icp(ptl_batch* b, int32_t s, ptl_icp** icp) {
     if (!b || !icp || s < 0 || s >= b->S) return set_err(PTL_ERR_ARG, "bad argument");
-    *icp = b->icp[s];
+    *icp = b->lane[s].icp;
     return PTL_OK;
 }
 extern "C" int ptl_batch_seq_clocks(ptl_batch* b, int32_t s, int64_t out[8]) {
@@ -2702,7 +2668,7 @@ extern "C" int ptl_batch_seq_clocks(ptl_batch* b, int32_t s, int64_t out[8]) {
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->stream));
     long long h[8];
-    HIPCHK(hipMemcpy(h, (char*)b->icp[s]->c.st + offsetof(DevState, seq_clk), sizeof h, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h, (char*)b->lane[s].icp->c.st + offsetof(DevState, seq_clk), sizeof h, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; ++i) out[i] = h[i];
     return PTL_OK;
 }
@@ -2713,13 +2679,13 @@ extern "C" int ptl_batch_exec_counters(ptl_batch* b, int32_t s, uint64_t out[16]
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
     memset(out, 0, 16 * sizeof(uint64_t));
-    HIPCHK(hipMemcpy(out, (char*)b->icp[s]->c.st + offsetof(DevState, exec_cnt), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out + 8, (char*)b->icp[s]->c.st + offsetof(DevState, empty_cnt), sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, (char*)b->lane[s].icp->c.st + offsetof(DevState, exec_cnt), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out + 8, (char*)b->lane[s].icp->c.st + offsetof(DevState, empty_cnt), sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PTL_OK;
 }
 extern "C" int ptl_batch_gn_phases(ptl_batch* b, int64_t out[8]) {
     if (!b || !out) return set_err(PTL_ERR_ARG, "null argument");
-    return ptl_icp_gn_phases(b->icp[0], out);
+    return ptl_icp_gn_phases(b->lane[0].icp, out);
 }
 extern "C" int ptl_batch_profile(ptl_batch* b, int enable, double* gn_ms_total, int64_t* gn_launches, int reset) {
     if (!b) return set_err(PTL_ERR_ARG, "null argument");
@@ -2936,8 +2902,8 @@ extern "C" int ptl_batch_gather_trajectories(ptl_batch* b, ptl_comm* c, double* 
     for (int64_t s = 0; s < S && e == hipSuccess; ++s) {
         const int64_t n = counts[(size_t)s];
         if (n <= 0) continue;
-        if (b->cfg.with_ekf) e = hipMemcpyAsync(d_rows + (size_t)s * T * 8, b->d_rows[s], (size_t)n * 64, hipMemcpyDeviceToDevice, b->stream);
-        else { k_kiss_rows<<<(int)((n + 63) / 64), 64, 0, b->stream>>>(b->icp[s]->c.traj, (int)n, d_rows + (size_t)s * T * 8); e = hipGetLastError(); }
+        if (b->cfg.with_ekf) e = hipMemcpyAsync(d_rows + (size_t)s * T * 8, b->lane[s].d_rows, (size_t)n * 64, hipMemcpyDeviceToDevice, b->stream);
+        else { k_kiss_rows<<<(int)((n + 63) / 64), 64, 0, b->stream>>>(b->lane[s].icp->c.traj, (int)n, d_rows + (size_t)s * T * 8); e = hipGetLastError(); }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess) { (void)hipFree(d_rows); return set_err(PTL_ERR_HIP, "row staging failed: %s", hipGetErrorString(e)); }
