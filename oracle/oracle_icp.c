@@ -64,10 +64,11 @@ void orc_se3_exp(const double xi[6], double T[16]) {
         b = 0.5 - t2 / 24.0;
         c = 1.0 / 6.0 - t2 / 120.0;
     } else {
-        double t2 = th * th;
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / t2;
-        c = (th - sin(th)) / (t2 * th);
+        double t2 = th * th, sn = sin(th), cs = cos(th);
+        a = sn / th;
+        /* not (1 - cos th) / th^2 while cos th > 0: its cancellation reaches t as 1e-16 / th (1e-10 |upsilon| at th = 1e-6) */
+        b = cs > 0.0 ? sn * sn / (t2 * (1.0 + cs)) : (1.0 - cs) / t2;
+        c = (th - sn) / (t2 * th);
     }
     for (int i = 0; i < 9; ++i) {
         double I = (i % 4 == 0) ? 1.0 : 0.0;

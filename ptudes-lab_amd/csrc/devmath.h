@@ -238,6 +238,10 @@ PTL_HD double rot_angle(const double R[9]) {
 }
 
 // SE(3) exp of xi = (upsilon, omega) [Sophus order]: R = I + a K + b K^2, t = (I + b K + c K^2) upsilon
+// b is NOT the textbook (1 - cos th) / th^2 while cos th > 0: the rounding of cos (1e-16, absolute) over th^2 times the |K| = th of
+// b K upsilon is an error of 1e-16 / th in t / |upsilon| - 1e-10 just above the series switch, in the deskew table of every sweep.
+// 1 - cos = sin^2 / (1 + cos) has no cancellation there; past a quarter turn the textbook form has none either.  (The same loss in
+// c = (th - sin) / th^3 is multiplied by |K^2| = th^2 and stays at 1e-16.)  oracle/oracle_icp.c orc_se3_exp does the same.
 PTL_HD Rt se3_exp(const double xi[6]) {
     const double* w = xi + 3;
     const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
@@ -246,7 +250,8 @@ PTL_HD Rt se3_exp(const double xi[6]) {
         a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; c = 1.0 / 6.0 - th2 / 120.0;
     } else {
         const double sn = sin(th), cs = cos(th);
-        a = sn / th; b = (1.0 - cs) / th2; c = (th - sn) / (th2 * th);
+        const bool acute = cs > 0.0;
+        a = sn / th; b = (acute ? sn * sn : 1.0 - cs) / (acute ? th2 * (1.0 + cs) : th2); c = (th - sn) / (th2 * th);
     }
     double K[9], K2[9];
     skew(w, K);
@@ -264,7 +269,8 @@ PTL_HD Rt se3_exp(const double xi[6]) {
 // se3_exp for the Gauss-Newton increments.  Below 0.05 rad the coefficients come from their Maclaurin series
 // (six terms: truncation < 1e-20, and none of the cancellation the closed forms (1 - cos) / th^2, (th - sin) / th^3
 // suffer at small angles) - no sin / cos / three divisions on the serial tail of every iteration.  The result
-// differs from se3_exp() by rounding only (<= 1e-16 in R and t for the increments a registration produces).
+// differs from se3_exp() by rounding only: both are within 2 x 2^-52 of the exact R and t / |upsilon|, and within
+// 1.3 x 2^-52 of each other (tests/test_devmath_probe.py).
 PTL_HD Rt se3_exp_gn(const double xi[6]) {
     const double* w = xi + 3;
     const double t = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];

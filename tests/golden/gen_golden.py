@@ -5,6 +5,8 @@ in THIS container and records inputs + expected outputs as small fixtures.
 Run only where /root/reference exists (the build container):
 
     python tests/golden/gen_golden.py            # regenerates every fixture
+    GOLDEN_OUT=dir python tests/golden/gen_golden.py ekf_steps_default   # one case; the ekf_steps_* cases write to GOLDEN_OUT, to
+                                                 # check that a regeneration reproduces the committed file before replacing it
 
 The reference cannot travel to the GPU box, so the fixtures written next to this
 script are what the tests consume.  Nothing here is imported by the product.
@@ -73,6 +75,18 @@ def _rand_pose(rng, trans_scale=1.0, rot_scale=0.3):
     return T
 
 
+def _quat_case_w(M):
+    """Which formula the four-case matrix-to-quaternion conversion (scipy's Rotation.from_matrix) takes for M - 0, 1, 2: that
+    diagonal entry is the largest, 3: the trace is - and the w it yields before normalisation and sign flip."""
+    import numpy as np
+    d = np.diag(M)
+    c = int(np.argmax(d))
+    if d.sum() > d[c]:
+        return 3, 1.0 + d.sum()
+    j, k = (c + 1) % 3, (c + 2) % 3
+    return c, M[k, j] - M[j, k]
+
+
 # ----------------------------------------------------------------------------- cases
 
 
@@ -83,9 +97,11 @@ def case_ekf_steps(variant):
     from ptudes.ins.es_ekf import ESEKF
     from ptudes.ins.data import IMU, GRAV
 
-    rng = np.random.default_rng({"default": 11, "init": 12, "cov": 13}[variant])
+    rng = np.random.default_rng({"default": 11, "init": 12, "cov": 13, "turn": 14, "inverted": 15}[variant])
     n_imu, upd_every = 300, 10
     kwargs = {}
+    if variant == "inverted":  # sensor mounted upside down: gravity along +z of the frame it starts in
+        kwargs = dict(init_grav=GRAV * np.array([0.0, 0.0, 1.0]))
     if variant == "init":
         kwargs = dict(init_grav=GRAV * np.array([0.02, -0.01, -0.9997]),
                       init_bacc=np.array([0.05, -0.02, 0.03]),
@@ -94,8 +110,19 @@ def case_ekf_steps(variant):
 
     # smooth-ish body motion: specific force + gyro, irregular dt
     ts = 100.0 + np.cumsum(rng.uniform(0.008, 0.012, n_imu))
-    lacc = np.array([0, 0, GRAV]) + rng.normal(0, 0.8, (n_imu, 3))
+    lacc = np.array([0, 0, -GRAV if variant == "inverted" else GRAV]) + rng.normal(0, 0.8, (n_imu, 3))
     avel = rng.normal(0, 0.3, (n_imu, 3))
+    if variant == "turn":  # the attitude passes through all of SO(3) in 3 s
+        avel = avel + np.array([0.4, -0.3, 2.2])
+    # measured poses far from the estimate (legal input): the first pose of the inverted sensor is a half roll; two updates of the
+    # turn are 175 degrees off about axes that make the attitude error's quaternion come out of the conversion with w < 0
+    far = {}
+    if variant == "inverted":
+        far = {upd_every: np.array([np.pi, 0.0, 0.0])}
+    if variant == "turn":
+        far = {10 * upd_every: np.radians(175.0) * np.array([-1.0, 0.2, 0.1]) / np.linalg.norm([-1.0, 0.2, 0.1]),
+               20 * upd_every: np.radians(175.0) * np.array([0.1, -1.0, 0.2]) / np.linalg.norm([0.1, -1.0, 0.2])}
+    resid_w = []
 
     navs = np.zeros((n_imu, 19))
     upd_idx, upd_pose, upd_cov = [], [], []
@@ -111,6 +138,9 @@ def case_ekf_steps(variant):
             T = ekf.nav.pose_mat()
             T[:3, 3] += rng.normal(0, 0.05, 3)
             T[:3, :3] = T[:3, :3] @ R.from_rotvec(rng.normal(0, 0.02, 3)).as_matrix()
+            if i in far:
+                T[:3, :3] = T[:3, :3] @ R.from_rotvec(far[i]).as_matrix()
+            resid_w.append(_quat_case_w(ekf.nav.att_h.T @ T[:3, :3])[1])
             cov = None
             if variant == "cov":
                 A = rng.normal(0, 0.03, (6, 6))
@@ -122,9 +152,16 @@ def case_ekf_steps(variant):
             upd_idx.append(i)
             upd_pose.append(T)
             upd_cov.append(np.zeros((6, 6)) if cov is None else cov)
+    if variant in ("turn", "inverted"):
+        # what these two are for, from the reference's own attitudes: together they take every matrix-to-quaternion case at least
+        # 20 times (the turn alone does; the inverted sensor stays in the x case), and an attitude error arrives with w < 0
+        cases = np.bincount([_quat_case_w(R.from_quat(q).as_matrix())[0] for q in navs[:, 3:7]], minlength=4)
+        print(f"golden: ekf_steps_{variant} quaternion cases x, y, z, trace = {cases}, attitude errors with w < 0: {sum(w < 0 for w in resid_w)}")
+        assert (cases >= 20).all() if variant == "turn" else cases[0] >= 20, cases
+        assert any(w < 0 for w in resid_w), resid_w
     np.savez_compressed(
-        os.path.join(HERE, f"ekf_steps_{variant}.npz"),
-        imu_ts=ts, imu_ts_ns=ts_ns, imu_lacc=lacc, imu_avel=avel, nav_after_imu=navs,
+        os.path.join(os.environ.get("GOLDEN_OUT", HERE), f"ekf_steps_{variant}.npz"),
+        imu_ts=ts, imu_lacc=lacc, imu_avel=avel, nav_after_imu=navs,
         upd_idx=np.array(upd_idx), upd_pose=np.array(upd_pose),
         upd_cov=np.array(upd_cov), has_cov=np.array(variant == "cov"),
         nav_after_upd=np.array(navs_post), cov_pre=np.array(covs_pre),
@@ -485,6 +522,8 @@ CASES = {
     "ekf_steps_default": lambda: case_ekf_steps("default"),
     "ekf_steps_init": lambda: case_ekf_steps("init"),
     "ekf_steps_cov": lambda: case_ekf_steps("cov"),
+    "ekf_steps_turn": lambda: case_ekf_steps("turn"),
+    "ekf_steps_inverted": lambda: case_ekf_steps("inverted"),
     "ekf_sim": case_ekf_sim,
     "sim_imu": case_sim_imu,
     "pose_files": case_pose_files,

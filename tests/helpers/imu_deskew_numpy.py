@@ -62,7 +62,9 @@ def se3_exp(xi):
     if th < 1e-6:
         a, b, c = 1.0 - th2 / 6.0, 0.5 - th2 / 24.0, 1.0 / 6.0 - th2 / 120.0
     else:
-        a, b, c = np.sin(th) / th, (1.0 - np.cos(th)) / th2, (th - np.sin(th)) / (th2 * th)
+        sn, cs = np.sin(th), np.cos(th)
+        # b as csrc/devmath.h se3_exp has it: (1 - cos) / th^2 cancels, and b K upsilon carries that into t as 1e-16 / th
+        a, b, c = sn / th, (sn * sn / (th2 * (1.0 + cs)) if cs > 0.0 else (1.0 - cs) / th2), (th - sn) / (th2 * th)
     K = skew(w)
     K2 = K @ K
     T = np.eye(4)

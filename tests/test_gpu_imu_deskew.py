@@ -77,6 +77,34 @@ def test_column_table_equals_the_restatement():
     assert list(icp.deskew_modes()) == [2] * n
 
 
+def test_column_table_through_a_full_turn(golden_dir):
+    """knots from tests/golden/ekf_steps_turn.npz - its IMU samples (2.2 rad/s) and its measured poses, two of them 175 degrees off - so
+    that the knots' attitudes take every case of the matrix-to-quaternion conversion (asserted).  The scans hold no valid point:
+    every registration returns its guess, the filter's own pose, and its update moves no state; the fixture's pose follows it."""
+    import os
+    from tests.helpers.so3_cases import quat_case, quat_to_R
+    g = np.load(os.path.join(golden_dir, "ekf_steps_turn.npz"))
+    rows = np.c_[g["imu_ts"], g["imu_lacc"], g["imu_avel"]]
+    icp, e = core.Icp(**KW), core.Ekf()
+    e.enable_knots(32)
+    scan = np.zeros((W, 3), dtype=np.float32)
+    seen, start = [], 0
+    for k, i in enumerate(int(i) for i in g["upd_idx"]):
+        e.process_imu_batch(rows[start:i + 1])
+        start = i + 1
+        kn, ovf = e.knots()
+        assert not ovf and len(kn) >= 10
+        seen.append(quat_case(quat_to_R(kn[:, 4:8])))
+        t0, t1 = kn[0, 0], kn[-1, 0]
+        core.icp_ekf_step(icp, e, [], scan, use_imu_prediction=True, sweep=(t0, t1))
+        mode, ref = dk.column_table(kn, t0, t1, W)
+        assert mode == 2
+        assert np.abs(icp.column_table() - ref).max() < 1e-12, k
+        e.process_pose(g["upd_pose"][k])
+    assert list(icp.deskew_modes()) == [2] * len(g["upd_idx"])
+    assert (np.bincount(np.concatenate(seen), minlength=4) >= 20).all()
+
+
 def _oracle_chain(seq, n):
     """oracle.cpu.EKF supplies the knots, the restatement deskews, oracle.cpu.ICP(deskew=0) registers, the EKF takes the KISS pose"""
     icp, ekf = orc.ICP(deskew=0, **KW), orc.EKF()

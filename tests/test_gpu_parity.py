@@ -5,6 +5,7 @@ Tolerances: integer / index work bit-exact (point selections, c
 covariance 1e-9; ICP teacher-forced |dt| <= 2e-4 m, angle <= 2e-5 rad; free-running trajectories
 RMSE <= 1 cm over the compared span.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -36,10 +37,10 @@ def _pose_diff(A, B):
 
 
 # ------------------------------------------------------------------------------------------------ EKF
-@pytest.mark.parametrize("variant", ["default", "init", "cov"])
+@pytest.mark.parametrize("variant", ["default", "init", "cov", "turn", "inverted"])
 def test_ekf_golden_steps(golden_dir, variant):
     g = np.load(os.path.join(golden_dir, f"ekf_steps_{variant}.npz"))
-    default = variant != "init"
+    default = variant not in ("init", "inverted")
     ekf = core.Ekf(None if default else g["init_grav"], None if default else g["init_bacc"],
                    None if default else g["init_bgyr"])
     assert np.abs(ekf.cov - g["cov0"]).max() <= 1e-12
@@ -58,6 +59,41 @@ def test_ekf_golden_steps(golden_dir, variant):
             assert np.abs(cov - ref).max() <= EKF_TOL * max(1.0, np.abs(ref).max())
             _nav_close(nav, g["nav_after_upd"][k])
     assert ekf.ts == float(g["final_ts"])
+
+
+@pytest.mark.parametrize("variant", ["turn", "inverted"])
+def test_ekf_golden_turned_streams_in_imu_batches(golden_dir, variant):
+    """the streams that reach the diagonal cases of R_to_quat and the w < 0 flip of R_to_rotvec (tests/test_oracle_ekf_golden.py
+    asserts that they do), the IMU samples between two updates in ONE launch: the reference's states at EKF_TOL, and the same bits
+    as a second handle fed sample by sample"""
+    g = np.load(os.path.join(golden_dir, f"ekf_steps_{variant}.npz"))
+    init = (None, None, None) if variant == "turn" else (g["init_grav"], g["init_bacc"], g["init_bgyr"])
+    one, bat = core.Ekf(*init), core.Ekf(*init)
+    rows = np.c_[g["imu_ts"], g["imu_lacc"], g["imu_avel"]]
+
+    def feed(a, b):
+        for r in rows[a:b]:
+            one.process_imu(r[1:4], r[4:7], r[0])
+        bat.process_imu_batch(rows[a:b])
+        (n1, c1), (nb, cb) = one.state(), bat.state()
+        assert np.array_equal(n1, nb) and np.array_equal(c1, cb), (a, b)
+        return nb, cb
+
+    start = 0
+    for k, i in enumerate(int(i) for i in g["upd_idx"]):
+        nav, cov = feed(start, i + 1)
+        start = i + 1
+        _nav_close(nav, g["nav_after_imu"][i])
+        assert np.abs(cov - g["cov_pre"][k]).max() <= EKF_TOL * max(1.0, np.abs(g["cov_pre"][k]).max())
+        for e in (one, bat):
+            e.process_pose(g["upd_pose"][k], None)
+        (n1, c1), (nav, cov) = one.state(), bat.state()
+        assert np.array_equal(n1, nav) and np.array_equal(c1, cov), k
+        _nav_close(nav, g["nav_after_upd"][k])
+        assert np.abs(cov - g["cov_post"][k]).max() <= EKF_TOL * max(1.0, np.abs(g["cov_post"][k]).max())
+    nav, _ = feed(start, len(rows))
+    _nav_close(nav, g["nav_after_imu"][-1])
+    assert bat.ts == one.ts == float(g["final_ts"])
 
 
 def test_ekf_golden_sim_batched(golden_dir):
@@ -145,19 +181,18 @@ def test_map_prune_and_capacity(seq):
     assert np.array_equal(_sorted_rows(icp.map_points()), _sorted_rows(m.points()))
 
 
-def test_register_frame_teacher_forced_guess(seq):
-    """per-scan pipeline (reference kiss.py:83-131) with the same external guess on both sides:
-    selections bit-exact, poses within the ICP tolerance, stats identical"""
-    gt = seq.gt_poses(0.5)
-    g0i = np.linalg.inv(gt[0])
+def _teacher_forced(seq, guesses):
+    """per-scan pipeline (reference kiss.py:83-131) with the same external guess on both sides: selections bit-exact, poses within
+    the ICP tolerance, stats identical; returns the oracle's poses"""
     t01 = seq.column_times()
     icp = core.Icp(70.0, 1.0)
     ref = orc.ICP(70.0, 1.0)
-    for k in range(8):
+    poses = []
+    for k, guess in enumerate(guesses):
         x32 = seq.scan(k)
-        guess = g0i @ gt[k]
         Tr = ref.register_frame(x32.astype(np.float64), t01, guess)
         Tg = icp.register_frame(x32, None, guess)  # f32 input, column-implicit times
+        poses.append(Tr)
         sr, sg = ref.stats[-1], icp.stats[-1]
         for key in ("n_in", "n_valid", "n_down", "n_src"):
             assert sr[key] == sg[key], (k, key, sr[key], sg[key])
@@ -171,6 +206,58 @@ def test_register_frame_teacher_forced_guess(seq):
         assert abs(sr["sigma"] - sg["sigma"]) <= 1e-9
         assert abs(sr["iterations"] - sg["iterations"]) <= 1
         assert (sr["map_voxels"], sr["map_points"]) == (sg["map_voxels"], sg["map_points"])
+    return np.array(poses)
+
+
+def test_register_frame_teacher_forced_guess(seq):
+    gt = seq.gt_poses(0.5)
+    g0i = np.linalg.inv(gt[0])
+    _teacher_forced(seq, [g0i @ gt[k] for k in range(8)])
+
+
+# a path that turns round: 72 sweeps of a 64 x 1024 sensor at 1 rad/s of yaw (a ramp of 6 sweeps) with 5 degrees of wobble
+@pytest.fixture(scope="module")
+def turn_seq():
+    return synth.make_path_sequence(seed=2000, n_scans=72, H=64, W=1024, step_m=0.5, ramp_sweeps=6, yaw_rate=1.0, wobble_deg=5.0)
+
+
+def _rotated_world():
+    """a ground-truth frame with an arbitrary rotation: 170 degrees about (1, 1, 0.2), far from the origin"""
+    from scipy.spatial.transform import Rotation
+    ax = np.array([1.0, 1.0, 0.2])
+    Wm = np.eye(4)
+    Wm[:3, :3] = Rotation.from_rotvec(np.radians(170.0) * ax / np.linalg.norm(ax)).as_matrix()
+    Wm[:3, 3] = [-1234.5, 987.6, -55.5]
+    return Wm
+
+
+@contextlib.contextmanager
+def _oracle_threads():
+    """fixed 128-point chunks reduced in chunk order: as deterministic as one thread"""
+    orc.set_threads(min(16, synth.usable_cores()))
+    try:
+        yield
+    finally:
+        orc.set_threads(1)
+
+
+@pytest.mark.parametrize("world,cases", [("plain", {3, 2}), ("rotated", {0, 1})])
+def test_register_frame_through_a_full_turn(turn_seq, world, cases):
+    """test_register_frame_teacher_forced_guess where the attitude leaves the trace case of R_to_quat (rt_project on every pose of
+    every iteration, mat4_inv of the raw guess): the yaw runs through 360 degrees; in the rotated world the voxel grid is cut at
+    another angle and the coordinates are negative and four digits long.  Which cases the poses take is asserted from the oracle's."""
+    from tests.helpers.so3_cases import quat_case
+    gt = turn_seq.gt_poses(0.5)
+    g0i = (np.eye(4) if world == "plain" else _rotated_world()) @ np.linalg.inv(gt[0])
+    guesses = [g0i @ g for g in gt]
+    with _oracle_threads():  # 72 sweeps take the oracle a minute on one core
+        poses = _teacher_forced(turn_seq, guesses)
+    off = [np.linalg.norm((np.linalg.inv(g) @ T)[:3, 3]) for g, T in zip(guesses, poses)]
+    assert max(off) < 1.0, max(off)  # the oracle keeps the track
+    seen = quat_case(poses[:, :3, :3])
+    assert cases <= set(seen.tolist()), np.bincount(seen, minlength=4)
+    yaw = np.unwrap([np.arctan2(g[1, 0], g[0, 0]) for g in gt])
+    assert yaw.max() - yaw.min() > 2 * np.pi
 
 
 def test_register_frame_edge_cases():
@@ -417,11 +504,9 @@ def _threaded_oracle(events, **kw):
         orc.set_threads(1)
 
 
-def test_free_running_220_sweeps_imu_mode_vs_oracle():
-    """BASELINE config 3's mode (ICP + IMU-EKF, --use-imu-prediction) free-running for 220 sweeps: the HIP loop and the
-    oracle's loop stay together to 1e-9 m on every pose, and every integer statistic of every scan is identical"""
-    n = 220
-    sq = synth.make_sequence(seed=1000, n_scans=n)
+def _free_running_imu_mode(sq, n):
+    """BASELINE config 3's mode (ICP + IMU-EKF, --use-imu-prediction) free-running for n sweeps: the HIP loop and the oracle's loop
+    stay together to 1e-9 m on every pose, and every integer statistic of every scan is identical; returns the oracle's run"""
     ref = _threaded_oracle(sq.events(n), max_range=70.0, min_range=1.0, use_imu_prediction=True)
     r = core.SeqRunner(n, sq.H * sq.W, sq.imu_range_for_scan(n - 1)[1], max_range=70.0, min_range=1.0,
                        use_imu_prediction=True, with_ekf=True)
@@ -438,6 +523,27 @@ def test_free_running_220_sweeps_imu_mode_vs_oracle():
             assert out["stats"][k][key] == ref["stats"][k][key], (k, key)
     ate_r, ate_t = orc.calc_ate(out["res_poses"], ref["res_poses"])
     assert ate_t <= 1e-16 and ate_r <= 1e-16
+    return ref
+
+
+def test_free_running_220_sweeps_imu_mode_vs_oracle():
+    _free_running_imu_mode(synth.make_sequence(seed=1000, n_scans=220), 220)
+
+
+def test_free_running_through_a_full_turn_imu_mode_vs_oracle(turn_seq):
+    """the same on the path that turns round (yaw_rate 1.0: the yaw passes 360 degrees; the oracle keeps the track, 0.87 m from
+    ground truth at most - the bootstrap offset): d_ekf_step and rt_project of the resident loop at attitudes in the z case of
+    R_to_quat as well as the trace case, asserted from the oracle's poses"""
+    from tests.helpers.so3_cases import quat_case
+    ref = _free_running_imu_mode(turn_seq, 72)
+    # the oracle itself keeps the track (mid-sweep ground truth, aligned on the first pose) and turns all the way round
+    gt = turn_seq.gt_poses(0.5)
+    A, B = np.linalg.inv(gt[0]), np.linalg.inv(ref["res_poses"][0])
+    off = [np.linalg.norm((A @ g)[:3, 3] - (B @ p)[:3, 3]) for g, p in zip(gt, ref["res_poses"])]
+    assert max(off) < 1.0, max(off)
+    yaw = np.unwrap([np.arctan2(p[1, 0], p[0, 0]) for p in ref["res_poses"]])
+    assert yaw.max() - yaw.min() > 2 * np.pi
+    assert {2, 3} <= set(quat_case(ref["res_poses"][:, :3, :3]).tolist())
 
 
 def test_free_running_icp_only_vs_oracle():

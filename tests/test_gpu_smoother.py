@@ -151,6 +151,27 @@ def test_sim_stream_smoother_arithmetic_invariants_and_it_smooths():
     assert s_err < f_err, (s_err, f_err)
 
 
+def test_turn_stream_smoother_arithmetic_and_invariants(golden_dir):
+    """tests/golden/ekf_steps_turn.npz (the attitude passes through all of SO(3), two updates 175 degrees off): the backward pass takes
+    R_to_rotvec / rotvec_to_R of attitudes in every case of R_to_quat - against the restatement at the sim stream's tolerances"""
+    import os
+    from tests.helpers.so3_cases import quat_case, quat_to_R
+    g = np.load(os.path.join(golden_dir, "ekf_steps_turn.npz"))
+    e = core.Ekf()
+    e.enable_smoother(64)
+    upd = {int(i): k for k, i in enumerate(g["upd_idx"])}
+    for i in range(len(g["imu_ts"])):
+        e.process_imu(g["imu_lacc"][i], g["imu_avel"][i], g["imu_ts"][i])
+        if i in upd:
+            e.process_pose(g["upd_pose"][upd[i]])
+    log = e.smoother_log()
+    assert len(log["ts"]) == len(upd) and not log["overflow"]
+    assert np.abs(log["nav_post"][:, :3] - g["nav_after_upd"][:, :3]).max() <= 1e-9
+    assert len(set(quat_case(quat_to_R(log["nav_post"][:, 3:7])))) == 4  # the smoothed epochs themselves take all four cases
+    sm = e.smooth()
+    _check_smoothed(log, sm, "turn")
+
+
 def _resident(seq, n, use_imu, smooth=True, plain=False, **kw):
     """a SeqRunner over seq (plain: configured like one sequence of a BatchRunner, tests/test_gpu_batch.py)"""
     n_imu = seq.imu_range_for_scan(n - 1)[1]

@@ -23,10 +23,20 @@ def _nav_close(a, b, tol=TOL):
     assert np.abs(a[7:] - b[7:]).max() <= tol
 
 
-@pytest.mark.parametrize("variant", ["default", "init", "cov"])
+def test_turn_and_inverted_fixtures_reach_every_quaternion_case(golden_dir):
+    """what ekf_steps_turn / ekf_steps_inverted are for (the other fixtures stay below 48 degrees, the trace case only): together
+    every case of the matrix-to-quaternion conversion at least 20 times, and attitude errors whose quaternion has w < 0"""
+    from tests.helpers.so3_cases import ekf_steps_coverage
+    cov = {v: ekf_steps_coverage(np.load(os.path.join(golden_dir, f"ekf_steps_{v}.npz"))) for v in ("default", "turn", "inverted")}
+    assert list(cov["default"][0][:3]) == [0, 0, 0] and cov["default"][1] == 0
+    assert ((cov["turn"][0] + cov["inverted"][0]) >= 20).all(), cov
+    assert cov["turn"][1] >= 1 and cov["inverted"][1] >= 1 and cov["inverted"][0][0] >= 20, cov
+
+
+@pytest.mark.parametrize("variant", ["default", "init", "cov", "turn", "inverted"])
 def test_ekf_step_by_step(golden_dir, variant):
     g = np.load(os.path.join(golden_dir, f"ekf_steps_{variant}.npz"))
-    default = variant != "init"
+    default = variant not in ("init", "inverted")
     ekf = orc.EKF(None if default else g["init_grav"], None if default else g["init_bacc"],
                   None if default else g["init_bgyr"])
     assert np.abs(ekf.cov - g["cov0"]).max() <= 1e-12

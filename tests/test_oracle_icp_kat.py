@@ -37,6 +37,27 @@ def test_se3_exp_log_roundtrip_and_reference_values():
     w = xi[3:]
     X[:3, :3] = [[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]
     assert np.abs(expm(X) - orc.se3_exp(xi)).max() < 1e-15
+    # 1e-6 <= th < 1e-2, where (1 - cos th) / th^2 used to put 1e-16 / th of |upsilon| into t (4e-11 of it at th = 1e-6; the device has
+    # the same formula, so no comparison with it could see that): against the closed forms in mpmath at 50 digits, |upsilon| to 100 m,
+    # at the bound tests/test_devmath_probe.py asks of csrc/devmath.h se3_exp (4 x its measured 2 x 2^-52)
+    import mpmath as mp
+    mp.mp.dps = 50
+    worst = 0.0
+    for th in [1e-6, 1.1e-6, 2e-6, 5e-6] + [float(a) for a in 10.0 ** np.arange(-6, -2, 0.125)] + [9.99e-3]:
+        for un in (0.1, 2.0, 100.0):
+            u, w = rng.normal(size=3), rng.normal(size=3)
+            xi = np.concatenate([u / np.linalg.norm(u) * un, w / np.linalg.norm(w) * th])
+            wm = [mp.mpf(float(v)) for v in xi[3:]]
+            t = mp.sqrt(sum(v * v for v in wm))
+            K = mp.matrix([[0, -wm[2], wm[1]], [wm[2], 0, -wm[0]], [-wm[1], wm[0], 0]])
+            V = mp.eye(3) + (1 - mp.cos(t)) / t ** 2 * K + (t - mp.sin(t)) / t ** 3 * K * K
+            R = mp.eye(3) + mp.sin(t) / t * K + (1 - mp.cos(t)) / t ** 2 * K * K
+            tv = V * mp.matrix([mp.mpf(float(v)) for v in xi[:3]])
+            T = orc.se3_exp(xi)
+            worst = max(worst, max(abs(float(tv[i]) - T[i, 3]) for i in range(3)) / un,
+                        max(abs(float(R[i, j]) - T[i, j]) for i in range(3) for j in range(3)))
+            assert np.abs(orc.se3_log(T) - xi).max() <= 16 * 2.0 ** -52 * un
+    assert worst <= 8 * 2.0 ** -52, worst
 
 
 def test_voxel_downsample_semantics():
