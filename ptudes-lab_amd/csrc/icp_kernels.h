@@ -1296,20 +1296,23 @@ __device__ __forceinline__ void gn_post(const Ctx& c, DevState* st, bool map_emp
     st->stats_pending = k;
 }
 
-// ---- flag-in-word exchange of the 29 sums (single-sequence GN kernel) -------------------------------------------
+// ---- flag-in-word exchange of the workgroups' sums (both Gauss-Newton kernels) ----------------------------------
 // A double travels as two 8-byte words, each (32 data bits | 32-bit flag); an aligned 8-byte store is single-copy
 // atomic, so a reader that sees the flag sees the data - no acknowledgement wait, no counter, no release word.
 // The flag is unique per (launch, iteration): gn_epoch << 10 | iteration + 1 (never 0; the buffers start zeroed and
 // are zeroed again when the epoch wraps).  Rows are double-buffered by iteration parity: nobody can be two
 // iterations ahead of a reader (a workgroup leaves iteration i only after every leader published i, and a leader
 // publishes only after every one of its members did).
-#define GN_LL_WORDS 64   /* words per row: 58 used */
+#define GN_LL_WORDS 64   /* words per row, two per entry: the 32-lane kernel uses 2 GN32_ROW_ENTRIES = 58, the 8-lane kernel 2 GN8_ROW_ENTRIES = 36 */
+#define GN32_ROW_ENTRIES 29  /* row of the 32-lane kernel = the totals both kernels solve from: 27 sums (21 JTJ upper triangle + 6 JTr), then */
+#define GN_TOT_PAIRS 27      /* the pair count */
+#define GN_TOT_CAND 28       /* and the candidate count */
 #ifndef GN_XSUM_COPIES
 #define GN_XSUM_COPIES 8  /* copies of every group sum (power of two <= 8): consumers are spread over them */
 #endif
 #define GN_LL_SPINS (1u << 22)
 __device__ __forceinline__ unsigned gn_flag(unsigned epoch, int it) { return (epoch << 10) | (unsigned)(it + 1); }
-// word `w` (0..57) of a row holding the doubles vals[0..28]
+// word `w` of a row holding the doubles vals[]
 __device__ __forceinline__ unsigned long long gn_ll_word(const double* vals, int w, unsigned flag) {
     const unsigned long long bits = (unsigned long long)__double_as_longlong(vals[w >> 1]);
     const unsigned half = (w & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
@@ -1346,6 +1349,196 @@ __device__ __forceinline__ double gn_ll_join(unsigned half) {
     return __longlong_as_double((long long)(((unsigned long long)other << 32) | half));  // meaningful in even lanes
 }
 
+// In-kernel phase clocks (tools_phase.py, ptl_icp_gn_phases / ptl_icp_gn_wg_clocks) are compiled in only with
+// -DGN_PHASE_CLOCKS (make PHASES=1): eight 64-bit accumulators and the counter reads otherwise compete with the loop's
+// live values for scalar and vector registers (the 32-lane kernel runs at its 128-VGPR cap and spills).
+#if defined(GN_PHASE_CLOCKS) || defined(GN_IT0_CLOCK)  /* (make IT0=1: only the split first iteration / other iterations of the point loop) */
+#define GN_CLK() ((long long)__builtin_readcyclecounter())
+#else
+#define GN_CLK() (0ll)
+#endif
+
+// ---- what the two persistent Gauss-Newton loops share: gn_loop_body (32 lanes per point, rows of GN32_ROW_ENTRIES) and gn8_body
+// (8 lanes per point, rows of GN8_ROW_ENTRIES) must agree bit for bit on the totals, on dx, on convergence and on the result (a
+// batch member equals its run alone), so the summation order of the exchange, the serial tail, the head and the result store are
+// defined here, once.  E = entries of a row, STRIDE = doubles between two staged rows in LDS; the LDS arrays belong to the bodies
+// (every kernel instance carries its own).
+
+// The head, part 1: false = this workgroup has nothing to do (the result of an empty map is written here).
+// (mode 1, the teacher-forced entry without guess and empty-map result, belongs to the 32-lane kernel: the 8-lane kernel is launched with
+// mode 0 only and has no test of anything else)
+__device__ __forceinline__ bool gn_enter(const Ctx& c, DevState* st, int mode, int wg, int tid) {
+    if (wg == 0 && tid == 0 && mode == 0) flush_map_stats(c, st);  // the previous scan's map update precedes this launch
+    if (st->n_live == 0 && mode != 1) {  // voxel_map.Empty() => return initial_guess
+        if (wg == 0 && tid == 0) {
+            Rt I = rt_identity();
+            rt_to16(I, st->T_icp);
+            st->gn_iters = 0; st->gn_ncorr = 0; st->gn_cand = 0;
+            gn_post(c, st, true, mode == 0);
+        }
+        return false;
+    }
+    return wg != st->dbg_dead_wg;  // test hook: a workgroup that never arrives (exercises the time-out / abort path)
+}
+// The head, part 2: T_icp = identity, the guess as the "increment of iteration -1" (buffer 1 of Esh2), no candidates yet.
+__device__ __forceinline__ void gn_init_pose(const Ctx& c, int mode, int tid, int NT, double* Tsh, double* Esh_guess, long long* cand_total) {
+    if (tid < 12) Tsh[tid] = (tid < 9) ? ((tid % 4 == 0) ? 1.0 : 0.0) : 0.0;
+    if (tid == 64) {
+        // the guess as a Sophus::SE3d would hold it (rotation through a unit quaternion): one lane of the second wavefront
+        Rt g = rt_identity();
+        if (mode != 1) g = rt_project(rt_from16(guess_src(c)));
+        for (int k = 0; k < 9; ++k) Esh_guess[k] = g.R[k];
+        for (int k = 0; k < 3; ++k) Esh_guess[9 + k] = g.t[k];
+    }
+    if (tid == NT - 1) *cand_total = 0;  // (kept out of the registers: only workgroup 0 reads it, after the loop)
+    __syncthreads();
+}
+
+// Staging: 32-lane group `grp` of NG polls row first + step j (of the G rows of parity par) for j = grp, grp + NG, ... < count and
+// leaves its E doubles at stage[j STRIDE ..].  Returns ok, false after a time-out / abort (of any of this lane's rows).
+template <int E, int STRIDE>
+__device__ __forceinline__ bool gn_ll_stage_rows(const unsigned long long* rows_ll, int par, int G, int first, int step, int count, int lane32, int grp,
+                                                 int NG, unsigned flag, double* stage, bool ok, const int* abort_word) {
+    static_assert(E > 16 && E <= 32 && E <= STRIDE, "a row is polled as words lane32 and lane32 + 32 of GN_LL_WORDS");
+    for (int j = grp; j < count; j += NG) {
+        const unsigned long long* row = rows_ll + ((size_t)par * G + (first + step * j)) * GN_LL_WORDS;
+        unsigned h0, h1;
+        gn_ll_wait2(row + lane32, row + lane32 + 32, lane32 + 32 < 2 * E, flag, &h0, &h1, &ok, abort_word);
+        const double v0 = gn_ll_join(h0), v1 = gn_ll_join(h1);
+        if ((lane32 & 1) == 0) {
+            stage[j * STRIDE + (lane32 >> 1)] = v0;
+            if (16 + (lane32 >> 1) < E) stage[j * STRIDE + 16 + (lane32 >> 1)] = v1;
+        }
+    }
+    return ok;
+}
+// THE association of the exchange: members g, g + 8, ... of group g = (workgroup & 7) in member order, then the groups in group
+// order.  One hop: entry e of the total from all G staged rows.
+template <int STRIDE>
+__device__ __forceinline__ double gn_one_hop_sum(const double* stage, int e, int G) {
+    double t = 0.0;
+    if (G == 32) {  // all reads in flight, then the same additions
+        double r[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) r[j] = stage[j * STRIDE + e];
+#pragma unroll
+        for (int g = 0; g < 8; ++g) t += (((0.0 + r[g]) + r[g + 8]) + r[g + 16]) + r[g + 24];
+    } else {
+        for (int g = 0; g < (G < 8 ? G : 8); ++g) {
+            double sg = 0.0;
+            for (int j = g; j < G; j += 8) sg += stage[j * STRIDE + e];
+            t += sg;
+        }
+    }
+    return t;
+}
+// Two hops (one sequence over the whole chip): workgroup row -> the leader of its group -> GN_XSUM_COPIES copies of the group sum
+// -> everybody.  The leaders (wg < 8) stage their members' rows, every 32-lane group one at a time, and add them in member
+// order; then ONE wavefront of every workgroup (lane l <-> word l of a row; lanes 2e, 2e + 1 hold the halves of entry e) polls
+// the group sums addressed to the workgroup's slot and adds them in group order: nothing between the arrival of the last word
+// and the solve needs LDS traffic but the totals in out[0 .. E).  Returns ok (meaningful in the first wavefront) and the phase
+// clocks: the leader's rows are staged | the poll begins | the totals are in; t0 for whoever does not get there.
+struct GnTwoHop {
+    bool ok;
+    long long t_staged, t_poll, t_done;
+};
+template <int E, int STRIDE>
+__device__ __forceinline__ GnTwoHop gn_two_hop(const Ctx& c, int G, int wg, int par, unsigned flag, int tl, int NG, double* stage, double* out,
+                                               bool ok, long long t0) {
+    GnTwoHop x = {ok, t0, t0, t0};
+    DevState* st = c.st;
+    const int lane32 = tl & 31, grp = tl >> 5, ngroups = G < 8 ? G : 8;
+    if (wg < ngroups) {  // leader of group wg: members wg, wg + 8, ...
+        const int nmem = (G - wg + 7) / 8;
+        ok = gn_ll_stage_rows<E, STRIDE>(c.gn_rows_ll, par, G, wg, 8, nmem, lane32, grp, NG, flag, stage, ok, &st->gn_abort);
+        if (!ok) gn_raise_abort(st);
+        __syncthreads();
+        x.t_staged = GN_CLK();
+        if (tl < E) {  // each summing lane publishes both halves of its entry, one copy per consumer slot
+            double s = 0.0;
+            if (nmem == 32) {  // 256 workgroups: all reads in flight, then the same additions in member order
+                double r[32];
+#pragma unroll
+                for (int j = 0; j < 32; ++j) r[j] = stage[j * STRIDE + tl];
+#pragma unroll
+                for (int j = 0; j < 32; ++j) s += r[j];
+            } else {
+                for (int j = 0; j < nmem; ++j) s += stage[j * STRIDE + tl];
+            }
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(s), fl = (unsigned long long)flag << 32;
+            const unsigned long long lo = (bits & 0xFFFFFFFFull) | fl, hi = (bits >> 32) | fl;
+#pragma unroll
+            for (int r = 0; r < GN_XSUM_COPIES; ++r) {
+                unsigned long long* dst = c.gn_xsum_ll + (((size_t)par * 8 + r) * 8 + wg) * GN_LL_WORDS + 2 * tl;
+                __hip_atomic_store(dst, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(dst + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    if (tl < 64) {
+        const bool mine = tl < 2 * E;
+        bool ok2 = true;
+        x.t_poll = GN_CLK();
+        unsigned h[8];
+        unsigned spins = 0;
+        for (;;) {
+            unsigned bad = 0u;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                unsigned long long vv = (unsigned long long)flag << 32;
+                if (mine && g < ngroups)
+                    vv = __hip_atomic_load(c.gn_xsum_ll + (((size_t)par * 8 + (wg & (GN_XSUM_COPIES - 1))) * 8 + g) * GN_LL_WORDS + tl,
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                bad |= (unsigned)(vv >> 32) ^ flag;
+                h[g] = (unsigned)vv;
+            }
+            if (__all(bad == 0u)) break;
+            ++spins;
+            if (spins > GN_LL_SPINS || ((spins & 1023u) == 0u && gn_abort_seen(&st->gn_abort))) { ok2 = false; break; }
+            /* no sleep: nothing else runs in this workgroup while its first wavefront waits for the totals */
+        }
+        double t = 0.0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+            const double v = gn_ll_join(h[g]);
+            if (g < ngroups) t += v;
+        }
+        if (mine && (tl & 1) == 0) out[tl >> 1] = t;
+        if (!ok2 && tl == 0) gn_raise_abort(st);
+        ok = ok && ok2;  // (a staging time-out of this workgroup as a leader counts too)
+        x.t_done = GN_CLK();
+    }
+    x.ok = ok;
+    return x;
+}
+// The serial tail, by the wavefront that holds the totals (tot[0 .. GN32_ROW_ENTRIES) in LDS): 6x6 solve - every lane ends up with
+// the same dx - then lane 0 publishes Exp(dx) in Esh and the convergence flag in *done.  sqrt(|dx|^2) < conv without the square
+// root on the serial path; !ok: the exchange gave up (time-out / abort).  Returns the clock between the solve and Exp.
+__device__ __forceinline__ long long gn_solve_publish(const double* tot, int tl, double conv2, bool ok, double* Esh, int* done) {
+    double dx[6];
+    solve6_ldlt_wave(tot, tl, dx);
+    const long long clk = GN_CLK();
+    if (tl == 0) {
+        const Rt e = se3_exp_gn(dx);
+        for (int k = 0; k < 9; ++k) Esh[k] = e.R[k];
+        for (int k = 0; k < 3; ++k) Esh[9 + k] = e.t[k];
+        double nn = 0.0;
+        for (int k = 0; k < 6; ++k) nn += dx[k] * dx[k];
+        *done = (nn < conv2 || !ok) ? 1 : 0;
+    }
+    return clk;
+}
+// The result, by one lane of workgroup 0 after the loop (the last iteration's totals are still in LDS); gn_post follows
+__device__ __forceinline__ void gn_store_result(DevState* st, const double* Tsh, int iters, const double* tot, long long cand_total) {
+    Rt T;
+    for (int k = 0; k < 9; ++k) T.R[k] = Tsh[k];
+    for (int k = 0; k < 3; ++k) T.t[k] = Tsh[9 + k];
+    rt_to16(T, st->T_icp);
+    st->gn_iters = iters;
+    st->gn_ncorr = iters > 0 ? (int)tot[GN_TOT_PAIRS] : 0;
+    st->gn_cand = cand_total;
+}
+
 // Persistent Gauss-Newton loop (Registration.cpp RegisterFrame).  G workgroups, all resident; per iteration the
 // workgroups' 29 sums meet through the flag-in-word exchange above (rows -> 8 group leaders -> group sums to everybody,
 // fixed summation order), and every workgroup solves the 6x6 system redundantly from the same totals, so all agree
@@ -1354,14 +1547,6 @@ __device__ __forceinline__ double gn_ll_join(unsigned half) {
 // mode 0: a scan: source = guess * src0, loop to convergence, then the post-ICP bookkeeping.
 // mode 1: src_cur given in world frame, one pass, sums exported to st->dbg_sums (teacher-forced entry).
 // mode 2: like 0 without touching the trajectory (ptl_icp_align).
-// In-kernel phase clocks (tools_phase.py, ptl_icp_gn_phases / ptl_icp_gn_wg_clocks) are compiled in only with
-// -DGN_PHASE_CLOCKS (make PHASES=1): eight 64-bit accumulators and the counter reads otherwise compete with the loop's
-// live values for scalar and vector registers (the kernel runs at its 128-VGPR cap and spills).
-#if defined(GN_PHASE_CLOCKS) || defined(GN_IT0_CLOCK)  /* (make IT0=1: only the split first iteration / other iterations of the point loop) */
-#define GN_CLK() ((long long)__builtin_readcyclecounter())
-#else
-#define GN_CLK() (0ll)
-#endif
 #ifndef GN_MAX_THREADS
 #define GN_MAX_THREADS 512
 #endif
@@ -1386,22 +1571,13 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
     __shared__ double scur[GN_MAX_GROUPS][4];
     __shared__ double redL[64][32];  // a leader's member rows (G <= 512)
     __shared__ int flag_done2[2];   // likewise
+    __shared__ long long cand_total_sh;
     DevState* st = c.st;
     const int tid = threadIdx.x, lane32 = tid & 31, grp = tid >> 5, gbase = (tid & 63) & 32;
     const int NG = blockDim.x >> 5;
     const int n = st->n_src;
     const unsigned epoch = st->gn_epoch;
-    if (wg == 0 && tid == 0 && mode == 0) flush_map_stats(c, st);  // the previous scan's map update precedes this launch
-    if (st->n_live == 0 && mode != 1) {  // voxel_map.Empty() => return initial_guess
-        if (wg == 0 && tid == 0) {
-            Rt I = rt_identity();
-            rt_to16(I, st->T_icp);
-            st->gn_iters = 0; st->gn_ncorr = 0; st->gn_cand = 0;
-            gn_post(c, st, true, mode == 0);
-        }
-        return;
-    }
-    if (wg == st->dbg_dead_wg) return;  // test hook: a workgroup that never arrives (exercises the time-out / abort path)
+    if (!gn_enter(c, st, mode, wg, tid)) return;
     const double kern = st->gn_kernel, k2 = kern * kern;
     const double gate2 = sqrt_gate(st->gn_max_dist);  // sqrt(d2) < max_dist  <=>  d2 < gate2
     const double conv2 = sqrt_gate(c.conv);           // likewise for the convergence test on |dx|
@@ -1414,17 +1590,7 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
             for (int b = a; b < 6; ++b) { if (o == lane32) { ia = a; ib = b; } ++o; }
         if (lane32 >= 21) { ia = lane32 - 21; ib = 6; }
     }
-    if (tid < 12) Tsh[tid] = (tid < 9) ? ((tid % 4 == 0) ? 1.0 : 0.0) : 0.0;
-    if (tid == 64) {
-        // the guess as a Sophus::SE3d would hold it (rotation through a unit quaternion): one lane of the second wavefront
-        Rt g = rt_identity();
-        if (mode != 1) g = rt_project(rt_from16(guess_src(c)));
-        for (int k = 0; k < 9; ++k) Esh2[1][k] = g.R[k];
-        for (int k = 0; k < 3; ++k) Esh2[1][9 + k] = g.t[k];
-    }
-    __syncthreads();
-    __shared__ long long cand_total_sh;  // (kept out of the registers: only workgroup 0 reads it, after the loop)
-    if (tid == (int)blockDim.x - 1) cand_total_sh = 0;
+    gn_init_pose(c, mode, tid, (int)blockDim.x, Tsh, Esh2[1], &cand_total_sh);
     int iters = 0;
     long long ph[5] = {0, 0, 0, 0, 0}, ph_wait = 0, ph_x1 = 0, ph_x2 = 0;
     // one point per 32-lane group for the whole loop => its probe results can be cached across iterations
@@ -1487,16 +1653,16 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
                 const V3 r = v3(s.x - t.x, s.y - t.y, s.z - t.z);
                 const double den = kern + (r.x * r.x + r.y * r.y + r.z * r.z);
                 const double w = k2 / (den * den);
-                if (lane32 < 27) acc += w * dot(jcol(ia, s, r), jcol(ib, s, r));
-                else if (lane32 == 27) acc += 1.0;
+                if (lane32 < GN_TOT_PAIRS) acc += w * dot(jcol(ia, s, r), jcol(ib, s, r));
+                else if (lane32 == GN_TOT_PAIRS) acc += 1.0;
             }
         }
         const long long c1 = GN_CLK();
-        // workgroup reduction in fixed order (column 28 carries the candidate count)
+        // workgroup reduction in fixed order (column GN_TOT_CAND carries the candidate count)
         const int ncand0 = group_sum32(ncand);  // sum of the per-lane probe counts over the 32 lanes of the group
         {
             // workgroup reduction, fixed tree: the two groups of a wavefront, then 4 segments of wavefronts, then 4 -> 1
-            const double mine = (lane32 == 28) ? (double)ncand0 : acc;
+            const double mine = (lane32 == GN_TOT_CAND) ? (double)ncand0 : acc;
             const double pair = mine + __shfl_xor(mine, 32);
             if ((tid & 63) < 32) red[tid >> 6][lane32] = pair;
         }
@@ -1506,9 +1672,9 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
         // its members' rows in member order and everybody adds the group sums in group order: the association the
         // counter-barrier version used (8 strided partial sums, then 8 -> 1), bit for bit.
         const unsigned flag = gn_flag(epoch, it);
-        const int par = it & 1, ngroups = G < 8 ? G : 8;
+        const int par = it & 1;
         bool ok = true;
-        if (tid < 58) {
+        if (tid < 2 * GN32_ROW_ENTRIES) {
             // lanes 2e, 2e + 1 of the first wavefront both form entry e of the workgroup's row - the 4 segments of
             // wavefronts, then 4 -> 1, the tree the batched kernel builds through LDS - and store one half each
             const int e = tid >> 1, NW = NG >> 1, per = (NW + 3) >> 2;
@@ -1537,148 +1703,38 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
         if (XL) {
             // one hop: every 32-lane group polls one row of the sequence (all its workgroups, this one included); the
             // first 29 lanes then add them in the two-hop association and hand the totals to the solve
-            for (int j = grp; j < G; j += NG) {
-                const unsigned long long* row = c.gn_rows_ll + ((size_t)par * G + j) * GN_LL_WORDS;
-                unsigned h0, h1;
-                gn_ll_wait2(row + lane32, row + lane32 + 32, lane32 + 32 < 58, flag, &h0, &h1, &ok, &st->gn_abort);
-                const double v0 = gn_ll_join(h0), v1 = gn_ll_join(h1);
-                if ((lane32 & 1) == 0) {
-                    redL[j][lane32 >> 1] = v0;
-                    if (16 + (lane32 >> 1) < 29) redL[j][16 + (lane32 >> 1)] = v1;
-                }
-            }
+            ok = gn_ll_stage_rows<GN32_ROW_ENTRIES, 32>(c.gn_rows_ll, par, G, 0, 1, G, lane32, grp, NG, flag, &redL[0][0], ok, &st->gn_abort);
             if (!ok) gn_raise_abort(st);
             ok = __syncthreads_or(ok ? 0 : 1) == 0;
             ph_x1 += GN_CLK() - c2;
-            if (tid < 29) {
-                double t = 0.0;
-                if (G == 32) {  // all reads in flight, then the additions in (group, member) order
-                    double r[32];
-#pragma unroll
-                    for (int j = 0; j < 32; ++j) r[j] = redL[j][tid];
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) t += (((0.0 + r[g]) + r[g + 8]) + r[g + 16]) + r[g + 24];
-                } else {
-                    for (int g = 0; g < ngroups; ++g) {
-                        double sg = 0.0;
-                        for (int j = g; j < G; j += 8) sg += redL[j][tid];
-                        t += sg;
-                    }
-                }
-                tot[tid] = t;
-            }
+            if (tid < GN32_ROW_ENTRIES) tot[tid] = gn_one_hop_sum<32>(&redL[0][0], tid, G);
             ph_x2 += GN_CLK() - c2;
         } else {
-            if (wg < ngroups) {  // leader of group wg: members wg, wg + 8, ... ; every wavefront takes two of their rows
-                const int nmem = (G - wg + 7) / 8;
-                for (int j = grp; j < nmem; j += NG) {
-                    const unsigned long long* row = c.gn_rows_ll + ((size_t)par * G + (wg + 8 * j)) * GN_LL_WORDS;
-                    unsigned h0, h1;
-                    gn_ll_wait2(row + lane32, row + lane32 + 32, lane32 + 32 < 58, flag, &h0, &h1, &ok, &st->gn_abort);
-                    const double v0 = gn_ll_join(h0), v1 = gn_ll_join(h1);
-                    if ((lane32 & 1) == 0) {
-                        redL[j][lane32 >> 1] = v0;
-                        if (16 + (lane32 >> 1) < 29) redL[j][16 + (lane32 >> 1)] = v1;
-                    }
-                }
-                if (!ok) gn_raise_abort(st);
-                __syncthreads();
-                ph_x1 += GN_CLK() - c2;
-                if (tid < 29) {  // sum in member order; each summing lane publishes both halves of its entry, one copy per consumer slot
-                    double s = 0.0;
-                    if (nmem == 32) {  // 256 workgroups: all reads in flight, then the same additions in member order
-                        double r[32];
-    #pragma unroll
-                        for (int j = 0; j < 32; ++j) r[j] = redL[j][tid];
-    #pragma unroll
-                        for (int j = 0; j < 32; ++j) s += r[j];
-                    } else {
-                        for (int j = 0; j < nmem; ++j) s += redL[j][tid];
-                    }
-                    const unsigned long long bits = (unsigned long long)__double_as_longlong(s), fl = (unsigned long long)flag << 32;
-                    const unsigned long long lo = (bits & 0xFFFFFFFFull) | fl, hi = (bits >> 32) | fl;
-    #pragma unroll
-                    for (int r = 0; r < GN_XSUM_COPIES; ++r) {
-                        unsigned long long* dst = c.gn_xsum_ll + (((size_t)par * 8 + r) * 8 + wg) * GN_LL_WORDS + 2 * tid;
-                        __hip_atomic_store(dst, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(dst + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            }
-            // The group sums are collected by ONE wavefront (lane l <-> word l of a row; lanes 2e, 2e + 1 hold the halves of
-            // entry e): nothing between the arrival of the last word and the solve needs LDS traffic but the 29 totals.
-            if (tid < 64) {
-                const bool mine = tid < 58, even = (tid & 1) == 0;
-                ok = true;
-                ph_x2 += GN_CLK() - c2;
-                // everybody: the group sums addressed to this workgroup's slot, added in group order
-                unsigned h[8];
-                unsigned spins = 0;
-                for (;;) {
-                    unsigned long long vv[8];
-    #pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        vv[g] = (unsigned long long)flag << 32;
-                        if (mine && g < ngroups)
-                            vv[g] = __hip_atomic_load(c.gn_xsum_ll + (((size_t)par * 8 + (wg & (GN_XSUM_COPIES - 1))) * 8 + g) * GN_LL_WORDS + tid,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    unsigned bad = 0u;
-    #pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        bad |= (unsigned)(vv[g] >> 32) ^ flag;
-                        h[g] = (unsigned)vv[g];
-                    }
-                    if (__all(bad == 0u)) break;
-                    if (++spins > GN_LL_SPINS) { ok = false; break; }
-                    /* no sleep: nothing else runs in this workgroup while its first wavefront waits for the totals */
-                }
-                double t = 0.0;
-    #pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    const double v = gn_ll_join(h[g]);
-                    if (g < ngroups) t += v;
-                }
-                if (mine && even) tot[tid >> 1] = t;
-                if (!ok && tid == 0) gn_raise_abort(st);
-            }
+            const GnTwoHop x = gn_two_hop<GN32_ROW_ENTRIES, 32>(c, G, wg, par, flag, tid, NG, &redL[0][0], tot, ok, c2);
+            ok = x.ok;
+            ph_x1 += x.t_staged - c2; ph_x2 += x.t_poll - c2;
         }
         long long c3 = 0, c4 = 0;
         if (tid < 64) {  // the wavefront that collected the totals solves: its own LDS writes are ordered before its reads,
             c3 = c4 = GN_CLK();  // so no workgroup barrier stands between the last arrival and the factorisation
             __builtin_amdgcn_wave_barrier();
-            double dx[6];        // every lane ends up with the same dx, lane 0 publishes
-            solve6_ldlt_wave(tot, tid, dx);
-          if (tid == 0) {
-            const Rt e = se3_exp_gn(dx);
-            for (int k = 0; k < 9; ++k) Esh2[it & 1][k] = e.R[k];
-            for (int k = 0; k < 3; ++k) Esh2[it & 1][9 + k] = e.t[k];
-            double nn = 0.0;
-            for (int k = 0; k < 6; ++k) nn += dx[k] * dx[k];
-            flag_done2[it & 1] = (nn < conv2 || !ok) ? 1 : 0;  // sqrt(nn) < conv, without the square root on the serial path; !ok: the exchange gave up (time-out / abort)
-          }
+            gn_solve_publish(tot, tid, conv2, ok, Esh2[it & 1], &flag_done2[it & 1]);
         }
         __syncthreads();
         const long long c5 = GN_CLK();
         ph[0] += c1 - c0; ph[1] += c2 - c1; ph[2] += c3 - c2; ph[3] += c4 - c3; ph[4] += c5 - c4;
         ph_wait += c1b - c1;
-        if (tid == (int)blockDim.x - 1) cand_total_sh += (long long)tot[28];  // (a lane of the last wavefront: off the serial path)
+        if (tid == (int)blockDim.x - 1) cand_total_sh += (long long)tot[GN_TOT_CAND];  // (a lane of the last wavefront: off the serial path)
         iters = it + 1;
         const int done = flag_done2[it & 1];
-        if (mode == 1 && wg == 0 && tid < 29) st->dbg_sums[tid] = tot[tid];
+        if (mode == 1 && wg == 0 && tid < GN32_ROW_ENTRIES) st->dbg_sums[tid] = tot[tid];
         if (done) break;
     }
     if (tid == 64 && iters > 0) gn_compose(Esh2[(iters - 1) & 1], Tsh);  // the last increment
     __syncthreads();
     if (tid == 0 && c.wg_clk) { c.wg_clk[wg] += ph[0] + ph_wait; c.wg_clk[G + wg] += ph[0]; }  // diagnostic: search phase per workgroup
     if (wg == 0 && tid == 0) {
-        Rt T;
-        for (int k = 0; k < 9; ++k) T.R[k] = Tsh[k];
-        for (int k = 0; k < 3; ++k) T.t[k] = Tsh[9 + k];
-        rt_to16(T, st->T_icp);
-        st->gn_iters = iters;
-        st->gn_ncorr = iters > 0 ? (int)tot[27] : 0;  // the last iteration's totals are still in LDS
-        st->gn_cand = cand_total_sh;
+        gn_store_result(st, Tsh, iters, tot, cand_total_sh);
         for (int k = 0; k < 5; ++k) st->gn_phase_clk[k] += ph[k];
         st->gn_phase_clk[5] += iters;
         st->gn_phase_clk[6] += ph_x1; st->gn_phase_clk[7] += ph_x2;  // part of phase 1 spent waiting for the workgroup's other wavefronts
@@ -2193,31 +2249,14 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
     if (tid < 4) xcnt[tid] = 0u;
     const int n = __builtin_amdgcn_readfirstlane(st->n_src);
     const unsigned epoch = (unsigned)__builtin_amdgcn_readfirstlane((int)st->gn_epoch);
-    if (wg == 0 && tid == 0 && mode == 0) flush_map_stats(c, st);
-    if (st->n_live == 0) {  // voxel_map.Empty() => return initial_guess
-        if (wg == 0 && tid == 0) {
-            Rt I = rt_identity();
-            rt_to16(I, st->T_icp);
-            st->gn_iters = 0; st->gn_ncorr = 0; st->gn_cand = 0;
-            gn_post(c, st, true, mode == 0);
-        }
-        return;
-    }
-    if (wg == st->dbg_dead_wg) return;  // test hook: a workgroup that never arrives
+    if (!gn_enter(c, st, mode, wg, tid)) return;
     // the loop's uniform values sit in scalar registers (they arrive through vector loads: left alone, each would hold a vector
     // register pair for the whole loop - at the 256-register cap that is what gets spilled)
     const double kern = uniform_f64(st->gn_kernel), k2 = uniform_f64(kern * kern);
     const double gate2 = uniform_f64(sqrt_gate(st->gn_max_dist));
     const double conv2 = uniform_f64(sqrt_gate(c.conv));
     const double inv_vs = uniform_f64(1.0 / c.vs);
-    if (tid < 12) Tsh[tid] = (tid < 9) ? ((tid % 4 == 0) ? 1.0 : 0.0) : 0.0;
-    if (tid == 64) {  // the guess as a Sophus::SE3d would hold it (rotation through a unit quaternion)
-        const Rt g = rt_project(rt_from16(guess_src(c)));
-        for (int k = 0; k < 9; ++k) Esh2[1][k] = g.R[k];
-        for (int k = 0; k < 3; ++k) Esh2[1][9 + k] = g.t[k];
-    }
-    if (tid == NT - 1) cand_total_sh = 0;
-    __syncthreads();
+    gn_init_pose(c, mode, tid, NT, Tsh, Esh2[1], &cand_total_sh);
     // The scan's source points are dealt to the workgroups in blocks of 64 consecutive points, round robin: block q of this
     // workgroup is global block q G + wg, a wavefront of phase A takes one block (its loads coalesce), and every workgroup
     // gets an even sample of the scan - the number of points that need a full search is then the same everywhere (with
@@ -2473,7 +2512,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
         }
         __syncthreads();
         const unsigned flag = gn_flag(epoch, it);
-        const int par = it & 1, ngroups = G < 8 ? G : 8;
+        const int par = it & 1;
         bool ok = true;
         if (tl < 2 * GN8_ROW_ENTRIES) {
             const int e = tl >> 1;
@@ -2521,89 +2560,17 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                 c3 = GN_CLK();
             }
         } else if (G <= 64) {
-            for (int j = grp32; j < G; j += NG32) {
-                const unsigned long long* row = c.gn_rows_ll + ((size_t)par * G + j) * GN_LL_WORDS;
-                unsigned h0, h1;
-                gn_ll_wait2(row + lane32, row + lane32 + 32, lane32 + 32 < 2 * GN8_ROW_ENTRIES, flag, &h0, &h1, &ok, &st->gn_abort);
-                const double v0 = gn_ll_join(h0), v1 = gn_ll_join(h1);
-                if ((lane32 & 1) == 0) {
-                    redL8[j][lane32 >> 1] = v0;
-                    if (16 + (lane32 >> 1) < GN8_ROW_ENTRIES) redL8[j][16 + (lane32 >> 1)] = v1;
-                }
-            }
+            ok = gn_ll_stage_rows<GN8_ROW_ENTRIES, GN8_ROW_ENTRIES>(c.gn_rows_ll, par, G, 0, 1, G, lane32, grp32, NG32, flag, &redL8[0][0], ok,
+                                                                    &st->gn_abort);
             if (!ok) gn_raise_abort(st);
             ok = __syncthreads_or(ok ? 0 : 1) == 0;
             c3 = GN_CLK();
-            if (tl < GN8_ROW_ENTRIES) {
-                double t = 0.0;
-                for (int g = 0; g < ngroups; ++g) {
-                    double sg = 0.0;
-                    for (int j = g; j < G; j += 8) sg += redL8[j][tl];
-                    t += sg;
-                }
-                mom[tl] = t;
-            }
+            if (tl < GN8_ROW_ENTRIES) mom[tl] = gn_one_hop_sum<GN8_ROW_ENTRIES>(&redL8[0][0], tl, G);
         } else {
-            // one sequence over the whole chip (G up to 512): the two-hop exchange of the 32-lane kernel - rows -> the
-            // leader of each group (wg & 7) -> 8 group sums to every consumer slot - with this kernel's 18-entry rows
-            if (wg < ngroups) {
-                const int nmem = (G - wg + 7) / 8;
-                for (int j = grp32; j < nmem; j += NG32) {
-                    const unsigned long long* row = c.gn_rows_ll + ((size_t)par * G + (wg + 8 * j)) * GN_LL_WORDS;
-                    unsigned h0, h1;
-                    gn_ll_wait2(row + lane32, row + lane32 + 32, lane32 + 32 < 2 * GN8_ROW_ENTRIES, flag, &h0, &h1, &ok, &st->gn_abort);
-                    const double v0 = gn_ll_join(h0), v1 = gn_ll_join(h1);
-                    if ((lane32 & 1) == 0) {
-                        redL8[j][lane32 >> 1] = v0;
-                        if (16 + (lane32 >> 1) < GN8_ROW_ENTRIES) redL8[j][16 + (lane32 >> 1)] = v1;
-                    }
-                }
-                if (!ok) gn_raise_abort(st);
-                __syncthreads();
-                if (tl < GN8_ROW_ENTRIES) {  // sum in member order; both halves of the entry to every consumer slot
-                    double sm = 0.0;
-                    for (int j = 0; j < nmem; ++j) sm += redL8[j][tl];
-                    const unsigned long long bits = (unsigned long long)__double_as_longlong(sm), fl = (unsigned long long)flag << 32;
-                    const unsigned long long lo = (bits & 0xFFFFFFFFull) | fl, hi = (bits >> 32) | fl;
-#pragma unroll
-                    for (int r = 0; r < GN_XSUM_COPIES; ++r) {
-                        unsigned long long* dst = c.gn_xsum_ll + (((size_t)par * 8 + r) * 8 + wg) * GN_LL_WORDS + 2 * tl;
-                        __hip_atomic_store(dst, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(dst + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            }
-            if (tl < 64) {  // everybody: the group sums addressed to this workgroup's slot, added in group order
-                const bool mine = tl < 2 * GN8_ROW_ENTRIES;
-                bool ok2 = true;
-                unsigned h[8];
-                unsigned spins = 0;
-                for (;;) {
-                    unsigned bad = 0u;
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        unsigned long long vv = (unsigned long long)flag << 32;
-                        if (mine && g < ngroups)
-                            vv = __hip_atomic_load(c.gn_xsum_ll + (((size_t)par * 8 + (wg & (GN_XSUM_COPIES - 1))) * 8 + g) * GN_LL_WORDS + tl,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        bad |= (unsigned)(vv >> 32) ^ flag;
-                        h[g] = (unsigned)vv;
-                    }
-                    if (__all(bad == 0u)) break;
-                    ++spins;
-                    if (spins > GN_LL_SPINS || ((spins & 1023u) == 0u && gn_abort_seen(&st->gn_abort))) { ok2 = false; break; }
-                }
-                double t = 0.0;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    const double v = gn_ll_join(h[g]);
-                    if (g < ngroups) t += v;
-                }
-                if (mine && (tl & 1) == 0) mom[tl >> 1] = t;
-                if (!ok2 && tl == 0) gn_raise_abort(st);
-                ok = ok && ok2;
-                c3 = GN_CLK();
-            }
+            // one sequence over the whole chip (G up to 512): the two-hop exchange, with this kernel's 18-entry rows
+            const GnTwoHop x = gn_two_hop<GN8_ROW_ENTRIES, GN8_ROW_ENTRIES>(c, G, wg, par, flag, tl, NG32, &redL8[0][0], mom, ok, c2);
+            ok = x.ok;
+            c3 = x.t_done;
         }
         if (tl < 64) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2614,28 +2581,16 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                 double mm[GN8_ROW_ENTRIES];
 #pragma unroll
                 for (int e = 0; e < GN8_ROW_ENTRIES; ++e) mm[e] = mom[e];
-                if (tl < 27) tot[tl] = sums_from_moments(tl, mm);
-                else if (tl == 27) tot[27] = mm[16];
-                else if (tl == 28) tot[28] = mm[17];
+                if (tl < GN_TOT_PAIRS) tot[tl] = sums_from_moments(tl, mm);
+                else if (tl == GN_TOT_PAIRS) tot[GN_TOT_PAIRS] = mm[16];
+                else if (tl == GN_TOT_CAND) tot[GN_TOT_CAND] = mm[17];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
 #ifdef GN_PHASE_CLOCKS
             const long long s1 = GN_CLK();
 #endif
-            double dx[6];
-            solve6_ldlt_wave(tot, tl, dx);
-#ifdef GN_PHASE_CLOCKS
-            const long long s2 = GN_CLK();
-#endif
-            if (tl == 0) {
-                const Rt e = se3_exp_gn(dx);
-                for (int k = 0; k < 9; ++k) Esh2[it & 1][k] = e.R[k];
-                for (int k = 0; k < 3; ++k) Esh2[it & 1][9 + k] = e.t[k];
-                double nn = 0.0;
-                for (int k = 0; k < 6; ++k) nn += dx[k] * dx[k];
-                flag_done2[it & 1] = (nn < conv2 || !ok) ? 1 : 0;
-            }
+            [[maybe_unused]] const long long s2 = gn_solve_publish(tot, tl, conv2, ok, Esh2[it & 1], &flag_done2[it & 1]);
 #ifdef GN_PHASE_CLOCKS
             if (tl == 0 && wg == 0) { const long long s3 = GN_CLK(); atomicAdd((unsigned long long*)&c.wg_clk[67], (unsigned long long)(s1 - c3)); atomicAdd((unsigned long long*)&c.wg_clk[68], (unsigned long long)(s2 - s1));
                                        atomicAdd((unsigned long long*)&c.wg_clk[69], (unsigned long long)(s3 - s2)); atomicAdd((unsigned long long*)&c.wg_clk[70], 1ull); }
@@ -2647,7 +2602,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
 #if defined(GN_PHASE_CLOCKS) || defined(GN_IT0_CLOCK)
         if (tl == 0 && wg == 0) atomicAdd((unsigned long long*)&c.wg_clk[52 + (it == 0 ? 0 : 1)], (unsigned long long)(c1 - c0));  // point loop of the first iteration / of the others
 #endif
-        if (tl == NT - 1) cand_total_sh += (long long)tot[28];
+        if (tl == NT - 1) cand_total_sh += (long long)tot[GN_TOT_CAND];
         iters = it + 1;
         if (flag_done2[it & 1]) break;
     }
@@ -2657,13 +2612,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
     if (tid < 3 && xcnt[tid]) atomicAdd(&st->exec_cnt[tid], (unsigned long long)xcnt[tid]);  // (integer sums: any order gives the same totals)
     if (tid == 3 && xcnt[3]) atomicAdd(&st->empty_cnt, (unsigned long long)xcnt[3]);
     if (wg == 0 && tid == 0) {
-        Rt T;
-        for (int k = 0; k < 9; ++k) T.R[k] = Tsh[k];
-        for (int k = 0; k < 3; ++k) T.t[k] = Tsh[9 + k];
-        rt_to16(T, st->T_icp);
-        st->gn_iters = iters;
-        st->gn_ncorr = iters > 0 ? (int)tot[27] : 0;
-        st->gn_cand = cand_total_sh;
+        gn_store_result(st, Tsh, iters, tot, cand_total_sh);
         st->exec_cnt[3] += (unsigned long long)iters;
         st->exec_cnt[6] += (unsigned long long)iters * (unsigned long long)n;
         st->exec_cnt[7] += 1ull;
