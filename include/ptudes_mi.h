@@ -528,6 +528,36 @@ int ptl_batch_upload_sweep_times(ptl_batch *b, int32_t seq, const double *t0t1);
 int ptl_batch_deskew_modes(ptl_batch *b, int32_t seq, int32_t *modes, int64_t max_n, int64_t *n);
 int ptl_batch_knots(ptl_batch *b, int32_t seq, double *knots, int64_t max_knots, int64_t *n_knots, int32_t *overflow);
 
+/* ------------------------------------------------------------------------------------------------
+ * Posed scans into the world map (reference cli/flyby.py:71-131, utils.py:344-392, fly.py:75-111).  Every lidar column gets
+ * its pose on a time-stamped trajectory, the sweep is de-warped with them and its returns are added to the voxel map of a ptl_icp used as a
+ * map container (like ptl_icp_map_add) - on the device, in scan order: the result equals ptl_traj_poses_at -> ptl_lut_dewarp -> the rows
+ * with a return -> ptl_icp_map_add bit for bit (one definition of the arithmetic, csrc/fly_kernels.h), without the two trips through the host.
+ * A scan with ANY column outside [first knot - bound_before, last knot + bound_after] is skipped as a whole (reference utils.py:379-384).
+ * Work buffers are the map handle's (nothing is allocated per scan, a runner is only read); map, trajectory, LUT and runner on one device
+ * (else PTL_ERR_ARG); W = the map handle's scan_cols and H W <= its max_points_per_scan (else PTL_ERR_CAPACITY); pool / table exhaustion
+ * is reported as ptl_icp_map_add reports it.  Per scan 8 bytes (count, flag) come back beside that error word; a multi-scan build
+ * reads its two totals once, at its end. */
+typedef struct ptl_traj ptl_traj; /* a time-stamped trajectory resident on a device */
+/* validation as ptl_traj_poses_at (>= 2 knots, strictly increasing: PTL_ERR_ARG naming the knot), BEFORE any HIP call */
+int ptl_traj_create(int device_id, const double *knot_ts, const double *knot_poses16, int64_t n_knots, double bound_before,
+                    double bound_after, ptl_traj **out);
+int ptl_traj_destroy(ptl_traj *t);
+/* one posed scan: a range image with its LUT, or H x W f32 xyz in the sensor frame with (0,0,0) = no return; col_ts: W seconds.
+ * *n_valid = returns added (nullable), *skipped = 1 when a column lay outside the bounds and nothing was added (nullable) */
+int ptl_icp_map_add_posed_range(ptl_icp *map, ptl_traj *t, ptl_lut *lut, const uint32_t *range_mm, const double *col_ts,
+                                int64_t *n_valid, int32_t *skipped);
+int ptl_icp_map_add_posed_xyz(ptl_icp *map, ptl_traj *t, const float *xyz, int32_t H, int32_t W, const double *col_ts,
+                              int64_t *n_valid, int32_t *skipped);
+/* the RESIDENT sweeps [first, last] of a runner, no sweep crosses the bus: column j of sweep k fires at
+ * t0t1[2k] + (j / W)(t0t1[2k+1] - t0t1[2k]) (the IMU deskew's convention above); t0t1: n_scans x 2, host.  Waits for the runner's own
+ * streams first and never writes to the runner (its later scans are bit-identical).  PTL_ERR_STATE: range images without a LUT, a batch
+ * with a sweep ring (resident_scans: its sweeps are gone).  One sequence per call (a map handle is 0.5 GB at the defaults). */
+int ptl_seq_map_build(ptl_seq *s, ptl_icp *map, ptl_traj *t, const double *t0t1, int64_t first, int64_t last, int64_t *n_valid,
+                      int64_t *n_skipped);
+int ptl_batch_map_build(ptl_batch *b, int32_t seq, ptl_icp *map, ptl_traj *t, const double *t0t1, int64_t first, int64_t last,
+                        int64_t *n_valid, int64_t *n_skipped);
+
 #ifdef __cplusplus
 }
 #endif

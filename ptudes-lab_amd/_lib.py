@@ -169,6 +169,13 @@ PROTOTYPES = {
     "ptl_batch_upload_sweep_times": (C.c_int, [_vp, C.c_int32, c_d_p]),
     "ptl_batch_deskew_modes": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, c_i64_p]),
     "ptl_batch_knots": (C.c_int, [_vp, C.c_int32, c_d_p, C.c_int64, c_i64_p, C.POINTER(C.c_int32)]),
+    # posed scans into the world map (include/ptudes_mi.h)
+    "ptl_traj_create": (C.c_int, [C.c_int, c_d_p, c_d_p, C.c_int64, C.c_double, C.c_double, _vpp]),
+    "ptl_traj_destroy": (C.c_int, [_vp]),
+    "ptl_icp_map_add_posed_range": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32), c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_icp_map_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_seq_map_build": (C.c_int, [_vp, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    "ptl_batch_map_build": (C.c_int, [_vp, C.c_int32, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -199,6 +199,39 @@ def _synthetic_source(seed: int, n_scans: int):
     return seq, meta, synthetic_events(seq)
 
 
+MAP_VOXEL_SIZE = 0.5
+MAP_TIME_BOUNDS = 1.5  # as the fly-by's pose_scans_from_nc_gt (reference utils.py:368)
+
+
+def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
+    """The world map of sweeps [first, n_scans) of a synthetic sequence under the trajectory `knots` [(ts, pose)]: the sweeps are
+    uploaded once and the map is built where they lie (SeqRunner.build_map), every column at its own pose, bounds 1.5 s.
+    Returns (map points (N, 3), voxels, n_skipped)."""
+    from .. import core
+    from ..sequence import sweep_times
+    traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
+    n = seq.n_scans
+    runner = core.SeqRunner(n, seq.H * seq.W, 0, with_ekf=False, device_id=device_id, scan_cols=seq.W)
+    for k in range(first, n):
+        runner.upload_scan(k, seq.scan(k))
+    map_icp = core.Icp(1.0e9, 0.0, voxel_size=voxel_size, scan_cols=seq.W, max_points_per_scan=seq.H * seq.W, device_id=device_id,
+                       map_block_capacity=1 << 21, map_table_capacity=1 << 23)
+    _, n_skipped = runner.build_map(map_icp, traj, sweep_times(seq), first=first)
+    voxels, _ = map_icp.map_size()
+    pts = map_icp.map_points()
+    for h in (runner, map_icp, traj):
+        h.close()
+    return pts, voxels, n_skipped
+
+
+def _save_run_map(path, seq, first, rows_t, rows_p):
+    """... under the rows as the poses file holds them (utils.nc_gt_file_rows): what `flyby --nc-gt-poses` of that file works with"""
+    from ..utils import nc_gt_file_rows, save_map_ply
+    pts, voxels, n_skipped = run_map(seq, first, nc_gt_file_rows(rows_t, rows_p))
+    save_map_ply(path, pts)
+    return voxels, len(pts), n_skipped
+
+
 @click.command(name="ouster")
 @click.argument("file", required=False, type=click.Path())
 @click.option("-m", "--meta", required=False, type=click.Path(exists=True, dir_okay=False, readable=True),
@@ -231,15 +264,26 @@ def _synthetic_source(seed: int, n_scans: int):
               help="deskew every sweep with the filter's IMU-propagated trajectory instead of KissICP's constant-velocity model "
                    "(the fused loop only; the call-by-call form, e.g. with -p, stays constant-velocity); needs --synthetic: "
                    "the sweep times of real recordings are not decoded here")
+@click.option("--save-map", required=False, type=click.Path(dir_okay=False),
+              help="after the run, build the world map of the sweeps (voxel size 0.5) with the poses of --map-from as they stand in the "
+                   "poses file, every column at its own pose, and write its points to this file (PLY, or .npy); needs --synthetic: "
+                   "the sweep times of real recordings are not decoded here")
+@click.option("--map-from", type=click.Choice(["filter", "kiss", "smoothed"]), default="filter",
+              help="trajectory of --save-map: the filter's poses (default), KissICP's own, or the RTS smoothed ones "
+                   "(needs --save-smoothed-poses)")
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
                       kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None,
-                      imu_deskew: bool = False) -> None:
+                      imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter") -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
     from ..utils import TrajectoryEvaluator, active_beam_rows
+    if save_map and synthetic is None:
+        raise click.ClickException("--save-map needs --synthetic: the sweep times of real recordings are not decoded here")
+    if save_map and map_from == "smoothed" and not save_smoothed_poses:
+        raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
         raise click.ClickException("--imu-deskew needs --synthetic and the fused loop (no -p)")
     if not gt_file and use_gt_guess:  # reference :416-418
@@ -340,6 +384,12 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                 pose0 = sm_m[0] @ np.linalg.inv(gts_m[0][1])
                 ate_rot, ate_trans = calc_ate(sm_m, [pose0 @ g[1] for g in gts_m])
                 print(f"ATE of the RTS smoothed poses ({len(gts_m)} poses): rot {ate_rot:.04f} deg, trans {ate_trans:.04f} m")
+    if save_map:
+        rows_t, rows_p = {"filter": (res_t, res_poses), "kiss": (res_t, kiss_poses),
+                          "smoothed": (out.get("smoothed_t"), out.get("smoothed_poses"))}[map_from]
+        voxels, points, n_skipped = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p))
+        print(f"Map of scans {start_scan} - {seq.n_scans - 1} ({map_from} poses, {n_skipped} skipped): {voxels} voxels, {points} points")
+        print(f"Map saved to: {save_map}")
     tm = out["timings"]
     if tm["n_imu"] and tm["n_corr"]:  # reference :590-595
         print("\nTimings:")

@@ -2,6 +2,7 @@
 import click
 
 from .ekf_bench import ptudes_ekf_bench
+from .flyby import ptudes_flyby
 from .stat import ptudes_stat
 
 
@@ -12,6 +13,7 @@ def ptudes_cli() -> None:
 
 ptudes_cli.add_command(ptudes_ekf_bench)
 ptudes_cli.add_command(ptudes_stat)
+ptudes_cli.add_command(ptudes_flyby)
 
 
 def main():

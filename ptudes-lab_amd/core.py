@@ -157,6 +157,33 @@ class Icp:
         L.check(L.lib().ptl_icp_map_add(self._h, L.dptr(x), len(x), None if o is None else L.dptr(o),
                                         0 if o is None else 1))
 
+    def map_add_posed(self, traj, col_ts, range_mm=None, lut=None, xyz=None, H=None):
+        """one posed scan into the map, on the device (include/ptudes_mi.h ptl_icp_map_add_posed_*): every column gets its pose on `traj`
+        at col_ts (W seconds), the sweep - a range image with its `lut`, or (H, W, 3) f32 `xyz` in the sensor frame with (0,0,0) = no
+        return - is de-warped and its returns are added in scan order.  Returns (n_valid, skipped): a scan with a column outside the
+        trajectory's bounds adds nothing"""
+        t = L.as_f64(col_ts).reshape(-1)
+        nv, sk = C.c_int64(), C.c_int32()
+        if (range_mm is None) == (xyz is None):
+            raise ValueError("give range_mm (with lut) or xyz")
+        if range_mm is not None:
+            if lut is None:
+                raise ValueError("a range image needs its lut")
+            r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+            if r.size != lut.H * lut.W or len(t) != lut.W:
+                raise ValueError("need an H x W range image and one time per column")
+            L.check(L.lib().ptl_icp_map_add_posed_range(self._h, traj._h, lut._h, r.ctypes.data_as(C.POINTER(C.c_uint32)), L.dptr(t),
+                                                        C.byref(nv), C.byref(sk)))
+        else:
+            x = np.ascontiguousarray(xyz, dtype=np.float32)
+            W = len(t)
+            H = int(H) if H is not None else x.size // (3 * max(W, 1))
+            if x.size != H * W * 3:
+                raise ValueError("need H x W x 3 points and one time per column")
+            L.check(L.lib().ptl_icp_map_add_posed_xyz(self._h, traj._h, x.ctypes.data_as(C.POINTER(C.c_float)), H, W, L.dptr(t),
+                                                      C.byref(nv), C.byref(sk)))
+        return nv.value, bool(sk.value)
+
     def linear_system(self, src_world, max_dist, kernel):
         s = L.as_f64(src_world)
         sums = np.empty(27)
@@ -229,6 +256,27 @@ def traj_poses_at(knot_ts, knot_poses, ts, bound_before=0.0, bound_after=0.0, de
     L.check(L.lib().ptl_traj_poses_at(device_id, L.dptr(kt), L.dptr(kp), len(kt), float(bound_before), float(bound_after),
                                       L.dptr(t), len(t), L.dptr(out), C.byref(nout)))
     return out, nout.value
+
+
+class Traj:
+    """A time-stamped trajectory resident on a device (include/ptudes_mi.h ptl_traj): knots (ts, 4x4 pose), the end segments extended by
+    bound_before / bound_after seconds - TrajectoryEvaluator's knots kept in HBM for the posed-scan entry points"""
+
+    def __init__(self, knot_ts, knot_poses, bound_before=0.0, bound_after=0.0, device_id=0):
+        kt, kp = L.as_f64(knot_ts).reshape(-1), L.as_f64(knot_poses).reshape(-1, 16)
+        if len(kt) != len(kp):
+            raise ValueError("one pose per knot timestamp")
+        self.n_knots, self.bounds, self.device_id = len(kt), (float(bound_before), float(bound_after)), int(device_id)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_traj_create(int(device_id), L.dptr(kt), L.dptr(kp), len(kt), float(bound_before), float(bound_after),
+                                        C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_traj_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 class Ekf:
@@ -515,6 +563,13 @@ class _Runner:
         L.check(self._c("profile")(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
+    def _build_map(self, call, map_icp, traj, t0t1, first, last):
+        t = _sweep_times(t0t1, self.n_scans)
+        last = self.n_scans - 1 if last is None else int(last)
+        nv, ns = C.c_int64(), C.c_int64()
+        L.check(call(map_icp._h, traj._h, L.dptr(t), int(first), last, C.byref(nv), C.byref(ns)))
+        return nv.value, ns.value
+
     def enable_smoother(self, on=True):
         """log the filter history of every sequence (capacity n_scans each) for smooth(); include/ptudes_mi.h ptl_*_smoother_enable"""
         L.check(self._c("smoother_enable")(self._h, int(bool(on))))
@@ -544,6 +599,12 @@ class SeqRunner(_Runner):
 
     def knots(self):
         return _knots(self.knot_capacity, lambda p, m, n, o: L.lib().ptl_seq_knots(self._h, p, m, n, o))
+
+    def build_map(self, map_icp, traj, t0t1, first=0, last=None):
+        """the world map of the RESIDENT sweeps [first, last] into `map_icp` (an Icp used as a map container), posed by `traj`: column j of
+        sweep k fires at t0 + (j / W)(t1 - t0) of t0t1[k].  No sweep crosses the bus and the runner is only read.  Returns
+        (n_valid, n_skipped); include/ptudes_mi.h ptl_seq_map_build"""
+        return self._build_map(lambda *a: L.lib().ptl_seq_map_build(self._h, *a), map_icp, traj, t0t1, first, last)
 
     def upload_scan(self, k, xyz_f32):
         L.check(L.lib().ptl_seq_upload_scan(self._h, k, _scan_f32(self.cfg, xyz_f32)))
@@ -662,6 +723,10 @@ class BatchRunner(_Runner):
         v = C.c_int32()
         L.check(L.lib().ptl_batch_debug_set_map_points_per_thread(self._h, int(points), C.byref(v)))
         return v.value
+
+    def build_map(self, s, map_icp, traj, t0t1, first=0, last=None):
+        """SeqRunner.build_map for sequence s of the batch (refused with a sweep ring: its sweeps are gone); ptl_batch_map_build"""
+        return self._build_map(lambda *a: L.lib().ptl_batch_map_build(self._h, int(s), *a), map_icp, traj, t0t1, first, last)
 
     def upload_scan(self, s, k, xyz_f32):
         L.check(L.lib().ptl_batch_upload_scan(self._h, s, k, _scan_f32(self.cfg, xyz_f32)))

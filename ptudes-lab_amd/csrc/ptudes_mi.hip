@@ -6,6 +6,7 @@
 #include "ekf_kernels.h"
 #include "icp_kernels.h"
 #include "seq_kernel.h"
+#include "fly_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -118,6 +119,7 @@ struct ptl_icp {
     int64_t dk_cap;
     bool dk_wired;                   // the device state holds the IMU deskew's wiring: the prologue runs its IMU instance
     std::vector<signed char> dk_rec; // per registered scan (icp_enqueue_scan): its deskew mode, or -1 = IMU-wired (the device recorded it)
+    FlyWs* d_fly = nullptr;          // posed scans into the map (fly_kernels.h): count, flag and totals, allocated by the first such call
 };
 
 extern "C" int ptl_icp_default_cfg(ptl_icp_cfg* cfg, double max_range, double min_range) {
@@ -159,7 +161,7 @@ static int icp_free(ptl_icp* h) {
     Ctx& c = h->c;
     void* ptrs[] = {c.pts, c.slot1, c.slot2, c.vtab1, c.vtab2, c.bcnt1, c.bcnt2, h->fd_buf[0], h->fd_buf[1], c.src0,
                     c.src_cur, c.fdw, c.coltab, c.pslot, c.nxt, c.prank, c.plen, c.tab, c.blocks, c.bhdr, c.bfirst, c.free_stack, c.free_stack_s, c.mig_list, c.wg_clk, c.pc_key, c.pc_pb, c.pc_ans, c.gn_rows_ll, c.gn_xsum_ll,
-                    c.st, c.traj, c.sstats, h->d_in, h->d_t01, h->d_ext, h->d_counter, h->d_row_mask, h->dk_t0t1, h->dk_modes};
+                    c.st, c.traj, c.sstats, h->d_in, h->d_t01, h->d_ext, h->d_counter, h->d_row_mask, h->dk_t0t1, h->dk_modes, h->d_fly};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -947,34 +949,19 @@ extern "C" int ptl_icp_register_range(ptl_icp* h, ptl_lut* lut, const uint32_t* 
 }
 
 // ------------------------------------------------------------------------------------------------ posed scans (flyby)
-// Poses along a time-stamped trajectory == ouster.sdk.pose_util.TrajectoryEvaluator as the reference uses it
-// (utils.py:344-392 pose_scans_from_nc_gt, time_bounds = 1.5; cli/ekf_bench.py:489, :537 --use-gt-guess, time_bounds = 1.0;
-// third-party, [UPSTREAM-KNOWLEDGE]): between the knots (t_i, P_i) that bracket ts the pose is the SE(3) geodesic
-//   P(ts) = P_i Exp(alpha Log(P_i^-1 P_i+1)),  alpha = (ts - t_i) / (t_i+1 - t_i);
-// up to `before` / `after` seconds outside the knots the first / last segment is extended (alpha < 0 / > 1); further out
-// is an error (the reference skips such scans, utils.py:382-384).  One thread per timestamp, binary search for the segment.
+// Poses along a time-stamped trajectory (fly_kernels.h d_traj_pose_at); a timestamp outside the bounds gets the identity and is counted.
+// One thread per timestamp.
 __global__ __launch_bounds__(256) void k_traj_poses_at(const double* kt, const double* kp, int n, double before, double after,
                                                        const double* ts, int m, double* out, int* n_outside) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
-    const double t = ts[j];
-    if (!(t >= kt[0] - before) || !(t <= kt[n - 1] + after)) {
+    Rt P;
+    if (!d_traj_pose_at(kt, kp, n, before, after, ts[j], &P)) {
         atomicAdd(n_outside, 1);
         for (int k = 0; k < 16; ++k) out[16 * (size_t)j + k] = (k % 5 == 0) ? 1.0 : 0.0;
         return;
     }
-    int lo = 0, hi = n - 1;  // largest i with kt[i] <= t, clamped to a valid segment start
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (kt[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int i = lo < n - 1 ? lo : n - 2;
-    const double alpha = (t - kt[i]) / (kt[i + 1] - kt[i]);
-    const Rt P0 = rt_from16(kp + 16 * (size_t)i), P1 = rt_from16(kp + 16 * (size_t)(i + 1));
-    double xi[6];
-    se3_log(rt_mul(rt_inv(P0), P1), xi);
-    for (int k = 0; k < 6; ++k) xi[k] *= alpha;
-    rt_to16(rt_mul(P0, se3_exp(xi)), out + 16 * (size_t)j);
+    rt_to16(P, out + 16 * (size_t)j);
 }
 extern "C" int ptl_traj_poses_at(int device_id, const double* knot_ts, const double* knot_poses16, int64_t n_knots,
                                  double bound_before, double bound_after, const double* ts, int64_t n, double* poses16_out,
@@ -1011,18 +998,20 @@ extern "C" int ptl_traj_poses_at(int device_id, const double* knot_ts, const dou
 }
 // ouster client.dewarp(XYZLut(scan), column_poses = scan.pose) (what ScansAccumulator does with a posed scan, reference
 // fly.py:75-86): pixel (u, v) -> R_v (range dir + off) + t_v with the pose of ITS column.  As upstream, pixels without a
-// return (range 0 -> xyz 0) land on their column's sensor origin; n_valid counts the others.
+// return (range 0 -> xyz 0) land on their column's sensor origin; n_valid counts the others.  The arithmetic: fly_kernels.h.
 __global__ __launch_bounds__(256) void k_dewarp(int H, int W, const unsigned* range, const double* dir, const double* off,
                                                 const double* col_poses, double* xyz, int* n_valid) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool valid = false;
     if (i < H * W) {
         const unsigned rg = range[i];
-        const double r = (double)rg;
-        const double* P = col_poses + 16 * (size_t)(i % W);
-        double p[3];
-        for (int k = 0; k < 3; ++k) p[k] = rg ? r * dir[3 * (size_t)i + k] + off[3 * (size_t)i + k] : 0.0;
-        for (int k = 0; k < 3; ++k) xyz[3 * (size_t)i + k] = ((P[4 * k] * p[0] + P[4 * k + 1] * p[1]) + P[4 * k + 2] * p[2]) + P[4 * k + 3];
+        const Rt P = rt_from16(col_poses + 16 * (size_t)(i % W));
+        double p[3], M[12], w[3];
+        for (int k = 0; k < 9; ++k) M[k] = P.R[k];
+        for (int k = 0; k < 3; ++k) M[9 + k] = P.t[k];
+        d_lut_pixel(rg, dir, off, (size_t)i, p);
+        d_pose_pixel(M, p, w);
+        for (int k = 0; k < 3; ++k) xyz[3 * (size_t)i + k] = w[k];
         valid = rg != 0;
     }
     const int nv = __syncthreads_count(valid ? 1 : 0);
@@ -2910,4 +2899,163 @@ extern "C" int ptl_batch_gather_trajectories(ptl_batch* b, ptl_comm* c, double* 
     const int rc = ptl_gather_trajectories(c, d_rows, S, T, counts.data(), rows_out, counts_out);
     (void)hipFree(d_rows);
     return rc;
+}
+
+// ================================================================================================ posed scans into the map
+// The world map of a run, built on the device: a trajectory resident as knots, sweeps taken from where they already are (the caller's
+// host buffer once, or a runner's resident slots), every pass on the MAP handle's stream and in the map handle's buffers (fly_kernels.h).
+struct ptl_traj {
+    int device_id;  // (first member: the one-device rule is tested by changing it)
+    int n;
+    double *d_kt, *d_kp;
+    double before, after;
+};
+extern "C" int ptl_traj_create(int device_id, const double* knot_ts, const double* knot_poses16, int64_t n_knots, double bound_before,
+                               double bound_after, ptl_traj** out) {
+    if (!knot_ts || !knot_poses16 || !out) return set_err(PTL_ERR_ARG, "null argument");
+    if (n_knots < 2) return set_err(PTL_ERR_ARG, "a trajectory needs >= 2 knots (%lld given: knot %lld is missing)", (long long)n_knots, (long long)(n_knots < 0 ? 0 : n_knots));
+    if (n_knots > (1 << 30)) return set_err(PTL_ERR_ARG, "too many knots");
+    for (int64_t i = 1; i < n_knots; ++i)
+        if (!(knot_ts[i] > knot_ts[i - 1])) return set_err(PTL_ERR_ARG, "knot timestamps must increase strictly (knot %lld)", (long long)i);
+    if (device_id < 0 || ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    ptl_traj* t = new ptl_traj();
+    t->device_id = device_id; t->n = (int)n_knots; t->d_kt = nullptr; t->d_kp = nullptr; t->before = bound_before; t->after = bound_after;
+    hipError_t e = dalloc(&t->d_kt, (size_t)n_knots);
+    if (e == hipSuccess) e = dalloc(&t->d_kp, (size_t)n_knots * 16);
+    if (e == hipSuccess) e = hipMemcpy(t->d_kt, knot_ts, (size_t)n_knots * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_kp, knot_poses16, (size_t)n_knots * 128, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ptl_traj_destroy(t);
+        return set_err(PTL_ERR_HIP, "ptl_traj_create: %s", hipGetErrorString(e));
+    }
+    *out = t;
+    return PTL_OK;
+}
+extern "C" int ptl_traj_destroy(ptl_traj* t) {
+    if (!t) return PTL_OK;
+    if (t->d_kt || t->d_kp) (void)hipSetDevice(t->device_id);
+    if (t->d_kt) (void)hipFree(t->d_kt);
+    if (t->d_kp) (void)hipFree(t->d_kp);
+    delete t;
+    return PTL_OK;
+}
+// what every posed-scan entry point checks (before any HIP call) and sets up: one device, the map handle's geometry, its FlyWs, and its
+// stream ordered behind a map update that may still run
+static int fly_prepare(ptl_icp* h, const ptl_traj* t, const ptl_lut* lut, int64_t H, int64_t W, const char* who) {
+    if (t->device_id != h->cfg.device_id) return set_err(PTL_ERR_ARG, "%s: trajectory on device %d, map on device %d", who, t->device_id, h->cfg.device_id);
+    if (lut && lut->device_id != h->cfg.device_id) return set_err(PTL_ERR_ARG, "%s: LUT on device %d, map on device %d", who, lut->device_id, h->cfg.device_id);
+    if (H < 1 || W < 1) return set_err(PTL_ERR_ARG, "%s: empty scan", who);
+    if (W != h->c.W) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld columns, the map handle's scan_cols is %d", who, (long long)W, h->c.W);
+    if (H * W > h->n_max) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the map handle's max_points_per_scan is %lld", who, (long long)(H * W), (long long)h->n_max);
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h->d_fly) {
+        HIPCHK(dalloc(&h->d_fly, 1));
+        HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), h->stream));
+    }
+    return icp_join_map(h);
+}
+// one posed scan enqueued on the map handle's stream; raw (device): the sweep; d_col_ts (device, W) or the sweep's (t0, t1)
+static int fly_enqueue(ptl_icp* h, const ptl_traj* t, const void* raw, bool is_range, const ptl_lut* lut, int H, int W, const double* d_col_ts,
+                       double t0, double t1) {
+    const Ctx& c = h->c;
+    hipStream_t s = h->stream;
+    const int n = H * W, nb = (n + 255) / 256;
+    FlyWs* ws = h->d_fly;
+    double* pts = (double*)h->d_in;
+    k_fly_coltab<<<1, 256, 0, s>>>(t->d_kt, t->d_kp, t->n, t->before, t->after, d_col_ts, t0, t1, W, c.coltab, ws);
+    if (is_range) {
+        k_fly_count<true><<<nb, 256, 0, s>>>(raw, n, c.bcnt1, ws);
+        k_fly_emit<true><<<nb, 256, 0, s>>>(raw, lut->dir, lut->off, n, W, c.coltab, c.bcnt1, pts, ws);
+    } else {
+        k_fly_count<false><<<nb, 256, 0, s>>>(raw, n, c.bcnt1, ws);
+        k_fly_emit<false><<<nb, 256, 0, s>>>(raw, nullptr, nullptr, n, W, c.coltab, c.bcnt1, pts, ws);
+    }
+    k_map_insert_a<<<nb, 256, 0, s>>>(c, pts, &ws->n, 0, 0);  // as ptl_icp_map_add, with the device count
+    k_map_insert_b<<<nb, 256, 0, s>>>(c, &ws->n, 0);
+    k_map_insert_c<<<nb, 256, 0, s>>>(c, &ws->n, 0);
+    HIPCHK(hipGetLastError());
+    return PTL_OK;
+}
+// per-call form: the raw sweep and its column times go up once (staged in the handle's deskew buffers, idle in a map container), the
+// count and the flag come back (8 bytes, beside the error word ptl_icp_map_add reads too)
+static int fly_add_percall(ptl_icp* h, ptl_traj* t, ptl_lut* lut, const void* raw_host, size_t raw_bytes, bool is_range, int64_t H, int64_t W,
+                           const double* col_ts, int64_t* n_valid, int32_t* skipped, const char* who) {
+    int rc = fly_prepare(h, t, lut, H, W, who);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h->c.pts, raw_host, raw_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_t01, col_ts, (size_t)W * 8, hipMemcpyHostToDevice, h->stream));
+    rc = fly_enqueue(h, t, h->c.pts, is_range, lut, (int)H, (int)W, h->d_t01, 0.0, 0.0);
+    if (rc) return rc;
+    int nf[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(nf, h->d_fly, sizeof nf, hipMemcpyDeviceToHost, h->stream));
+    rc = icp_check_flags(h);  // (waits for the stream)
+    if (rc) return rc;
+    if (n_valid) *n_valid = nf[0];
+    if (skipped) *skipped = nf[1] ? 1 : 0;
+    return PTL_OK;
+}
+extern "C" int ptl_icp_map_add_posed_range(ptl_icp* map, ptl_traj* t, ptl_lut* lut, const uint32_t* range_mm, const double* col_ts,
+                                           int64_t* n_valid, int32_t* skipped) {
+    if (!map || !t || !lut || !range_mm || !col_ts) return set_err(PTL_ERR_ARG, "null argument");
+    return fly_add_percall(map, t, lut, range_mm, (size_t)lut->H * lut->W * 4, true, lut->H, lut->W, col_ts, n_valid, skipped, "ptl_icp_map_add_posed_range");
+}
+extern "C" int ptl_icp_map_add_posed_xyz(ptl_icp* map, ptl_traj* t, const float* xyz, int32_t H, int32_t W, const double* col_ts,
+                                         int64_t* n_valid, int32_t* skipped) {
+    if (!map || !t || !xyz || !col_ts) return set_err(PTL_ERR_ARG, "null argument");
+    return fly_add_percall(map, t, nullptr, xyz, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * 12, false, H, W, col_ts, n_valid, skipped, "ptl_icp_map_add_posed_xyz");
+}
+// resident form: sweeps [first, last] of a lane, `slot` bytes apart; nothing but the two totals crosses the bus, once, at the end.
+// The caller has checked the runner's side and waited for its streams; the lane is only read.
+static int fly_build(ptl_icp* map, ptl_traj* t, const SeqLane& l, size_t slot, const unsigned char* is_range_k, bool all_range, const ptl_lut* lut,
+                     int64_t pps, const double* t0t1, int64_t first, int64_t last, int64_t* n_valid, int64_t* n_skipped, const char* who) {
+    if (map == l.icp) return set_err(PTL_ERR_ARG, "%s: the map handle is the runner's own registration handle", who);
+    const int64_t W = map->c.W;
+    if (pps % W) return set_err(PTL_ERR_CAPACITY, "%s: %lld points per sweep are no multiple of the map handle's scan_cols = %lld", who, (long long)pps, (long long)W);
+    if (l.icp->c.W != W) return set_err(PTL_ERR_CAPACITY, "%s: the runner's scan_cols is %d, the map handle's %lld", who, l.icp->c.W, (long long)W);
+    int rc = fly_prepare(map, t, lut, pps / W, W, who);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(&map->d_fly->n_valid, 0, 2 * sizeof(long long), map->stream));
+    for (int64_t k = first; k <= last; ++k) {
+        const bool rg = all_range || (is_range_k && is_range_k[(size_t)k]);
+        rc = fly_enqueue(map, t, (const char*)l.d_scans + (size_t)k * slot, rg, lut, (int)(pps / W), (int)W, nullptr, t0t1[2 * k], t0t1[2 * k + 1]);
+        if (rc) return rc;
+    }
+    long long tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tot, &map->d_fly->n_valid, sizeof tot, hipMemcpyDeviceToHost, map->stream));
+    rc = icp_check_flags(map);
+    if (rc) return rc;
+    if (n_valid) *n_valid = tot[0];
+    if (n_skipped) *n_skipped = tot[1];
+    return PTL_OK;
+}
+extern "C" int ptl_seq_map_build(ptl_seq* s, ptl_icp* map, ptl_traj* t, const double* t0t1, int64_t first, int64_t last, int64_t* n_valid,
+                                 int64_t* n_skipped) {
+    if (!s || !map || !t || !t0t1) return set_err(PTL_ERR_ARG, "null argument");
+    if (first < 0 || last < first || last >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_seq_map_build: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)s->cfg.n_scans);
+    if (s->cfg.icp.device_id != map->cfg.device_id) return set_err(PTL_ERR_ARG, "ptl_seq_map_build: runner on device %d, map on device %d", s->cfg.icp.device_id, map->cfg.device_id);
+    bool any_range = false;
+    for (int64_t k = first; k <= last; ++k) any_range = any_range || s->is_range[(size_t)k];
+    if (any_range && !s->lut) return set_err(PTL_ERR_STATE, "ptl_seq_map_build: the sweeps are range images but no LUT was set (ptl_seq_set_lut)");
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));  // the runner's own work first; its sweeps are then only read
+    HIPCHK(hipStreamSynchronize(s->ekf_stream));
+    return fly_build(map, t, s->lane, (size_t)s->cfg.points_per_scan * 12, s->is_range.data(), false, any_range ? s->lut : nullptr, s->cfg.points_per_scan,
+                     t0t1, first, last, n_valid, n_skipped, "ptl_seq_map_build");
+}
+extern "C" int ptl_batch_map_build(ptl_batch* b, int32_t seq, ptl_icp* map, ptl_traj* t, const double* t0t1, int64_t first, int64_t last,
+                                   int64_t* n_valid, int64_t* n_skipped) {
+    if (!b || !map || !t || !t0t1) return set_err(PTL_ERR_ARG, "null argument");
+    if (seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "ptl_batch_map_build: sequence %d of %d", seq, b->S);
+    if (first < 0 || last < first || last >= b->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_batch_map_build: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)b->cfg.n_scans);
+    if (b->cfg.icp.device_id != map->cfg.device_id) return set_err(PTL_ERR_ARG, "ptl_batch_map_build: batch on device %d, map on device %d", b->cfg.icp.device_id, map->cfg.device_id);
+    if (b->ring < b->cfg.n_scans) return set_err(PTL_ERR_STATE, "ptl_batch_map_build: the batch keeps a ring of %lld sweep slots (resident_scans): earlier sweeps are gone", (long long)b->ring);
+    if (b->cfg.range_input && !b->lut) return set_err(PTL_ERR_STATE, "ptl_batch_map_build: a range-input batch needs its LUT (ptl_batch_set_lut)");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    HIPCHK(hipStreamSynchronize(b->stream));  // the batch's own work first; its sweeps are then only read
+    HIPCHK(hipStreamSynchronize(b->side));
+    const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
+    return fly_build(map, t, b->lane[seq], slot, nullptr, b->is_range != 0, b->is_range ? b->lut : nullptr, b->cfg.points_per_scan, t0t1, first, last,
+                     n_valid, n_skipped, "ptl_batch_map_build");
 }

@@ -3,7 +3,9 @@ carry one pose per column are de-warped into the world frame and accumulated int
 both to ouster-sdk's `ScansAccumulator` and draws the result (the viewer is out of scope here); this module keeps the
 arithmetic: column poses from a time-stamped trajectory (`utils.TrajectoryEvaluator`, `utils.pose_scans_from_nc_gt`),
 `client.dewarp` on the GPU (`ptl_lut_dewarp`), and the map as the voxel-hash map of the registration path
-(`ptl_icp_map_add`: a voxel keeps its first points, deterministic) instead of ScansAccumulator's random subsample."""
+(`ptl_icp_map_add`: a voxel keeps its first points, deterministic) instead of ScansAccumulator's random subsample.
+With a `core.Traj` the three steps run fused on the device (`ptl_icp_map_add_posed_range`), and `add_run` builds the map of a
+runner's resident sweeps without moving them (`ptl_*_map_build`); DESIGN.md 3.14."""
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -37,9 +39,20 @@ class MapAccumulator:
                              map_block_capacity=map_block_capacity, map_table_capacity=map_table_capacity)
         self.scans = 0
         self.returns = 0
+        self.skipped = 0
 
-    def update(self, scan) -> np.ndarray:
-        """de-warp one posed scan and add its returns to the map; gives back their world coordinates"""
+    def update(self, scan, traj=None):
+        """de-warp one posed scan and add its returns to the map; gives back their world coordinates.
+        traj (a core.Traj): the fused path - the column poses come from `traj` at scan.timestamp on the device, scan.pose is ignored,
+        the sweep goes up once and nothing but the count comes back: returns n_valid (0 for a scan skipped as outside the bounds,
+        counted in `skipped`) instead of the points.  The map is the same, bit for bit."""
+        if traj is not None:
+            n_valid, skipped = self._icp.map_add_posed(traj, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9,
+                                                       range_mm=scan.range_mm, lut=self.lut)
+            self.skipped += int(skipped)
+            self.scans += 0 if skipped else 1
+            self.returns += n_valid
+            return n_valid
         xyz, n_valid = self.lut.dewarp(scan.range_mm, scan.pose)
         keep = np.asarray(scan.range_mm).reshape(-1) != 0
         pts = xyz[keep]
@@ -48,8 +61,37 @@ class MapAccumulator:
         self.returns += n_valid
         return pts
 
+    def add_run(self, runner, traj, t0t1, s=None, first=0, last=None):
+        """the RESIDENT sweeps [first, last] of a core.SeqRunner (s=None) or of sequence s of a core.BatchRunner into the map, posed by
+        `traj` with the sweep times t0t1 (n_scans, 2): no sweep crosses the bus.  Returns (n_valid, n_skipped)"""
+        if s is None:
+            n_valid, n_skipped = runner.build_map(self._icp, traj, t0t1, first, last)
+        else:
+            n_valid, n_skipped = runner.build_map(s, self._icp, traj, t0t1, first, last)
+        n = (runner.n_scans - 1 if last is None else int(last)) - int(first) + 1
+        self.scans += n - n_skipped
+        self.skipped += n_skipped
+        self.returns += n_valid
+        return n_valid, n_skipped
+
     def map_size(self):
         return self._icp.map_size()
 
     def map_points(self) -> np.ndarray:
         return self._icp.map_points()
+
+
+def synthetic_range_scans(seq, first=0, last=None):
+    """The sweeps [first, last] of a synth.Sequence as a sensor would deliver them: (core.Lut, [PosedScan]) - range images in mm on the
+    ouster column convention (column v looks along 2 pi (1 - v / W)), column timestamps in ns, the sequence's beam fan (45 .. -45 deg)"""
+    H, W = seq.H, seq.W
+    last = seq.n_scans - 1 if last is None else int(last)
+    lut = core.Lut(H, W, np.linspace(45.0, -45.0, H), np.zeros(H), 0.0)
+    src = (W - np.arange(W)) % W
+    scans = []
+    for k in range(int(first), last + 1):
+        x = seq.scan(k).astype(np.float64).reshape(H, W, 3)
+        rng_mm = np.round(np.linalg.norm(x, axis=2) * 1000.0).astype(np.uint32)[:, src]
+        col_t = seq.t_base + (k + src / W) * seq.scan_dt
+        scans.append(PosedScan(rng_mm, (col_t * 1e9).astype(np.int64)))
+    return lut, scans

@@ -228,3 +228,59 @@ def pose_scans_from_nc_gt(source, nc_gt_poses_file: Optional[str] = None, nc_gt_
         yield scan
     print(f"NOTE: Therere where {skipped_scans} skipped scans that wasn't "
           "because they were outside of the NC GT poses available")
+
+
+_PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {n}\n"
+               "property double x\nproperty double y\nproperty double z\nend_header\n")
+
+
+def save_map_ply(path: str, xyz) -> None:
+    """A point map (N, 3) to disk: PLY `binary_little_endian 1.0`, `element vertex N`, three `property double` x y z - the doubles
+    as they are, so a map read back is bit-equal; a path ending in .npy uses np.save instead"""
+    pts = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    if str(path).endswith(".npy"):
+        np.save(path, pts)
+        return
+    with open(path, "wb") as f:
+        f.write(_PLY_HEADER.format(n=len(pts)).encode("ascii"))
+        f.write(pts.astype("<f8", copy=False).tobytes())
+
+
+def load_map_ply(path: str) -> np.ndarray:
+    """(N, 3) float64 of a map written by `save_map_ply` (.npy: np.load).  Reads the PLY subset that function writes."""
+    if str(path).endswith(".npy"):
+        return np.load(path).reshape(-1, 3)
+    with open(path, "rb") as f:
+        n, fmt, props = None, None, []
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        for raw in iter(f.readline, b""):
+            w = raw.decode("ascii", "replace").split()
+            if w[:1] == ["end_header"]:
+                break
+            if w[:1] == ["format"]:
+                fmt = w[1]
+            elif w[:2] == ["element", "vertex"]:
+                n = int(w[2])
+            elif w[:1] == ["element"]:
+                raise ValueError(f"{path}: only a vertex element is read")
+            elif w[:1] == ["property"]:
+                props.append(tuple(w[1:]))
+        else:
+            raise ValueError(f"{path}: no end_header")
+        if fmt != "binary_little_endian" or n is None or props != [("double", "x"), ("double", "y"), ("double", "z")]:
+            raise ValueError(f"{path}: expected binary_little_endian, element vertex N, property double x y z")
+        data = f.read(n * 24)
+    if len(data) != n * 24:
+        raise ValueError(f"{path}: {n} vertices announced, {len(data) // 24} present")
+    return np.frombuffer(data, dtype="<f8").astype(np.float64).reshape(n, 3)
+
+
+def nc_gt_file_rows(t, poses) -> List[Tuple[float, np.ndarray]]:
+    """[(ts, pose)] as `read_newer_college_gt` gives them back from the file `save_poses_nc_gt_format(t, poses)` writes (through the
+    same text, in memory): what a later `flyby --nc-gt-poses` of that file works with"""
+    import io
+    buf = io.StringIO()
+    save_poses_nc_gt_format(buf, t=t, poses=poses)
+    buf.seek(0)
+    return read_newer_college_gt(buf)
