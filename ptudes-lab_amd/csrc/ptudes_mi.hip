@@ -7,6 +7,7 @@
 #include "icp_kernels.h"
 #include "seq_kernel.h"
 #include "fly_kernels.h"
+#include "hip_own.h"
 
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -15,6 +16,8 @@
 #include <string.h>
 #include <algorithm>
 #include <atomic>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 static thread_local char g_err[512] = "";
@@ -74,52 +77,49 @@ static int abi_check(const char* what, uint32_t size_caller, uint32_t abi_caller
 #define ABI_CHECK(what, p) do { int rc_ = abi_check(#what, (p)->struct_size, (p)->abi_version, sizeof(what)); if (rc_) return rc_; } while (0)
 
 // ================================================================================================ ICP
+// (every handle: streams first, events next, the memory's owner last - they are destroyed in the reverse order)
 struct ptl_icp {
     ptl_icp_cfg cfg;
-    hipStream_t stream;
-    bool own_stream;
-    Ctx c;               // kernel context (device pointers)
-    int64_t n_max;
-    int nblk_scan;
-    void* d_in;          // staging for host-provided scans (n_max * 3 * 8 bytes)
-    double* d_t01;
-    double* d_ext;       // staging for a host-provided guess
-    int* d_counter;
-    int64_t traj_cap;
-    int64_t scans_done;
-    unsigned char* d_row_mask;  // active-beam mask for range-image input, or null
-    int64_t last_n;      // points of the previous scan
-    bool lazy_map_stats; // per-call API: do not wait for the scan's map update before returning (ptl_icp_set_lazy_map_stats)
+    Stream stream;       // its own, or borrowed from the runner it is a member of
+    Stream map_stream;   // the map update's (below)
+    Ctx c = {};          // kernel context (device pointers)
+    int64_t n_max = 0;
+    int nblk_scan = 0;
+    void* d_in = nullptr;       // staging for host-provided scans (n_max * 3 * 8 bytes)
+    double* d_t01 = nullptr;
+    double* d_ext = nullptr;    // staging for a host-provided guess
+    int* d_counter = nullptr;
+    int64_t traj_cap = 0;
+    int64_t scans_done = 0;
+    unsigned char* d_row_mask = nullptr;  // active-beam mask for range-image input, or null
+    int64_t last_n = 0;          // points of the previous scan
+    bool lazy_map_stats = false; // per-call API: do not wait for the scan's map update before returning (ptl_icp_set_lazy_map_stats)
     // profiling of the dominant kernel
-    bool prof;
-    int prof_every;  // time every n-th GN launch (two event records cost ~18 us of command-processor time per scan)
-    std::vector<hipEvent_t> ev;
-    size_t ev_used;
+    int prof_every = 1;  // time every n-th GN launch (two event records cost ~18 us of command-processor time per scan)
+    GnTimer prof;
     // set by the sequence runner around a scan: the GN kernel waits for `gn_wait` (the EKF stream produced the guess)
-    hipEvent_t gn_wait, gn_done;  // ... and `gn_done` is recorded right after it (a second event: two streams waiting on one measured slower)
-    hipEvent_t ev_step_guess, ev_step_gn;  // ptl_icp_ekf_step's own pair (created on first use)
+    hipEvent_t gn_wait = nullptr, gn_done = nullptr;  // ... and `gn_done` is recorded right after it (a second event: two streams waiting on one measured slower); both borrowed
+    Event ev_step_guess, ev_step_gn;  // ptl_icp_ekf_step's own pair (created on first use)
     // ev_gn is recorded right after each GN launch: the map update (and the sequence runner's EKF step) start from it.
     // frame_down is double-buffered so that K3 of scan k+1 does not overwrite what K7 of scan k still reads.
     // the map update (K7-K10, rebuild) runs on `map_stream`: it needs the GN result (ev_gn) and must be complete before
     // the next GN launch (ev_map); beside it, on `stream`, run K0-K4 of the next scan
-    hipStream_t map_stream;
-    hipEvent_t ev_map;
-    bool ev_map_valid;
-    hipEvent_t ev_gn;
-    bool ev_gn_valid;
-    int* n_src_hint;  // pinned host copy of the last scan's N_s, written by an asynchronous copy on the map stream
-    double* fd_buf[2];
-    double gn_ms;
-    int64_t gn_launches;
+    Event ev_map;
+    bool ev_map_valid = false;
+    Event ev_gn;
+    bool ev_gn_valid = false;
+    int* n_src_hint = nullptr;  // pinned host copy of the last scan's N_s, written by an asynchronous copy on the map stream
+    double* fd_buf[2] = {nullptr, nullptr};
     // IMU deskew: the prologue waits for `pro_wait` (the filter's predicts through the sweep's samples); the per-call step's sweep times and
     // recorded modes, one entry per scan (dk_cap entries, grown with the scans)
-    hipEvent_t pro_wait;
-    double* dk_t0t1;
-    int* dk_modes;
-    int64_t dk_cap;
-    bool dk_wired;                   // the device state holds the IMU deskew's wiring: the prologue runs its IMU instance
+    hipEvent_t pro_wait = nullptr;   // (borrowed)
+    double* dk_t0t1 = nullptr;
+    int* dk_modes = nullptr;
+    int64_t dk_cap = 0;
+    bool dk_wired = false;           // the device state holds the IMU deskew's wiring: the prologue runs its IMU instance
     std::vector<signed char> dk_rec; // per registered scan (icp_enqueue_scan): its deskew mode, or -1 = IMU-wired (the device recorded it)
     FlyWs* d_fly = nullptr;          // posed scans into the map (fly_kernels.h): count, flag and totals, allocated by the first such call
+    DevOwner mem;                    // every device buffer above and in `c`, and the pinned word
 };
 
 extern "C" int ptl_icp_default_cfg(ptl_icp_cfg* cfg, double max_range, double min_range) {
@@ -152,26 +152,32 @@ extern "C" int ptl_icp_default_cfg(ptl_icp_cfg* cfg, double max_range, double mi
     return PTL_OK;
 }
 
-template <typename T>
-static hipError_t dalloc(T** p, size_t n) { return hipMalloc((void**)p, n * sizeof(T)); }
-
-static int icp_free(ptl_icp* h) {
-    if (!h) return PTL_OK;
-    (void)hipSetDevice(h->cfg.device_id);
-    Ctx& c = h->c;
-    void* ptrs[] = {c.pts, c.slot1, c.slot2, c.vtab1, c.vtab2, c.bcnt1, c.bcnt2, h->fd_buf[0], h->fd_buf[1], c.src0,
-                    c.src_cur, c.fdw, c.coltab, c.pslot, c.nxt, c.prank, c.plen, c.tab, c.blocks, c.bhdr, c.bfirst, c.free_stack, c.free_stack_s, c.mig_list, c.wg_clk, c.pc_key, c.pc_pb, c.pc_ans, c.gn_rows_ll, c.gn_xsum_ll,
-                    c.st, c.traj, c.sstats, h->d_in, h->d_t01, h->d_ext, h->d_counter, h->d_row_mask, h->dk_t0t1, h->dk_modes, h->d_fly};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_gn, h->ev_map, h->ev_step_guess, h->ev_step_gn})
-        if (e) (void)hipEventDestroy(e);
-    if (h->n_src_hint) (void)hipHostFree(h->n_src_hint);
-    if (h->map_stream) (void)hipStreamDestroy(h->map_stream);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+// the whole of every destroy function: the handle's device first, then its members in their order
+template <class H>
+static int handle_destroy(H* h, int device_id) {
+    (void)hipSetDevice(device_id);
     delete h;
     return PTL_OK;
+}
+#define ERR_FLAGS_FMT "device capacity/error flags 0x%x (1 key range, 2 block pool, 4 map table, 8 vds table, 16 gn barrier timeout)"
+
+// ---- the kernel instance for a run-time configuration: f gets the template arguments as std::integral_constant values
+// points per voxel: 20 (the default, unrolled) or 0 (any)
+template <class F>
+static void pick_p(int P, F&& f) {
+    if (P == 20) f(std::integral_constant<int, 20>{}); else f(std::integral_constant<int, 0>{});
+}
+// workgroups per team: one of GC..., else 0 (any)
+template <int... GC, class F>
+static void pick_team(int g, F&& f) {
+    if (!((g == GC ? (f(std::integral_constant<int, GC>{}), true) : false) || ...)) f(std::integral_constant<int, 0>{});
+}
+// A persistent kernel's workgroups wait for each other, so ALL of them have to be resident at once: what the runtime reports for this
+// kernel on this device (partitioned GPU, fewer CUs, larger workgroups) instead of finding out through a poll time-out
+template <class K>
+static hipError_t resident_capacity(K kernel, int threads, int device_id, int* per_cu, int* cus) {
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, threads, 0);
+    return e != hipSuccess ? e : hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device_id);
 }
 
 __global__ void k_fill_free_stack(int* fs, int n, int base) {
@@ -211,17 +217,17 @@ static size_t vds_table_slots(size_t per_point, size_t n) {
 }
 static int icp_reset_device(ptl_icp* h) {
     Ctx& c = h->c;
-    const size_t vcap = (size_t)c.vmask + 1, vcap2 = (size_t)c.vmask2 + 1;
-    HIPCHK(hipMemsetAsync(c.vtab1, 0xFF, vcap * sizeof(VdsEnt), h->stream));  // (key = EMPTY, index = none)
-    HIPCHK(hipMemsetAsync(c.vtab2, 0xFF, vcap2 * sizeof(VdsEnt), h->stream));
-    HIPCHK(hipMemsetAsync(c.tab, 0xFF, ((size_t)c.tmask + 1) * sizeof(TabEnt), h->stream));
-    HIPCHK(hipMemsetAsync(c.blocks, 0, (size_t)c.n_small * SMALL_BYTES + (size_t)(c.pool_cap - c.n_small) * c.bstride, h->stream));
-    HIPCHK(hipMemsetAsync(c.bhdr, 0, (size_t)c.pool_cap * 16, h->stream));
-    HIPCHK(hipMemsetAsync(c.bfirst, 0, (size_t)c.pool_cap * 24, h->stream));
-    HIPCHK(hipMemsetAsync(c.bcnt1, 0, (size_t)h->nblk_scan * sizeof(int), h->stream));  // look-back words of the compactions: tag 0 = never published
-    HIPCHK(hipMemsetAsync(c.bcnt2, 0, (size_t)h->nblk_scan * sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(c.gn_rows_ll, 0, (size_t)2 * c.G * 64 * 8, h->stream));  // the launch epoch restarts with the state
-    HIPCHK(hipMemsetAsync(c.gn_xsum_ll, 0, (size_t)2 * 8 * 8 * 64 * 8, h->stream));
+    const DevOwner& m = h->mem;  // (each buffer whole: its size is what icp_alloc asked for)
+    HIPCHK(hipMemsetAsync(c.vtab1, 0xFF, m.bytes_of(c.vtab1), h->stream));  // (key = EMPTY, index = none)
+    HIPCHK(hipMemsetAsync(c.vtab2, 0xFF, m.bytes_of(c.vtab2), h->stream));
+    HIPCHK(hipMemsetAsync(c.tab, 0xFF, m.bytes_of(c.tab), h->stream));
+    HIPCHK(hipMemsetAsync(c.blocks, 0, m.bytes_of(c.blocks), h->stream));
+    HIPCHK(hipMemsetAsync(c.bhdr, 0, m.bytes_of(c.bhdr), h->stream));
+    HIPCHK(hipMemsetAsync(c.bfirst, 0, m.bytes_of(c.bfirst), h->stream));
+    HIPCHK(hipMemsetAsync(c.bcnt1, 0, m.bytes_of(c.bcnt1), h->stream));  // look-back words of the compactions: tag 0 = never published
+    HIPCHK(hipMemsetAsync(c.bcnt2, 0, m.bytes_of(c.bcnt2), h->stream));
+    HIPCHK(hipMemsetAsync(c.gn_rows_ll, 0, m.bytes_of(c.gn_rows_ll), h->stream));  // the launch epoch restarts with the state
+    HIPCHK(hipMemsetAsync(c.gn_xsum_ll, 0, m.bytes_of(c.gn_xsum_ll), h->stream));
     k_fill_free_stack<<<(c.pool_cap - c.n_small + 255) / 256, 256, 0, h->stream>>>(c.free_stack, c.pool_cap - c.n_small, c.n_small);
     if (c.n_small > 0) k_fill_free_stack<<<(c.n_small + 255) / 256, 256, 0, h->stream>>>(c.free_stack_s, c.n_small, 0);
     k_state_init<<<1, 64, 0, h->stream>>>(c.st, c.pool_cap - c.n_small, c.n_small);
@@ -235,7 +241,81 @@ static int icp_reset_device(ptl_icp* h) {
     return PTL_OK;
 }
 
-static int icp_create_impl(const ptl_icp_cfg* cfg, hipStream_t shared_stream, ptl_icp** out, bool batch_member = false) {
+// the sizes of a registration handle's buffers, from its configuration (host only: nothing is allocated)
+static void icp_settle(ptl_icp* h, const ptl_icp_cfg* cfg) {
+    h->cfg = *cfg;
+    Ctx& c = h->c;
+    const int64_t n = cfg->max_points_per_scan;
+    h->n_max = n;
+    c.max_range = cfg->max_range; c.min_range = cfg->min_range; c.vs = cfg->voxel_size;
+    c.vds1 = cfg->voxel_size * 0.5;  // KissICP.voxelize
+    c.vds2 = cfg->voxel_size * 1.5;
+    c.init_thr = cfg->initial_threshold; c.min_motion = cfg->min_motion_th; c.conv = cfg->convergence;
+    c.P = cfg->max_points_per_voxel; c.deskew = cfg->deskew; c.max_iter = cfg->max_iterations;
+    c.W = cfg->scan_cols > 0 ? cfg->scan_cols : 1;
+    c.n_max = (int)n;
+    // per-scan voxel tables.  A table line holds a 2x2x2 brick of voxels (brick_slot), so what counts is how many LINES are taken:
+    // a voxel of a brick that lands on a taken line walks on through dependent reads, and one such voxel among the 512 claims of a
+    // wavefront's round costs the wavefront another round trip.  The lines a scan touches do not depend on the table's size, the
+    // slots are released by the compaction that follows (no clear per scan): size costs footprint only.  Pass 1 (~46 k voxels of
+    // ~120 k points): 64 slots per point (K0-K4 516 -> 485 us per scan against 8; 32: 493); pass 2 (~14 k voxels): 16.
+    c.vmask = (unsigned)(vds_table_slots(VDS1_SLOTS_PER_POINT, n) - 1);
+    c.vmask2 = (unsigned)(vds_table_slots(VDS2_SLOTS_PER_POINT, n) - 1);
+    c.tmask = (unsigned)(cfg->map_table_capacity - 1);
+    c.bstride = (int)(((size_t)c.P * 24 + 127) / 128 * 128);  // points only: the per-voxel header lives in the block directory (bhdr / bfirst)
+    c.n_small = (int)cfg->map_small_blocks;
+    c.pool_cap = (int)(cfg->map_block_capacity + cfg->map_small_blocks);  // block ids: the small blocks first, then map_block_capacity full ones
+    c.G = cfg->gn_workgroups;
+    c.overlap_pre = 1;
+    h->nblk_scan = (int)((n + 255) / 256);
+}
+// trajectory / statistics rows a handle starts with: 4096, doubled (as icp_grow_traj would) until a batch member's whole run fits
+static int64_t icp_traj_rows(int64_t n_scans, bool batch_member) {
+    int64_t cap = 4096;
+    while (batch_member && cap < n_scans) cap *= 2;
+    return cap;
+}
+// EVERY device buffer a settled registration handle is created with, once: `m` allocates them (h->mem) or only counts their bytes
+// (ptl_batch_create's capacity check).  Per point of max_points_per_scan the work buffers (deskewed points, slots, frame_down x 2,
+// source x 2, world frame_down, list links, probe rows, answer rows, the per-call input), the two per-scan voxel tables, the map table,
+// the block pool with its directory and free stacks, the exchange rows, the state, `traj_rows` result rows
+static void icp_alloc(DevOwner& m, ptl_icp* h, int64_t traj_rows) {
+    Ctx& c = h->c;
+    const size_t n = (size_t)h->n_max, n_small = (size_t)(c.n_small > 0 ? c.n_small : 1);
+    m.add(&c.pts, 3 * n);
+    m.add(&c.slot1, n); m.add(&c.slot2, n);
+    m.add(&c.vtab1, (size_t)c.vmask + 1); m.add(&c.vtab2, (size_t)c.vmask2 + 1);
+    m.add(&c.bcnt1, (size_t)h->nblk_scan); m.add(&c.bcnt2, (size_t)h->nblk_scan);
+    m.add(&h->fd_buf[0], 3 * n); m.add(&c.src0, 3 * n);
+    c.fd = h->fd_buf[0];
+    m.add(&h->fd_buf[1], 3 * n);
+    m.add(&c.src_cur, 3 * n); m.add(&c.fdw, 3 * n);
+    m.add(&c.coltab, (size_t)c.W * 12);
+    m.add(&c.pslot, n); m.add(&c.nxt, n);
+    m.add(&c.prank, n); m.add(&c.plen, n);
+    m.add(&c.tab, (size_t)c.tmask + 1);
+    m.add(&c.blocks, (size_t)c.n_small * SMALL_BYTES + (size_t)(c.pool_cap - c.n_small) * c.bstride);
+    c.big_base = (unsigned char*)((uintptr_t)c.blocks + (uintptr_t)c.n_small * SMALL_BYTES - (uintptr_t)c.n_small * (uintptr_t)c.bstride);
+    m.add(&c.bhdr, (size_t)c.pool_cap * 4); m.add(&c.bfirst, (size_t)c.pool_cap * 3);
+    m.add(&c.free_stack, (size_t)(c.pool_cap - c.n_small));
+    m.add(&c.free_stack_s, n_small); m.add(&c.mig_list, n_small);
+    m.add(&c.pc_key, n); m.add(&c.pc_pb, 32 * n); m.add(&c.pc_ans, GN8_ANS_ROW * n);
+    m.add_pinned(&h->n_src_hint, 1);
+    m.add(&c.gn_rows_ll, (size_t)2 * c.G * 64);
+    m.add(&c.gn_xsum_ll, (size_t)2 * 8 * 8 * 64);
+    m.add(&c.wg_clk, (size_t)c.G * 2);
+    m.add(&c.st, 1);
+    h->traj_cap = traj_rows;
+    c.traj_cap = (int)traj_rows;
+    m.add(&c.traj, (size_t)traj_rows * 16);
+    m.add(&c.sstats, (size_t)traj_rows);
+    m.add((unsigned char**)&h->d_in, n * 3 * 8);
+    m.add(&h->d_t01, n);
+    m.add(&h->d_ext, 16);
+    m.add(&h->d_counter, 4);
+}
+// traj_rows: the trajectory / statistics rows to start with (icp_traj_rows)
+static int icp_create_impl(const ptl_icp_cfg* cfg, hipStream_t shared_stream, ptl_icp** out, bool batch_member = false, int64_t traj_rows = 4096) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
     ABI_CHECK(ptl_icp_cfg, cfg);
     // the search maps one lane of a 32-lane group to one stored point of a voxel: more than 32 per voxel would be stored and never examined
@@ -254,125 +334,38 @@ static int icp_create_impl(const ptl_icp_cfg* cfg, hipStream_t shared_stream, pt
     if (ptl_device_count() <= cfg->device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", cfg->device_id);
     HIPCHK(hipSetDevice(cfg->device_id));
     {
-        // The Gauss-Newton kernel is persistent: its workgroups exchange sums every iteration, so ALL of them have to be
-        // resident at once.  Check that against the occupancy the runtime reports for this kernel on this device
-        // (partitioned GPU, fewer CUs, larger gn_threads) instead of finding out through a poll time-out.
         int per_cu = 0, cus = 0;
-        const int P20 = cfg->max_points_per_voxel == 20;
-        hipError_t e;
-        if (cfg->gn_lanes_per_point == 8)
-            e = P20 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gn_loop8<20, 0>, cfg->gn_threads, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gn_loop8<0, 0>, cfg->gn_threads, 0);  // (the instance with the largest footprint)
-        else
-            e = P20 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gn_loop<20, true>, cfg->gn_threads, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gn_loop<0, true>, cfg->gn_threads, 0);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device_id);
+        hipError_t e = hipSuccess;
+        pick_p(cfg->max_points_per_voxel, [&](auto pc) {  // (of the 8-lane kernel, the instance with the largest footprint)
+            e = cfg->gn_lanes_per_point == 8 ? resident_capacity(k_gn_loop8<pc(), 0>, cfg->gn_threads, cfg->device_id, &per_cu, &cus)
+                                             : resident_capacity(k_gn_loop<pc(), true>, cfg->gn_threads, cfg->device_id, &per_cu, &cus);
+        });
         if (e != hipSuccess) return set_err(PTL_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
         if ((int64_t)per_cu * cus < cfg->gn_workgroups)
             return set_err(PTL_ERR_STATE, "gn_workgroups = %d x %d threads cannot be co-resident on device %d (%d CUs x %d workgroups per CU): "
                            "lower gn_workgroups", cfg->gn_workgroups, cfg->gn_threads, cfg->device_id, cus, per_cu);
     }
-    ptl_icp* h = new ptl_icp();
-    h->cfg = *cfg;
-    h->own_stream = shared_stream == nullptr;
-    h->stream = shared_stream;
-    h->prof = false; h->prof_every = 1; h->ev_used = 0; h->gn_ms = 0; h->gn_launches = 0;
-    h->gn_wait = nullptr; h->gn_done = nullptr; h->ev_step_guess = nullptr; h->ev_step_gn = nullptr;
-    h->lazy_map_stats = false;
-    h->n_src_hint = nullptr;
-    h->map_stream = nullptr; h->ev_map = nullptr; h->ev_map_valid = false;
-    h->ev_gn = nullptr;
-    h->ev_gn_valid = false; h->fd_buf[0] = h->fd_buf[1] = nullptr;
-    h->d_in = nullptr; h->d_t01 = nullptr; h->d_ext = nullptr; h->d_counter = nullptr; h->d_row_mask = nullptr;
-    h->pro_wait = nullptr; h->dk_t0t1 = nullptr; h->dk_modes = nullptr; h->dk_cap = 0; h->dk_wired = false;
-    memset(&h->c, 0, sizeof(Ctx));
-    if (h->own_stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return set_err(PTL_ERR_HIP, "hipStreamCreate failed");
-    }
+    std::unique_ptr<ptl_icp> owner(new ptl_icp());  // (an error return below deletes the handle, and with it what it holds by then)
+    ptl_icp* h = owner.get();
+    icp_settle(h, cfg);
+    if (shared_stream) h->stream.borrow(shared_stream);
+    else if (h->stream.create() != hipSuccess) return set_err(PTL_ERR_HIP, "hipStreamCreate failed");
     Ctx& c = h->c;
-    const int64_t n = cfg->max_points_per_scan;
-    h->n_max = n;
-    c.max_range = cfg->max_range; c.min_range = cfg->min_range; c.vs = cfg->voxel_size;
-    c.vds1 = cfg->voxel_size * 0.5;  // KissICP.voxelize
-    c.vds2 = cfg->voxel_size * 1.5;
-    c.init_thr = cfg->initial_threshold; c.min_motion = cfg->min_motion_th; c.conv = cfg->convergence;
-    c.P = cfg->max_points_per_voxel; c.deskew = cfg->deskew; c.max_iter = cfg->max_iterations;
-    c.W = cfg->scan_cols > 0 ? cfg->scan_cols : 1;
-    c.n_max = (int)n;
-    // per-scan voxel tables.  A table line holds a 2x2x2 brick of voxels (brick_slot), so what counts is how many LINES are taken:
-    // a voxel of a brick that lands on a taken line walks on through dependent reads, and one such voxel among the 512 claims of a
-    // wavefront's round costs the wavefront another round trip.  The lines a scan touches do not depend on the table's size, the
-    // slots are released by the compaction that follows (no clear per scan): size costs footprint only.  Pass 1 (~46 k voxels of
-    // ~120 k points): 64 slots per point (K0-K4 516 -> 485 us per scan against 8; 32: 493); pass 2 (~14 k voxels): 16.
-    const size_t vcap = vds_table_slots(VDS1_SLOTS_PER_POINT, n), vcap2 = vds_table_slots(VDS2_SLOTS_PER_POINT, n);
-    c.vmask = (unsigned)(vcap - 1);
-    c.vmask2 = (unsigned)(vcap2 - 1);
-    c.tmask = (unsigned)(cfg->map_table_capacity - 1);
-    c.bstride = (int)(((size_t)c.P * 24 + 127) / 128 * 128);  // points only: the per-voxel header lives in the block directory (bhdr / bfirst)
-    c.n_small = (int)cfg->map_small_blocks;
-    c.pool_cap = (int)(cfg->map_block_capacity + cfg->map_small_blocks);  // block ids: the small blocks first, then map_block_capacity full ones
-    c.G = cfg->gn_workgroups;
-    h->nblk_scan = (int)((n + 255) / 256);
-    h->traj_cap = 4096;
-    c.traj_cap = (int)h->traj_cap;
-    bool ok = true;
-    ok &= dalloc(&c.pts, 3 * n) == hipSuccess;
-    ok &= dalloc(&c.slot1, n) == hipSuccess && dalloc(&c.slot2, n) == hipSuccess;
-    ok &= dalloc(&c.vtab1, vcap) == hipSuccess && dalloc(&c.vtab2, vcap2) == hipSuccess;
-    ok &= dalloc(&c.bcnt1, h->nblk_scan) == hipSuccess && dalloc(&c.bcnt2, h->nblk_scan) == hipSuccess;
-    ok &= dalloc(&c.fd, 3 * n) == hipSuccess && dalloc(&c.src0, 3 * n) == hipSuccess;
-    h->fd_buf[0] = c.fd;
-    ok &= dalloc(&h->fd_buf[1], 3 * n) == hipSuccess;
-    ok &= hipStreamCreateWithFlags(&h->map_stream, hipStreamNonBlocking) == hipSuccess;
-    ok &= hipEventCreateWithFlags(&h->ev_map, hipEventDisableTiming) == hipSuccess;
-    ok &= hipEventCreateWithFlags(&h->ev_gn, hipEventDisableTiming) == hipSuccess;
-    c.overlap_pre = 1;
-    ok &= dalloc(&c.src_cur, 3 * n) == hipSuccess && dalloc(&c.fdw, 3 * n) == hipSuccess;
-    ok &= dalloc(&c.coltab, (size_t)c.W * 12) == hipSuccess;
-    ok &= dalloc(&c.pslot, n) == hipSuccess && dalloc(&c.nxt, n) == hipSuccess;
-    ok &= dalloc(&c.prank, n) == hipSuccess && dalloc(&c.plen, n) == hipSuccess;
-    ok &= dalloc(&c.tab, (size_t)cfg->map_table_capacity) == hipSuccess;
-    ok &= hipMalloc((void**)&c.blocks, (size_t)c.n_small * SMALL_BYTES + (size_t)(c.pool_cap - c.n_small) * c.bstride) == hipSuccess;
-    c.big_base = (unsigned char*)((uintptr_t)c.blocks + (uintptr_t)c.n_small * SMALL_BYTES - (uintptr_t)c.n_small * (uintptr_t)c.bstride);
-    ok &= dalloc(&c.bhdr, (size_t)c.pool_cap * 4) == hipSuccess && dalloc(&c.bfirst, (size_t)c.pool_cap * 3) == hipSuccess;
-    ok &= dalloc(&c.free_stack, c.pool_cap - c.n_small) == hipSuccess;
-    ok &= dalloc(&c.free_stack_s, (size_t)(c.n_small > 0 ? c.n_small : 1)) == hipSuccess && dalloc(&c.mig_list, (size_t)(c.n_small > 0 ? c.n_small : 1)) == hipSuccess;
-    ok &= dalloc(&c.pc_key, n) == hipSuccess && dalloc(&c.pc_pb, 32 * n) == hipSuccess && dalloc(&c.pc_ans, GN8_ANS_ROW * n) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->n_src_hint, sizeof(int)) == hipSuccess;
-    if (h->n_src_hint) *h->n_src_hint = 0;
-    ok &= dalloc(&c.gn_rows_ll, (size_t)2 * c.G * 64) == hipSuccess && hipMemset(c.gn_rows_ll, 0, (size_t)2 * c.G * 64 * 8) == hipSuccess;
-    ok &= dalloc(&c.gn_xsum_ll, (size_t)2 * 8 * 8 * 64) == hipSuccess && hipMemset(c.gn_xsum_ll, 0, (size_t)2 * 8 * 8 * 64 * 8) == hipSuccess;
-    ok &= hipMalloc((void**)&c.wg_clk, (size_t)c.G * 16) == hipSuccess && hipMemset(c.wg_clk, 0, (size_t)c.G * 16) == hipSuccess;
-    ok &= dalloc(&c.st, 1) == hipSuccess && hipMemset(c.st, 0, sizeof(DevState)) == hipSuccess;  // (IMU deskew off: k_state_init keeps its wiring)
-    ok &= dalloc(&c.traj, (size_t)h->traj_cap * 16) == hipSuccess;
-    ok &= dalloc(&c.sstats, (size_t)h->traj_cap) == hipSuccess;
-    ok &= hipMalloc(&h->d_in, (size_t)n * 3 * 8) == hipSuccess;
-    ok &= dalloc(&h->d_t01, n) == hipSuccess;
-    ok &= dalloc(&h->d_ext, 16) == hipSuccess;
-    ok &= dalloc(&h->d_counter, 4) == hipSuccess;
-    if (!ok) {
-        icp_free(h);
-        return set_err(PTL_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
-    }
+    DevOwner& m = h->mem;
+    icp_alloc(m, h, traj_rows);
+    bool ok = m.err == hipSuccess && h->map_stream.create() == hipSuccess && h->ev_map.create() == hipSuccess && h->ev_gn.create() == hipSuccess;
+    if (ok) *h->n_src_hint = 0;
+    ok = ok && hipMemset(c.gn_rows_ll, 0, m.bytes_of(c.gn_rows_ll)) == hipSuccess && hipMemset(c.gn_xsum_ll, 0, m.bytes_of(c.gn_xsum_ll)) == hipSuccess &&
+         hipMemset(c.wg_clk, 0, m.bytes_of(c.wg_clk)) == hipSuccess && hipMemset(c.st, 0, sizeof(DevState)) == hipSuccess;  // (IMU deskew off: k_state_init keeps its wiring)
+    if (!ok) return set_err(PTL_ERR_HIP, "device allocation failed: %s", hipGetErrorString(m.err != hipSuccess ? m.err : hipGetLastError()));
     int rc = icp_reset_device(h);
-    if (rc != PTL_OK) { icp_free(h); return rc; }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { icp_free(h); return set_err(PTL_ERR_HIP, "init sync failed"); }
-    *out = h;
+    if (rc != PTL_OK) return rc;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return set_err(PTL_ERR_HIP, "init sync failed");
+    *out = owner.release();
     return PTL_OK;
 }
-// device bytes one registration handle allocates (icp_create_impl above, term by term): per point of max_points_per_scan the work
-// buffers (deskewed points, slots, the two per-scan voxel tables, frame_down x 2, source x 2, world frame_down, list links,
-// probe rows, answer rows, the per-call input), plus the map table, the block pool and its free stack
-static size_t icp_footprint_bytes(const ptl_icp_cfg* cfg) {
-    const size_t n = (size_t)cfg->max_points_per_scan;
-    const size_t bstride = ((size_t)cfg->max_points_per_voxel * 24 + 127) / 128 * 128;
-    const size_t per_point = 24 + 4 + 4 + 24 * 2 + 24 + 24 + 24 + 4 * 4 + 8 + 128 + GN8_ANS_ROW * 8 + 24 + 8;
-    return n * per_point + (vds_table_slots(VDS1_SLOTS_PER_POINT, n) + vds_table_slots(VDS2_SLOTS_PER_POINT, n)) * sizeof(VdsEnt) + (size_t)cfg->map_table_capacity * sizeof(TabEnt) +
-           (size_t)cfg->map_block_capacity * (bstride + 4 + 16 + 24) + (size_t)cfg->map_small_blocks * (SMALL_BYTES + 8 + 16 + 24) + (size_t)4096 * (128 + sizeof(ScanStats)) + (1u << 20);
-}
 extern "C" int ptl_icp_create(const ptl_icp_cfg* cfg, ptl_icp** out) { return icp_create_impl(cfg, nullptr, out); }
-extern "C" int ptl_icp_destroy(ptl_icp* h) { return icp_free(h); }
+extern "C" int ptl_icp_destroy(ptl_icp* h) { return h ? handle_destroy(h, h->cfg.device_id) : PTL_OK; }
 
 static int icp_grow_traj(ptl_icp* h) {
     // doubles the trajectory / stats buffers (host-side decision: scans_done is known on the host)
@@ -380,15 +373,16 @@ static int icp_grow_traj(ptl_icp* h) {
     const int64_t ncap = h->traj_cap * 2;
     double* nt = nullptr;
     ScanStats* ns = nullptr;
-    HIPCHK(dalloc(&nt, (size_t)ncap * 16));
-    HIPCHK(dalloc(&ns, (size_t)ncap));
+    DevOwner tmp;  // (the new rows are the handle's once the old ones are out of use)
+    HIPCHK(tmp.alloc(&nt, (size_t)ncap * 16));
+    HIPCHK(tmp.alloc(&ns, (size_t)ncap));
     HIPCHK(hipMemcpyAsync(nt, c.traj, (size_t)h->traj_cap * 16 * 8, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(ns, c.sstats, (size_t)h->traj_cap * sizeof(ScanStats), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipStreamSynchronize(h->map_stream));
     HIPCHK(hipDeviceSynchronize());  // (a sequence runner's EKF stream may still read the old trajectory rows)
-    (void)hipFree(c.traj); (void)hipFree(c.sstats);
-    c.traj = nt; c.sstats = ns;
+    h->mem.replace(&c.traj, tmp, nt);
+    h->mem.replace(&c.sstats, tmp, ns);
     h->traj_cap = ncap; c.traj_cap = (int)ncap;
     return PTL_OK;
 }
@@ -404,8 +398,9 @@ static int map_rebuild(ptl_icp* h, hipStream_t s) {
 // Enqueue one whole scan on the handle's stream (no host synchronisation):
 // in_f32 / in_f64 / t01 / ext_guess are DEVICE pointers (one of in_* non-null).
 struct ptl_lut {
-    int device_id, H, W;
-    double *dir, *off;
+    int device_id = 0, H = 0, W = 0;
+    double *dir = nullptr, *off = nullptr;
+    DevOwner mem;
 };
 static int icp_enqueue_scan(ptl_icp* h, const float* in_f32, const double* in_f64, const double* t01, int64_t n,
                             const double* ext_guess, const unsigned* in_range = nullptr, const ptl_lut* lut = nullptr) {
@@ -440,26 +435,16 @@ static int icp_enqueue_scan(ptl_icp* h, const float* in_f32, const double* in_f6
     k_compact_src<<<nb, 256, 0, s>>>(c);
     if (h->ev_map_valid) HIPCHK(hipStreamWaitEvent(s, h->ev_map, 0));
     if (h->gn_wait) HIPCHK(hipStreamWaitEvent(s, h->gn_wait, 0));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = h->prof && (h->scans_done % h->prof_every) == 0;
-    if (timed) {
-        if (h->ev_used + 2 > h->ev.size()) {
-            for (int k = 0; k < 2; ++k) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
-        }
-        e0 = h->ev[h->ev_used++]; e1 = h->ev[h->ev_used++];
-        HIPCHK(hipEventRecord(e0, s));
-    }
+    HIPCHK(h->prof.begin(s, (h->scans_done % h->prof_every) == 0));
     // ends with the post-ICP bookkeeping (kiss.py:116-128).  Dense scans (more source points than 32-lane groups) run the
     // variant that keeps probe results in memory; the previous scan's N_s, copied back without a wait, is the hint
     const bool dense = *h->n_src_hint > (int64_t)c.G * (h->cfg.gn_threads / 32);
-    if (h->cfg.gn_lanes_per_point == 8) {
-#define KG8(GC) do { if (c.P == 20) k_gn_loop8<20, GC><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); else k_gn_loop8<0, GC><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); } while (0)
-        if (c.G == 32) KG8(32); else if (c.G == 16) KG8(16); else if (c.G == 8) KG8(8); else KG8(0);
-#undef KG8
-    }
-    else if (c.P == 20) { if (dense) k_gn_loop<20, true><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); else k_gn_loop<20, false><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); }
-    else { if (dense) k_gn_loop<0, true><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); else k_gn_loop<0, false><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); }
-    if (timed) HIPCHK(hipEventRecord(e1, s));
+    pick_p(c.P, [&](auto pc) {
+        if (h->cfg.gn_lanes_per_point == 8) pick_team<32, 16, 8>(c.G, [&](auto gc) { k_gn_loop8<pc(), gc()><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0); });
+        else if (dense) k_gn_loop<pc(), true><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0);
+        else k_gn_loop<pc(), false><<<c.G, h->cfg.gn_threads, 0, s>>>(c, 0);
+    });
+    HIPCHK(h->prof.end(s));
     HIPCHK(hipEventRecord(h->ev_gn, s));
     h->ev_gn_valid = true;
     if (h->gn_done) HIPCHK(hipEventRecord(h->gn_done, s));
@@ -480,14 +465,6 @@ static int icp_enqueue_scan(ptl_icp* h, const float* in_f32, const double* in_f6
     return PTL_OK;
 }
 
-static void icp_collect_profile(ptl_icp* h) {
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]) == hipSuccess) { h->gn_ms += ms; h->gn_launches++; }
-    }
-    h->ev_used = 0;
-}
-
 // Every entry point that touches the map, the device state or the handle's staging buffers (d_in, d_ext, fdw) on h->stream goes through
 // this first: with lazy_map_stats a registration returns while its scan's map update (K7-K10, the rebuild) still runs on map_stream, and
 // the sequence runner leaves one in flight too - work enqueued on h->stream must be ordered behind it (map_add / align /
@@ -502,9 +479,8 @@ static int icp_check_flags(ptl_icp* h) {
     k_finish_scan<<<1, 64, 0, h->stream>>>(h->c);  // closes the last scan's bookkeeping (no-op when none is pending)
     HIPCHK(hipMemcpyAsync(&flags, &h->c.st->err_flags, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->prof) icp_collect_profile(h);
-    if (flags)
-        return set_err(PTL_ERR_CAPACITY, "device capacity/error flags 0x%x (1 key range, 2 block pool, 4 map table, 8 vds table, 16 gn barrier timeout)", flags);
+    h->prof.collect();
+    if (flags) return set_err(PTL_ERR_CAPACITY, ERR_FLAGS_FMT, flags);
     return PTL_OK;
 }
 
@@ -532,8 +508,8 @@ static int icp_percall_finish(ptl_icp* h, double out_pose[16], ptl_icp_stats* st
     if (lazy) {
         HIPCHK(hipMemcpyAsync(&flags, &h->c.st->err_flags, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->prof) icp_collect_profile(h);
-        if (flags) rc = set_err(PTL_ERR_CAPACITY, "device capacity/error flags 0x%x (1 key range, 2 block pool, 4 map table, 8 vds table, 16 gn barrier timeout)", flags);
+        h->prof.collect();
+        if (flags) rc = set_err(PTL_ERR_CAPACITY, ERR_FLAGS_FMT, flags);
         ss.map_voxels = -1; ss.map_points = -1;
     } else {
         rc = icp_check_flags(h);
@@ -617,7 +593,8 @@ extern "C" int ptl_icp_map_points(ptl_icp* h, double* xyz_out, int64_t max_point
     HIPCHK(hipSetDevice(h->cfg.device_id));
     double* d_out = nullptr;
     HIPCHK(hipStreamSynchronize(h->map_stream));  // (a map update may still be under way)
-    HIPCHK(dalloc(&d_out, (size_t)(max_points > 0 ? max_points : 1) * 3));
+    DevOwner tmp;
+    HIPCHK(tmp.alloc(&d_out, (size_t)(max_points > 0 ? max_points : 1) * 3));
     HIPCHK(hipMemsetAsync(h->d_counter, 0, sizeof(int), h->stream));
     k_map_export<<<(h->c.pool_cap + 255) / 256, 256, 0, h->stream>>>(h->c, d_out, h->d_counter, (int)max_points);
     int cnt = 0;
@@ -625,7 +602,6 @@ extern "C" int ptl_icp_map_points(ptl_icp* h, double* xyz_out, int64_t max_point
     HIPCHK(hipStreamSynchronize(h->stream));
     const int64_t n = cnt < max_points ? cnt : max_points;
     if (n > 0) HIPCHK(hipMemcpy(xyz_out, d_out, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(d_out);
     if (n_written) *n_written = n;
     return PTL_OK;
 }
@@ -703,7 +679,7 @@ extern "C" int ptl_icp_linear_system(ptl_icp* h, const double* src_world, int64_
     { int rcj = icp_join_map(h); if (rcj) return rcj; }
     HIPCHK(hipMemcpyAsync(c.src_cur, src_world, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
     k_set_gn<<<1, 64, 0, h->stream>>>(c, (int)n, max_dist, kernel, nullptr);
-    if (c.P == 20) k_gn_loop<20, false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 1); else k_gn_loop<0, false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 1);
+    pick_p(c.P, [&](auto pc) { k_gn_loop<pc(), false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 1); });
     double out[32];
     HIPCHK(hipMemcpyAsync(out, (char*)c.st + offsetof(DevState, dbg_sums), sizeof out, hipMemcpyDeviceToHost, h->stream));
     int rc = icp_check_flags(h);
@@ -723,7 +699,7 @@ extern "C" int ptl_icp_align(ptl_icp* h, const double* frame, int64_t n, const d
     HIPCHK(hipMemcpyAsync(c.src0, frame, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_ext, guess, 128, hipMemcpyHostToDevice, h->stream));
     k_set_gn<<<1, 64, 0, h->stream>>>(c, (int)n, max_dist, kernel, h->d_ext);
-    if (c.P == 20) k_gn_loop<20, false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 2); else k_gn_loop<0, false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 2);  // new_pose = T_icp * guess, trajectory untouched
+    pick_p(c.P, [&](auto pc) { k_gn_loop<pc(), false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 2); });  // new_pose = T_icp * guess, trajectory untouched
     DevState st;
     HIPCHK(hipMemcpyAsync(&st, c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
     int rc = icp_check_flags(h);
@@ -806,11 +782,7 @@ extern "C" int ptl_icp_profile(ptl_icp* h, int enable, double* gn_ms_total, int6
     if (!h) return set_err(PTL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipStreamSynchronize(h->stream));
-    icp_collect_profile(h);
-    if (gn_ms_total) *gn_ms_total = h->gn_ms;
-    if (gn_launches) *gn_launches = h->gn_launches;
-    if (reset) { h->gn_ms = 0; h->gn_launches = 0; }
-    h->prof = enable != 0;
+    h->prof.report(enable, gn_ms_total, gn_launches, reset);
     h->prof_every = enable > 1 ? enable : 1;
     return PTL_OK;
 }
@@ -837,32 +809,22 @@ extern "C" int ptl_lut_create(int device_id, int32_t H, int32_t W, const double*
             }
         memcpy(T, R, sizeof T);
     }
-    ptl_lut* l = new ptl_lut();
-    l->device_id = device_id; l->H = H; l->W = W; l->dir = nullptr; l->off = nullptr;
+    std::unique_ptr<ptl_lut> l(new ptl_lut());  // (an error return below deletes it, and with it what it has allocated)
+    l->device_id = device_id; l->H = H; l->W = W;
     double* d_tmp = nullptr;
+    DevOwner tmp;
     const size_t n = (size_t)H * W;
-    if (dalloc(&l->dir, 3 * n) != hipSuccess || dalloc(&l->off, 3 * n) != hipSuccess || dalloc(&d_tmp, (size_t)2 * H + 16) != hipSuccess) {
-        if (l->dir) (void)hipFree(l->dir);
-        if (l->off) (void)hipFree(l->off);
-        delete l;
-        return set_err(PTL_ERR_HIP, "LUT allocation failed");
-    }
+    l->mem.add(&l->dir, 3 * n); l->mem.add(&l->off, 3 * n); tmp.add(&d_tmp, (size_t)2 * H + 16);
+    if (l->mem.err != hipSuccess || tmp.err != hipSuccess) return set_err(PTL_ERR_HIP, "LUT allocation failed");
     HIPCHK(hipMemcpy(d_tmp, beam_altitude_deg, (size_t)H * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_tmp + H, beam_azimuth_deg, (size_t)H * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_tmp + 2 * H, T, sizeof T, hipMemcpyHostToDevice));
     k_build_lut<<<(int)((n + 255) / 256), 256>>>(H, W, d_tmp, d_tmp + H, lidar_origin_to_beam_origin_mm, d_tmp + 2 * H, l->dir, l->off);
     HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(d_tmp);
-    *out = l;
+    *out = l.release();
     return PTL_OK;
 }
-extern "C" int ptl_lut_destroy(ptl_lut* l) {
-    if (!l) return PTL_OK;
-    (void)hipSetDevice(l->device_id);
-    (void)hipFree(l->dir); (void)hipFree(l->off);
-    delete l;
-    return PTL_OK;
-}
+extern "C" int ptl_lut_destroy(ptl_lut* l) { return l ? handle_destroy(l, l->device_id) : PTL_OK; }
 // XYZLut.__call__: range image -> (H*W, 3) f64 xyz in metres (RANGE == 0 -> (0,0,0))
 __global__ __launch_bounds__(256) void k_lut_apply(int n, const unsigned* range, const double* dir, const double* off, double* xyz) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -877,13 +839,23 @@ extern "C" int ptl_lut_apply(ptl_lut* l, const uint32_t* range_mm, double* xyz_o
     const size_t n = (size_t)l->H * l->W;
     unsigned* d_r = nullptr;
     double* d_x = nullptr;
-    HIPCHK(dalloc(&d_r, n));
-    HIPCHK(dalloc(&d_x, 3 * n));
+    DevOwner tmp;
+    HIPCHK(tmp.alloc(&d_r, n));
+    HIPCHK(tmp.alloc(&d_x, 3 * n));
     HIPCHK(hipMemcpy(d_r, range_mm, n * 4, hipMemcpyHostToDevice));
     k_lut_apply<<<(int)((n + 255) / 256), 256>>>((int)n, d_r, l->dir, l->off, d_x);
     HIPCHK(hipMemcpy(xyz_out, d_x, n * 24, hipMemcpyDeviceToHost));
-    (void)hipFree(d_r); (void)hipFree(d_x);
     return PTL_OK;
+}
+// rows np.linspace(0, H, beams_num, endpoint=False, dtype=int), that is (int)(i * (H / beams_num)), marked 1 among H
+static std::vector<unsigned char> beam_mask(int H, int beams_num) {
+    std::vector<unsigned char> m((size_t)H, 0);
+    const double step = (double)H / (double)beams_num;
+    for (int i = 0; i < beams_num; ++i) {
+        const int r = (int)((double)i * step);
+        if (r >= 0 && r < H) m[(size_t)r] = 1;
+    }
+    return m;
 }
 // StreamStatsTracker.trackScan's reduction (reference ins/data.py:284-308) on a range image given by the host
 extern "C" int ptl_range_stats(int device_id, const uint32_t* range, int32_t H, int32_t W, int32_t beams_num,
@@ -895,24 +867,17 @@ extern "C" int ptl_range_stats(int device_id, const uint32_t* range, int32_t H, 
     unsigned* d_r = nullptr;
     unsigned char* d_m = nullptr;
     double* d_o = nullptr;
-    HIPCHK(dalloc(&d_r, n));
-    HIPCHK(dalloc(&d_o, 5));
+    DevOwner tmp;
+    HIPCHK(tmp.alloc(&d_r, n));
+    HIPCHK(tmp.alloc(&d_o, 5));
     HIPCHK(hipMemcpy(d_r, range, n * 4, hipMemcpyHostToDevice));
-    if (beams_num > 0) {  // np.linspace(0, H, num, endpoint=False, dtype=int) (:288-293)
-        std::vector<unsigned char> m((size_t)H, 0);
-        const double step = (double)H / (double)beams_num;
-        for (int i = 0; i < beams_num; ++i) {
-            const int r = (int)((double)i * step);
-            if (r >= 0 && r < H) m[(size_t)r] = 1;
-        }
-        HIPCHK(hipMalloc((void**)&d_m, (size_t)H));
-        HIPCHK(hipMemcpy(d_m, m.data(), (size_t)H, hipMemcpyHostToDevice));
+    if (beams_num > 0) {  // (:288-293)
+        HIPCHK(tmp.alloc(&d_m, (size_t)H));
+        HIPCHK(hipMemcpy(d_m, beam_mask(H, beams_num).data(), (size_t)H, hipMemcpyHostToDevice));
     }
     k_range_stats<<<1, 1024>>>(d_r, H, W, d_m, range_to_m, d_o);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out5, d_o, 40, hipMemcpyDeviceToHost));
-    (void)hipFree(d_r); (void)hipFree(d_o);
-    if (d_m) (void)hipFree(d_m);
     return PTL_OK;
 }
 // reduce_active_beams (reference utils.py:328-341): rows np.linspace(0, H, beams, endpoint=False, dtype=int) stay
@@ -921,16 +886,10 @@ extern "C" int ptl_icp_set_active_beams(ptl_icp* h, int32_t H, int32_t beams_num
     if (!h || H < 1) return set_err(PTL_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_row_mask) { (void)hipFree(h->d_row_mask); h->d_row_mask = nullptr; }
+    h->mem.release(&h->d_row_mask);
     if (beams_num <= 0) return PTL_OK;
-    std::vector<unsigned char> m((size_t)H, 0);
-    const double step = (double)H / (double)beams_num;  // numpy linspace(0, H, num, endpoint=False): i * (H / num)
-    for (int i = 0; i < beams_num; ++i) {
-        const int r = (int)((double)i * step);
-        if (r >= 0 && r < H) m[(size_t)r] = 1;
-    }
-    HIPCHK(hipMalloc((void**)&h->d_row_mask, (size_t)H));
-    HIPCHK(hipMemcpy(h->d_row_mask, m.data(), (size_t)H, hipMemcpyHostToDevice));
+    HIPCHK(h->mem.alloc(&h->d_row_mask, (size_t)H));
+    HIPCHK(hipMemcpy(h->d_row_mask, beam_mask(H, beams_num).data(), (size_t)H, hipMemcpyHostToDevice));
     return PTL_OK;
 }
 // KissICPWrapper.register_frame on a raw range image (reference kiss.py:54-74): XYZLut + RANGE != 0 mask + pipeline
@@ -975,24 +934,18 @@ extern "C" int ptl_traj_poses_at(int device_id, const double* knot_ts, const dou
     if (n == 0) return PTL_OK;
     double *d_kt = nullptr, *d_kp = nullptr, *d_ts = nullptr, *d_out = nullptr;
     int* d_cnt = nullptr;
-    hipError_t e = dalloc(&d_kt, (size_t)n_knots);
-    if (e == hipSuccess) e = dalloc(&d_kp, (size_t)n_knots * 16);
-    if (e == hipSuccess) e = dalloc(&d_ts, (size_t)n);
-    if (e == hipSuccess) e = dalloc(&d_out, (size_t)n * 16);
-    if (e == hipSuccess) e = dalloc(&d_cnt, 1);
-    if (e == hipSuccess) e = hipMemcpy(d_kt, knot_ts, (size_t)n_knots * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_kp, knot_poses16, (size_t)n_knots * 128, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ts, ts, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, sizeof(int));
+    DevOwner tmp;
+    tmp.add(&d_kt, (size_t)n_knots); tmp.add(&d_kp, (size_t)n_knots * 16);
+    tmp.add(&d_ts, (size_t)n); tmp.add(&d_out, (size_t)n * 16); tmp.add(&d_cnt, 1);
+    HIPCHK(tmp.err);
+    HIPCHK(hipMemcpy(d_kt, knot_ts, (size_t)n_knots * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_kp, knot_poses16, (size_t)n_knots * 128, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ts, ts, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_cnt, 0, sizeof(int)));
     int outside = 0;
-    if (e == hipSuccess) {
-        k_traj_poses_at<<<(int)((n + 255) / 256), 256>>>(d_kt, d_kp, (int)n_knots, bound_before, bound_after, d_ts, (int)n, d_out, d_cnt);
-        e = hipMemcpy(poses16_out, d_out, (size_t)n * 128, hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipMemcpy(&outside, d_cnt, sizeof(int), hipMemcpyDeviceToHost);
-    for (void* q : {(void*)d_kt, (void*)d_kp, (void*)d_ts, (void*)d_out, (void*)d_cnt})
-        if (q) (void)hipFree(q);
-    if (e != hipSuccess) return set_err(PTL_ERR_HIP, "ptl_traj_poses_at: %s", hipGetErrorString(e));
+    k_traj_poses_at<<<(int)((n + 255) / 256), 256>>>(d_kt, d_kp, (int)n_knots, bound_before, bound_after, d_ts, (int)n, d_out, d_cnt);
+    HIPCHK(hipMemcpy(poses16_out, d_out, (size_t)n * 128, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&outside, d_cnt, sizeof(int), hipMemcpyDeviceToHost));
     if (n_outside) *n_outside = outside;
     return PTL_OK;
 }
@@ -1024,22 +977,16 @@ extern "C" int ptl_lut_dewarp(ptl_lut* l, const uint32_t* range_mm, const double
     unsigned* d_r = nullptr;
     double *d_x = nullptr, *d_p = nullptr;
     int* d_c = nullptr;
-    hipError_t e = dalloc(&d_r, n);
-    if (e == hipSuccess) e = dalloc(&d_x, 3 * n);
-    if (e == hipSuccess) e = dalloc(&d_p, (size_t)l->W * 16);
-    if (e == hipSuccess) e = dalloc(&d_c, 1);
-    if (e == hipSuccess) e = hipMemcpy(d_r, range_mm, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_p, col_poses16, (size_t)l->W * 128, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_c, 0, sizeof(int));
+    DevOwner tmp;
+    tmp.add(&d_r, n); tmp.add(&d_x, 3 * n); tmp.add(&d_p, (size_t)l->W * 16); tmp.add(&d_c, 1);
+    HIPCHK(tmp.err);
+    HIPCHK(hipMemcpy(d_r, range_mm, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_p, col_poses16, (size_t)l->W * 128, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_c, 0, sizeof(int)));
     int cnt = 0;
-    if (e == hipSuccess) {
-        k_dewarp<<<(int)((n + 255) / 256), 256>>>(l->H, l->W, d_r, l->dir, l->off, d_p, d_x, d_c);
-        e = hipMemcpy(xyz_out, d_x, n * 24, hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipMemcpy(&cnt, d_c, sizeof(int), hipMemcpyDeviceToHost);
-    for (void* q : {(void*)d_r, (void*)d_x, (void*)d_p, (void*)d_c})
-        if (q) (void)hipFree(q);
-    if (e != hipSuccess) return set_err(PTL_ERR_HIP, "ptl_lut_dewarp: %s", hipGetErrorString(e));
+    k_dewarp<<<(int)((n + 255) / 256), 256>>>(l->H, l->W, d_r, l->dir, l->off, d_p, d_x, d_c);
+    HIPCHK(hipMemcpy(xyz_out, d_x, n * 24, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&cnt, d_c, sizeof(int), hipMemcpyDeviceToHost));
     if (n_valid) *n_valid = cnt;
     return PTL_OK;
 }
@@ -1047,21 +994,21 @@ extern "C" int ptl_lut_dewarp(ptl_lut* l, const uint32_t* range_mm, const double
 // ================================================================================================ EKF
 struct ptl_ekf {
     ptl_ekf_cfg cfg;
-    hipStream_t stream;
-    bool own_stream;
-    EkfState* st;
-    double* d_buf;  // staging: imu rows / pose / cov
-    int64_t buf_rows;
+    Stream stream;  // its own, or borrowed from the runner it is a member of
+    EkfState* st = nullptr;
+    double* d_buf = nullptr;  // staging: imu rows / pose / cov
+    int64_t buf_rows = 1024;
     // fixed-interval smoother (ptl_ekf_log_enable): the history log in HBM, the backward pass's outputs, its job and status words
-    double* d_log;
-    int64_t log_cap;
-    double* d_sm;  // [cap][16] poses | [cap] t | [cap][19] nav | [cap][324] P^s
-    EkfSmoothJob job;
-    EkfSmoothJob* d_job;
-    long long* d_info;
+    double* d_log = nullptr;
+    int64_t log_cap = 0;
+    double* d_sm = nullptr;  // [cap][16] poses | [cap] t | [cap][19] nav | [cap][324] P^s
+    EkfSmoothJob job = {};
+    EkfSmoothJob* d_job = nullptr;
+    long long* d_info = nullptr;
     // IMU deskew knot list (ptl_ekf_knots_enable)
-    double* d_knots;
-    int64_t knot_cap;
+    double* d_knots = nullptr;
+    int64_t knot_cap = 0;
+    DevOwner mem;
 };
 
 extern "C" int ptl_ekf_default_cfg(ptl_ekf_cfg* cfg) {
@@ -1079,42 +1026,32 @@ static int ekf_reset(ptl_ekf* h) {
     HIPCHK(hipGetLastError());
     return PTL_OK;
 }
+// the device buffers a filter is created with: `m` allocates them (h->mem) or only counts their bytes
+static void ekf_alloc(DevOwner& m, ptl_ekf* h) {
+    m.add(&h->st, 1);
+    m.add(&h->d_buf, (size_t)h->buf_rows * 7 + 64);
+}
 static int ekf_create_impl(const ptl_ekf_cfg* cfg, hipStream_t shared, ptl_ekf** out) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
     ABI_CHECK(ptl_ekf_cfg, cfg);
     if (ptl_device_count() <= cfg->device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", cfg->device_id);
     HIPCHK(hipSetDevice(cfg->device_id));
-    ptl_ekf* h = new ptl_ekf();
+    std::unique_ptr<ptl_ekf> owner(new ptl_ekf());
+    ptl_ekf* h = owner.get();
     h->cfg = *cfg;
-    h->own_stream = shared == nullptr;
-    h->stream = shared;
-    h->st = nullptr; h->d_buf = nullptr; h->buf_rows = 1024;
-    h->d_knots = nullptr; h->knot_cap = 0;
-    if (h->own_stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return set_err(PTL_ERR_HIP, "stream"); }
-    if (dalloc(&h->st, 1) != hipSuccess || dalloc(&h->d_buf, (size_t)h->buf_rows * 7 + 64) != hipSuccess) {
-        if (h->st) (void)hipFree(h->st);
-        delete h;
-        return set_err(PTL_ERR_HIP, "device allocation failed");
-    }
-    int rc = PTL_OK;
-    if (hipMemsetAsync(h->st, 0, sizeof(EkfState), h->stream) != hipSuccess) rc = set_err(PTL_ERR_HIP, "memset");  // smoother log off
+    if (shared) h->stream.borrow(shared);
+    else if (h->stream.create() != hipSuccess) return set_err(PTL_ERR_HIP, "stream");
+    ekf_alloc(h->mem, h);
+    int rc = h->mem.err == hipSuccess ? PTL_OK : set_err(PTL_ERR_HIP, "device allocation failed");
+    if (rc == PTL_OK && hipMemsetAsync(h->st, 0, sizeof(EkfState), h->stream) != hipSuccess) rc = set_err(PTL_ERR_HIP, "memset");  // smoother log off
     if (rc == PTL_OK) rc = ekf_reset(h);
     if (rc == PTL_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = set_err(PTL_ERR_HIP, "sync");
-    if (rc) { (void)hipFree(h->st); (void)hipFree(h->d_buf); delete h; return rc; }
-    *out = h;
+    if (rc) return rc;
+    *out = owner.release();
     return PTL_OK;
 }
 extern "C" int ptl_ekf_create(const ptl_ekf_cfg* cfg, ptl_ekf** out) { return ekf_create_impl(cfg, nullptr, out); }
-extern "C" int ptl_ekf_destroy(ptl_ekf* h) {
-    if (!h) return PTL_OK;
-    (void)hipSetDevice(h->cfg.device_id);
-    (void)hipFree(h->st); (void)hipFree(h->d_buf);
-    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info, (void*)h->d_knots})
-        if (p) (void)hipFree(p);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return PTL_OK;
-}
+extern "C" int ptl_ekf_destroy(ptl_ekf* h) { return h ? handle_destroy(h, h->cfg.device_id) : PTL_OK; }
 // n IMU rows -> the filter's predicts, staged through d_buf buf_rows at a time with a wait for the buffer's reuse; wait_last = false leaves
 // the last buf_rows or fewer in flight for the caller's own wait
 static int ekf_stage_imu(ptl_ekf* h, const double* imu, int64_t n, bool wait_last) {
@@ -1188,9 +1125,7 @@ __global__ void k_ekf_log_set(EkfState* e, double* log, long long cap) {
     if (t == 0) { e->log = log; e->log_cap = cap; e->log_count = 0; e->log_overflow = 0; }
 }
 static void ekf_log_free(ptl_ekf* h) {
-    for (void* p : {(void*)h->d_log, (void*)h->d_sm, (void*)h->d_job, (void*)h->d_info})
-        if (p) (void)hipFree(p);
-    h->d_log = nullptr; h->d_sm = nullptr; h->d_job = nullptr; h->d_info = nullptr;
+    h->mem.release(&h->d_log); h->mem.release(&h->d_sm); h->mem.release(&h->d_job); h->mem.release(&h->d_info);
     h->log_cap = 0;
 }
 // capacity > 0: a fresh, empty log of that many updates (the old one, if any, is dropped); 0: off.  The caller's other streams must be idle.
@@ -1202,8 +1137,8 @@ static int ekf_log_set(ptl_ekf* h, int64_t cap) {
     ekf_log_free(h);
     if (cap <= 0) return PTL_OK;
     const size_t c = (size_t)cap;
-    if (dalloc(&h->d_log, c * EKF_LOG_STRIDE) != hipSuccess || dalloc(&h->d_sm, c * 360) != hipSuccess ||
-        dalloc(&h->d_job, 1) != hipSuccess || dalloc(&h->d_info, 2) != hipSuccess) {
+    if (h->mem.alloc(&h->d_log, c * EKF_LOG_STRIDE) != hipSuccess || h->mem.alloc(&h->d_sm, c * 360) != hipSuccess ||
+        h->mem.alloc(&h->d_job, 1) != hipSuccess || h->mem.alloc(&h->d_info, 2) != hipSuccess) {
         ekf_log_free(h);
         return set_err(PTL_ERR_HIP, "smoother log allocation failed (%lld entries, %.1f MB)", (long long)cap, cap * (EKF_LOG_STRIDE + 360) * 8 / 1e6);
     }
@@ -1293,10 +1228,10 @@ static int ekf_knots_set(ptl_ekf* h, int64_t cap) {
     k_ekf_knots_set<<<1, 64, 0, h->stream>>>(h->st, nullptr, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_knots) (void)hipFree(h->d_knots);
-    h->d_knots = nullptr; h->knot_cap = 0;
+    h->mem.release(&h->d_knots);
+    h->knot_cap = 0;
     if (cap <= 0) return PTL_OK;
-    if (dalloc(&h->d_knots, (size_t)cap * EKF_KNOT_STRIDE) != hipSuccess) return set_err(PTL_ERR_HIP, "knot list allocation failed (%lld knots)", (long long)cap);
+    if (h->mem.alloc(&h->d_knots, (size_t)cap * EKF_KNOT_STRIDE) != hipSuccess) return set_err(PTL_ERR_HIP, "knot list allocation failed (%lld knots)", (long long)cap);
     h->knot_cap = cap;
     k_ekf_knots_set<<<1, 64, 0, h->stream>>>(h->st, h->d_knots, (long long)cap);
     HIPCHK(hipGetLastError());
@@ -1410,19 +1345,20 @@ static int icp_ekf_step_impl(ptl_icp* h, ptl_ekf* e, const double* imu_rows, int
             const int64_t cap = h->dk_cap > 0 ? 2 * h->dk_cap : h->traj_cap;
             double* nt = nullptr;
             int* nm = nullptr;
-            HIPCHK(dalloc(&nt, (size_t)cap * 2));
-            HIPCHK(dalloc(&nm, (size_t)cap));
+            DevOwner tmp;
+            HIPCHK(tmp.alloc(&nt, (size_t)cap * 2));
+            HIPCHK(tmp.alloc(&nm, (size_t)cap));
             HIPCHK(hipMemset(nm, 0, (size_t)cap * sizeof(int)));
             HIPCHK(hipStreamSynchronize(h->stream));
             if (h->dk_modes) HIPCHK(hipMemcpy(nm, h->dk_modes, (size_t)h->dk_cap * sizeof(int), hipMemcpyDeviceToDevice));
-            if (h->dk_t0t1) (void)hipFree(h->dk_t0t1);
-            if (h->dk_modes) (void)hipFree(h->dk_modes);
-            h->dk_t0t1 = nt; h->dk_modes = nm; h->dk_cap = cap;
+            h->mem.replace(&h->dk_t0t1, tmp, nt);
+            h->mem.replace(&h->dk_modes, tmp, nm);
+            h->dk_cap = cap;
         }
     }
     if (!h->ev_step_guess) {
-        HIPCHK(hipEventCreateWithFlags(&h->ev_step_guess, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_step_gn, hipEventDisableTiming));
+        HIPCHK(h->ev_step_guess.create());
+        HIPCHK(h->ev_step_gn.create());
     }
     hipStream_t es = e->stream;
     // processImu x n_imu (ptl_ekf_process_imu_batch's kernel).  Any count is served, like the call-by-call loop (a long IMU-only prefix,
@@ -1507,6 +1443,8 @@ struct SeqLane {
     double* d_dk_t0t1 = nullptr;    // [n_scans][2]
     int* d_dk_modes = nullptr;      // [n_scans]
     bool dk_times = false;
+    DevOwner mem;  // the lane's own buffers
+    ~SeqLane() { delete icp; delete ekf; }  // (the runner has set the device; its streams, which the two borrow, outlive the lane)
 };
 
 // what ptl_seq_create and ptl_batch_create check and settle alike: `out` = *cfg with room for a whole sweep in the registration and the
@@ -1523,27 +1461,40 @@ static int seq_cfg_settle(const ptl_seq_cfg* cfg, ptl_seq_cfg* out) {
     out->ekf.device_id = cfg->icp.device_id;
     return PTL_OK;
 }
-static void lane_free(SeqLane& l) {
-    if (l.icp) icp_free(l.icp);
-    if (l.ekf) ptl_ekf_destroy(l.ekf);
-    for (void* p : {(void*)l.d_scans, (void*)l.d_imu, (void*)l.d_imu_end, (void*)l.d_res_poses, (void*)l.d_res_t, (void*)l.d_rows,
-                    (void*)l.d_dk_t0t1, (void*)l.d_dk_modes})
-        if (p) (void)hipFree(p);
+// a lane's own device buffers for a settled configuration (`slots` sweep slots of `slot_bytes` each, the IMU rows, the result rows; a batch
+// member: the IMU split on the device): `m` allocates them (l.mem) or only counts their bytes
+static void lane_alloc(DevOwner& m, SeqLane& l, const ptl_seq_cfg& cfg, size_t slot_bytes, size_t slots, bool batch) {
+    const size_t n = (size_t)cfg.n_scans, nim = cfg.n_imu > 0 ? (size_t)cfg.n_imu : 1;
+    m.add((unsigned char**)&l.d_scans, slots * slot_bytes);
+    m.add(&l.d_imu, nim * 7);
+    m.add(&l.d_res_poses, n * 16); m.add(&l.d_res_t, n); m.add(&l.d_rows, n * 8);
+    if (batch) m.add(&l.d_imu_end, n);
+}
+// device bytes one member of a batch asks for - its registration (*icp_bytes), its filter and the lane's own buffers: the three allocation
+// functions over an owner that only counts, on handles that are settled and never created
+static size_t lane_footprint_bytes(const ptl_seq_cfg& cfg, size_t slot_bytes, size_t slots, size_t* icp_bytes) {
+    DevOwner count(true);
+    ptl_icp icp;
+    ptl_ekf ekf;
+    SeqLane l;
+    icp_settle(&icp, &cfg.icp);
+    icp_alloc(count, &icp, icp_traj_rows(cfg.n_scans, true));
+    *icp_bytes = count.requested();
+    ekf_alloc(count, &ekf);
+    lane_alloc(count, l, cfg, slot_bytes, slots, true);
+    return count.requested();
 }
 // the registration (on `stream`), the filter (on `ekf_stream`), `slots` sweep slots of `slot_bytes` each, the IMU rows and the result rows of
 // a settled configuration.  batch: a member of a batch (icp_create_impl's batch_member, the whole trajectory up front, the IMU split on the device)
 static int lane_create(SeqLane& l, const ptl_seq_cfg& cfg, hipStream_t stream, hipStream_t ekf_stream, size_t slot_bytes, size_t slots, bool batch,
                        const char* who) {
-    int rc = icp_create_impl(&cfg.icp, stream, &l.icp, batch);
+    int rc = icp_create_impl(&cfg.icp, stream, &l.icp, batch, icp_traj_rows(cfg.n_scans, batch));
     if (rc == PTL_OK) rc = ekf_create_impl(&cfg.ekf, ekf_stream, &l.ekf);
-    while (batch && rc == PTL_OK && l.icp->traj_cap < cfg.n_scans) rc = icp_grow_traj(l.icp);
     if (rc) return rc;
-    const size_t n = (size_t)cfg.n_scans, nim = cfg.n_imu > 0 ? (size_t)cfg.n_imu : 1;
-    if (hipMalloc((void**)&l.d_scans, slots * slot_bytes) != hipSuccess || dalloc(&l.d_imu, nim * 7) != hipSuccess ||
-        dalloc(&l.d_res_poses, n * 16) != hipSuccess || dalloc(&l.d_res_t, n) != hipSuccess || dalloc(&l.d_rows, n * 8) != hipSuccess ||
-        (batch && (dalloc(&l.d_imu_end, n) != hipSuccess || hipMemset(l.d_imu_end, 0, n * sizeof(int)) != hipSuccess)))
+    lane_alloc(l.mem, l, cfg, slot_bytes, slots, batch);
+    if (l.mem.err != hipSuccess || (batch && hipMemset(l.d_imu_end, 0, l.mem.bytes_of(l.d_imu_end)) != hipSuccess))
         return set_err(PTL_ERR_HIP, "%s: allocation failed (%.1f MB of sweeps per sequence)", who, slots * slot_bytes / 1e6);
-    l.imu_end.assign(n, 0);
+    l.imu_end.assign((size_t)cfg.n_scans, 0);
     return PTL_OK;
 }
 // the IMU rows and their split over the scans.  one_per_scan: at least one sample between consecutive scans - lockstep batching cannot
@@ -1623,7 +1574,7 @@ static int lane_dk_set(SeqLane& l, int64_t n_scans, int64_t knot_capacity) {
     int rc = dk_wire(l.icp, nullptr, nullptr, nullptr, 0);
     if (rc == PTL_OK) rc = ekf_knots_set(l.ekf, 0);
     if (rc || knot_capacity <= 0) return rc;
-    if ((!l.d_dk_t0t1 && dalloc(&l.d_dk_t0t1, 2 * n) != hipSuccess) || (!l.d_dk_modes && dalloc(&l.d_dk_modes, n) != hipSuccess))
+    if ((!l.d_dk_t0t1 && l.mem.alloc(&l.d_dk_t0t1, 2 * n) != hipSuccess) || (!l.d_dk_modes && l.mem.alloc(&l.d_dk_modes, n) != hipSuccess))
         return set_err(PTL_ERR_HIP, "IMU deskew: allocation failed");
     HIPCHK(hipMemset(l.d_dk_modes, 0, n * sizeof(int)));
     rc = ekf_knots_set(l.ekf, knot_capacity);
@@ -1666,52 +1617,37 @@ static int lane_deskew_modes(const SeqLane& l, const ptl_seq_cfg& cfg, bool dk_o
 // ================================================================================================ sequence runner
 struct ptl_seq {
     ptl_seq_cfg cfg;
-    hipStream_t stream = nullptr;
+    Stream stream;
     // The EKF launches run on their own stream: the update with scan k's pose and the IMU predicts up to scan k+1
     // overlap scan k's map update and scan k+1's deskew / downsampling; only the GN kernel waits for the EKF
     // (its guess), and the EKF waits for the GN kernel (the pose measurement).
-    hipStream_t ekf_stream = nullptr;
-    hipEvent_t ev_guess = nullptr, ev_gn = nullptr;
+    Stream ekf_stream;
+    Event ev_guess, ev_gn;
+    Event ev_pro;  // IMU deskew: the event the prologue waits for
     SeqLane lane;  // sweep slots: [n_scans][pps][3] f32
     std::vector<int64_t> scan_of_out;  // scan index of each processed output
     int64_t n_out = 0;
     int64_t next_scan = 0, imus_per_scan = 0;  // driver-loop position (ekf_bench.py:491-518)
     ptl_lut* lut = nullptr;          // non-null => sweeps were uploaded as u32 range images
     std::vector<unsigned char> is_range;
-    // IMU deskew (ptl_seq_imu_deskew_enable): on, and the event the prologue waits for
-    bool dk_on = false;
-    hipEvent_t ev_pro = nullptr;
+    bool dk_on = false;  // IMU deskew (ptl_seq_imu_deskew_enable)
 };
 
-extern "C" int ptl_seq_destroy(ptl_seq* s) {
-    if (!s) return PTL_OK;
-    (void)hipSetDevice(s->cfg.icp.device_id);
-    lane_free(s->lane);
-    for (hipEvent_t e : {s->ev_guess, s->ev_gn, s->ev_pro})
-        if (e) (void)hipEventDestroy(e);
-    if (s->ekf_stream) (void)hipStreamDestroy(s->ekf_stream);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-    return PTL_OK;
-}
+extern "C" int ptl_seq_destroy(ptl_seq* s) { return s ? handle_destroy(s, s->cfg.icp.device_id) : PTL_OK; }
 extern "C" int ptl_seq_create(const ptl_seq_cfg* cfg, ptl_seq** out) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
     ptl_seq_cfg c;
     int rc = seq_cfg_settle(cfg, &c);
     if (rc) return rc;
-    ptl_seq* s = new ptl_seq();
+    std::unique_ptr<ptl_seq> owner(new ptl_seq());
+    ptl_seq* s = owner.get();
     s->cfg = c;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&s->ekf_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_guess, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_gn, hipEventDisableTiming) != hipSuccess) {
-        ptl_seq_destroy(s);
+    if (s->stream.create() != hipSuccess || s->ekf_stream.create() != hipSuccess || s->ev_guess.create() != hipSuccess || s->ev_gn.create() != hipSuccess)
         return set_err(PTL_ERR_HIP, "stream / event creation failed");
-    }
     rc = lane_create(s->lane, c, s->stream, s->ekf_stream, (size_t)c.points_per_scan * 12, (size_t)c.n_scans, false, "ptl_seq_create");
-    if (rc) { ptl_seq_destroy(s); return rc; }
+    if (rc) return rc;
     s->is_range.assign((size_t)c.n_scans, 0);
-    *out = s;
+    *out = owner.release();
     return PTL_OK;
 }
 extern "C" int ptl_seq_upload_scan(ptl_seq* s, int64_t k, const float* xyz) {
@@ -1876,7 +1812,7 @@ extern "C" int ptl_seq_imu_deskew_enable(ptl_seq* s, int32_t on, int64_t knot_ca
     HIPCHK(hipStreamSynchronize(s->lane.icp->map_stream));
     HIPCHK(hipStreamSynchronize(s->ekf_stream));
     s->dk_on = false;
-    if (on && !s->ev_pro) HIPCHK(hipEventCreateWithFlags(&s->ev_pro, hipEventDisableTiming));
+    if (on && !s->ev_pro) HIPCHK(s->ev_pro.create());
     rc = lane_dk_set(s->lane, s->cfg.n_scans, on ? knot_capacity : 0);
     HIPCHK(hipStreamSynchronize(s->stream));
     s->dk_on = on && rc == PTL_OK;
@@ -1945,13 +1881,20 @@ extern "C" int ptl_seq_profile(ptl_seq* s, int enable, double* gn_ms_total, int6
 struct ptl_batch {
     ptl_seq_cfg cfg;
     int S = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     // the map update and the filter step of scan k run on `side` beside K0-K4 of scan k + 1 (both need only the GN result);
     // the GN launch of scan k + 1 waits for them
-    hipStream_t side = nullptr;
-    hipEvent_t ev_gn = nullptr, ev_side = nullptr;
+    Stream side;
+    Event ev_gn, ev_side;
     bool ev_side_valid = false;
-    SeqLane lane[GN_MAX_SEQ];    // sweep slots: [ring][pps][3] f32, or [ring][pps] u32 with range_input
+    // IMU deskew (ptl_batch_imu_deskew_enable): on for every sequence (their sweep times and modes: the lanes); the lockstep driver's prologue
+    // waits for `ev_filter`, recorded behind the filter step
+    bool dk_on = false;
+    Event ev_filter;
+    bool ev_filter_valid = false;
+    GnTimer prof;                // the dominant kernel's launches
+    DevOwner mem;                // the batch's own buffers and the pinned flag words
+    SeqLane lane[GN_MAX_SEQ];    // sweep slots: [ring][pps][3] f32, or [ring][pps] u32 with range_input (declared behind what must outlive the lanes)
     unsigned* d_bar = nullptr;   // [SEQ_MAX_TEAMS][64] barrier counters and job words of the free-running kernel's teams
     SeqSched* d_sched = nullptr; // [8] its per-XCD scan schedulers
     int *d_flags = nullptr, *h_flags = nullptr;  // [GN_MAX_SEQ + 1] error flags of every sequence + the status word, gathered by k_finish_all (h_flags: pinned)
@@ -1976,21 +1919,11 @@ struct ptl_batch {
     std::atomic<int64_t> up_hi[GN_MAX_SEQ] = {};
     std::atomic<int64_t> done_scans{0};
     bool ctx_dirty = true;
-    bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    double gn_ms = 0;
-    int64_t gn_launches = 0;
     // fixed-interval smoother (ptl_batch_smoother_enable): one k_ekf_smooth job per sequence, their status words side by side
     EkfSmoothJob* d_sm_jobs = nullptr;
     long long* d_sm_info = nullptr;
     std::vector<long long> h_sm_info;
     bool sm_done = false;  // the last ptl_batch_smooth succeeded and nothing ran since
-    // IMU deskew (ptl_batch_imu_deskew_enable): on for every sequence (their sweep times and modes: the lanes); the lockstep driver's prologue
-    // waits for `ev_filter`, recorded behind the filter step
-    bool dk_on = false;
-    hipEvent_t ev_filter = nullptr;
-    bool ev_filter_valid = false;
 };
 
 // launch geometry: workgroups per team.  Lockstep (kx_assign): one team per sequence, 1 / 2 / 4 per XCD.  Free-running: 1 / 2 / 4
@@ -2004,14 +1937,6 @@ static int batch_gseq(const ptl_batch* b) {
     const int g = J / (b->S <= 128 ? 8 : 16);
     return g < 1 ? 1 : g;
 }
-template <int GC>
-static hipError_t seq_run_occupancy(bool p20, int threads, int* per_cu) {
-    return p20 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kx_seq_run<20, GC>, threads, 0)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kx_seq_run<0, GC>, threads, 0);
-}
-// the instance of a template <int PC, int GC> kernel for `gseq` workgroups per team: GC = gseq when that is 32 / 16 / 8 / 4 / 2 / 1, else 0
-#define GC_DISPATCH(gseq, CALL) do { switch (gseq) { case 32: CALL(32); break; case 16: CALL(16); break; case 8: CALL(8); break; \
-    case 4: CALL(4); break; case 2: CALL(2); break; case 1: CALL(1); break; default: CALL(0); break; } } while (0)
 // every workgroup of the persistent launch has to be resident (they wait for each other); a team needs a workgroup
 // beside the filter's
 static int batch_check_seq_run(ptl_batch* b) {
@@ -2025,33 +1950,17 @@ static int batch_check_seq_run(ptl_batch* b) {
     if (b->cfg.n_scans >= 65535) return set_err(PTL_ERR_ARG, "free-running batches run at most 65534 scans per sequence (look-back tags of the compaction passes)");
     if (b->cfg.with_ekf && ic.gn_threads < 384) return set_err(PTL_ERR_ARG, "free-running batches with a filter need gn_threads >= 384 (the filter step maps one thread to each of the 324 covariance cells)");
     int per_cu = 0, cus = 0;
-    const bool p20 = ic.max_points_per_voxel == 20;
     hipError_t e = hipSuccess;
-#define OCC(GC) e = seq_run_occupancy<GC>(p20, ic.gn_threads, &per_cu)
-    GC_DISPATCH(gseq, OCC);
-#undef OCC
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ic.device_id);
+    pick_p(ic.max_points_per_voxel, [&](auto pc) {
+        pick_team<32, 16, 8, 4, 2, 1>(gseq, [&](auto gc) { e = resident_capacity(kx_seq_run<pc(), gc()>, ic.gn_threads, ic.device_id, &per_cu, &cus); });
+    });
     if (e != hipSuccess) return set_err(PTL_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(e));
     if ((int64_t)per_cu * cus < ic.gn_workgroups)
         return set_err(PTL_ERR_STATE, "free-running batch: %d workgroups x %d threads cannot be co-resident on device %d (%d CUs x %d per CU): lower gn_workgroups",
                        ic.gn_workgroups, ic.gn_threads, ic.device_id, cus, per_cu);
     return PTL_OK;
 }
-extern "C" int ptl_batch_destroy(ptl_batch* b) {
-    if (!b) return PTL_OK;
-    (void)hipSetDevice(b->cfg.icp.device_id);
-    for (int s = 0; s < b->S; ++s) lane_free(b->lane[s]);
-    for (void* p : {(void*)b->d_ctx, (void*)b->d_bar, (void*)b->d_sched, (void*)b->d_status, (void*)b->d_flags, (void*)b->d_sm_jobs, (void*)b->d_sm_info})
-        if (p) (void)hipFree(p);
-    if (b->h_flags) (void)hipHostFree(b->h_flags);
-    for (hipEvent_t e : b->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {b->ev_gn, b->ev_side, b->ev_filter})
-        if (e) (void)hipEventDestroy(e);
-    if (b->side) (void)hipStreamDestroy(b->side);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-    return PTL_OK;
-}
+extern "C" int ptl_batch_destroy(ptl_batch* b) { return b ? handle_destroy(b, b->cfg.icp.device_id) : PTL_OK; }
 extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl_batch** out) {
     if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
     if (n_sequences < 1 || n_sequences > GN_MAX_SEQ) return set_err(PTL_ERR_ARG, "n_sequences must be in [1, %d]", GN_MAX_SEQ);
@@ -2063,18 +1972,21 @@ extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl
     const int64_t ring = (c.resident_scans > 0 && c.resident_scans < c.n_scans) ? c.resident_scans : c.n_scans;
     const size_t slot = (size_t)c.points_per_scan * (c.range_input ? 4 : 12);  // resident bytes of a sweep
     {   // the whole batch has to fit the device: say so here, with numbers, instead of failing part-way through the allocations
-        const size_t per_seq = icp_footprint_bytes(&c.icp) + (size_t)ring * slot + (size_t)(c.n_imu > 0 ? c.n_imu : 1) * 56 + (size_t)c.n_scans * (128 + 8 + 64 + 4) + (64u << 10);
+        // (what a member's allocation functions ask for, plus slack for the granularity of the runtime's own allocations)
+        size_t icp_bytes = 0;
+        const size_t per_seq = lane_footprint_bytes(c, slot, (size_t)ring, &icp_bytes) + (1u << 20) + (64u << 10);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * (size_t)n_sequences > free_b)
             return set_err(PTL_ERR_CAPACITY, "batch of %d sequences needs %.1f GB of device memory (%.0f MB per sequence: %.0f MB of work buffers, map table "
                            "and block pool, %.0f MB of sweeps), %.1f GB are free of %.1f GB: fewer sequences, fewer resident sweeps or a smaller map_block_capacity",
-                           n_sequences, per_seq * (double)n_sequences / 1e9, per_seq / 1e6, icp_footprint_bytes(&c.icp) / 1e6,
+                           n_sequences, per_seq * (double)n_sequences / 1e9, per_seq / 1e6, icp_bytes / 1e6,
                            (double)ring * slot / 1e6, free_b / 1e9, total_b / 1e9);
     }
     const bool free_running = c.icp.gn_lanes_per_point == 8;
     if (!free_running && c.icp.map_small_blocks > 0) return set_err(PTL_ERR_ARG, "map_small_blocks (two block classes) needs the free-running driver (gn_lanes_per_point = 8)");
     if (ring < c.n_scans && !free_running) return set_err(PTL_ERR_ARG, "resident_scans (the sweep ring) is served by the free-running driver (gn_lanes_per_point = 8)");
-    ptl_batch* b = new ptl_batch();
+    std::unique_ptr<ptl_batch> owner(new ptl_batch());
+    ptl_batch* b = owner.get();
     b->cfg = c;
     b->S = n_sequences;
     b->free_running = free_running;
@@ -2086,20 +1998,20 @@ extern "C" int ptl_batch_create(const ptl_seq_cfg* cfg, int32_t n_sequences, ptl
         b->balance_margin = (m && *m) ? atoi(m) : 1;
         if (b->balance_margin < -1 || b->balance_margin > 4096) b->balance_margin = 1;
     }
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&b->ev_gn, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b->ev_side, hipEventDisableTiming) != hipSuccess) {
-        ptl_batch_destroy(b);
+    if (b->stream.create() != hipSuccess || b->side.create() != hipSuccess || b->ev_gn.create() != hipSuccess || b->ev_side.create() != hipSuccess)
         return set_err(PTL_ERR_HIP, "stream / event creation failed");
-    }
     for (int s = 0; s < b->S && rc == PTL_OK; ++s) rc = lane_create(b->lane[s], c, b->stream, b->stream, slot, (size_t)ring, true, "ptl_batch_create");
-    if (rc == PTL_OK && (dalloc(&b->d_ctx, (size_t)GN_MAX_SEQ) != hipSuccess || dalloc(&b->d_bar, (size_t)SEQ_MAX_TEAMS * 64) != hipSuccess || dalloc(&b->d_sched, (size_t)8) != hipSuccess ||
-                         dalloc(&b->d_status, (size_t)16) != hipSuccess || hipMemset(b->d_status, 0, 16 * sizeof(unsigned)) != hipSuccess ||
-                         dalloc(&b->d_flags, (size_t)GN_MAX_SEQ + 1) != hipSuccess || hipHostMalloc((void**)&b->h_flags, (size_t)(GN_MAX_SEQ + 1) * sizeof(int)) != hipSuccess))
-        rc = set_err(PTL_ERR_HIP, "batch allocation failed");
+    if (rc == PTL_OK) {
+        DevOwner& m = b->mem;
+        m.add(&b->d_ctx, (size_t)GN_MAX_SEQ); m.add(&b->d_bar, (size_t)SEQ_MAX_TEAMS * 64); m.add(&b->d_sched, (size_t)8);
+        m.add(&b->d_status, (size_t)16);
+        m.add(&b->d_flags, (size_t)GN_MAX_SEQ + 1); m.add_pinned(&b->h_flags, (size_t)GN_MAX_SEQ + 1);
+        if (m.err != hipSuccess || hipMemset(b->d_status, 0, m.bytes_of(b->d_status)) != hipSuccess) rc = set_err(PTL_ERR_HIP, "batch allocation failed");
+    }
     // (the free-running driver's own limits - co-residency of the persistent grid, team size - are checked when that driver is
     // chosen or first used: a batch that is switched to lockstep right after creation must not be refused on them)
-    if (rc) { ptl_batch_destroy(b); return rc; }
-    *out = b;
+    if (rc) return rc;
+    *out = owner.release();
     return PTL_OK;
 }
 // Sweep ring (resident_scans < n_scans): sweeps arrive in order, and sweep k may take its slot (k % ring) only when the scan that used the slot
@@ -2211,6 +2123,26 @@ __global__ void k_ring_rebase(SeqCtx* a, int S, long long delta_floats) {
     const int s = (int)threadIdx.x;
     if (s < S) a[s].scan_base += delta_floats;
 }
+// The filter's argument block for the `ns` sequences from `l` on: each filter's IMU rows from where it stands (imu_pos) up to the samples
+// before scan `stop_scan` (< 0: none), and where it stands moves there.  out_row >= 0: the step starts with the update by the registration's
+// pose of that output row and writes that row of the results.  Returns whether any sequence has samples to run.
+static bool ekf_args_fill(EkfBatchArgs& ea, SeqLane* l, int ns, int64_t stop_scan, int64_t out_row = -1) {
+    memset(&ea, 0, sizeof ea);
+    bool any = false;
+    for (int q = 0; q < ns; ++q, ++l) {
+        const int64_t i1 = stop_scan >= 0 ? l->imu_end[(size_t)stop_scan] : l->imu_pos;
+        ea.e[q] = l->ekf->st; ea.imu[q] = l->d_imu;
+        ea.i0[q] = (int)l->imu_pos; ea.i1[q] = (int)i1;
+        any = any || i1 > l->imu_pos;
+        if (out_row >= 0) {
+            ea.pose[q] = l->icp->c.traj + 16 * out_row;
+            ea.out_pose[q] = l->d_res_poses + 16 * out_row; ea.out_t[q] = l->d_res_t + out_row; ea.out_row8[q] = l->d_rows + 8 * out_row;
+        }
+        if (out_row >= 0 || i1 > l->imu_pos) l->imu_pos = i1;
+    }
+    ea.update_first = out_row >= 0 ? 1 : 0;
+    return any;
+}
 // free-running driver: the scans [next_scan, next_scan + n) of every sequence in launches of up to scans_per_launch scans
 static int batch_enqueue_free(ptl_batch* b, int64_t n) {
     const bool with_ekf = b->cfg.with_ekf != 0;
@@ -2237,28 +2169,13 @@ static int batch_enqueue_free(ptl_batch* b, int64_t n) {
         if (with_ekf) {  // IMU samples before the first scan of the launch that the filter has not seen (a run's first scan)
             for (int s0 = 0; s0 < S; s0 += EKF_MAX_SEQ) {  // (the argument block holds EKF_MAX_SEQ sequences)
                 EkfBatchArgs ea;
-                memset(&ea, 0, sizeof ea);
-                bool any = false;
                 const int ns = S - s0 < EKF_MAX_SEQ ? S - s0 : EKF_MAX_SEQ;
-                for (int q = 0; q < ns; ++q) {
-                    const int s = s0 + q;
-                    ea.e[q] = b->lane[s].ekf->st; ea.imu[q] = b->lane[s].d_imu;
-                    ea.i0[q] = (int)b->lane[s].imu_pos; ea.i1[q] = (int)b->lane[s].imu_end[(size_t)k0];
-                    any = any || ea.i1[q] > ea.i0[q];
-                    if (b->lane[s].imu_end[(size_t)k0] > b->lane[s].imu_pos) b->lane[s].imu_pos = b->lane[s].imu_end[(size_t)k0];
-                }
-                if (any) kb_ekf_step<<<ns, 384, 0, st>>>(ea);
+                if (ekf_args_fill(ea, b->lane + s0, ns, k0)) kb_ekf_step<<<ns, 384, 0, st>>>(ea);
             }
         }
         HIPCHK(hipMemsetAsync(b->d_bar, 0, (size_t)SEQ_MAX_TEAMS * 64 * sizeof(unsigned), st));
         k_sched_init<<<1, 8 * SEQ_SLOTS, 0, st>>>(b->d_sched, S, (int)k0, (int)k1);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (b->prof) {
-            if (b->ev_used + 2 > b->ev.size())
-                for (int q = 0; q < 2; ++q) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); b->ev.push_back(e); }
-            e0 = b->ev[b->ev_used++]; e1 = b->ev[b->ev_used++];
-            HIPCHK(hipEventRecord(e0, st));
-        }
+        HIPCHK(b->prof.begin(st));
         SeqRun r;
         r.S = S; r.k0 = (int)k0; r.k1 = (int)k1; r.with_ekf = with_ekf ? 1 : 0; r.rebuild_every = ic.rebuild_every;
         const int gseq = batch_gseq(b);
@@ -2266,12 +2183,10 @@ static int batch_enqueue_free(ptl_batch* b, int64_t n) {
         r.um_alt = b->um_alt;
         r.balance_margin = b->balance_margin;
         r.force_agent = b->force_agent; r.dbg_dead_block = b->dbg_dead_block; r.dbg_dead_round = b->dbg_dead_round;
-        const bool p20 = ic.max_points_per_voxel == 20;
-#define KXR(GC) do { if (p20) kx_seq_run<20, GC><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, r, b->d_sched, b->d_bar, b->d_status); \
-                     else kx_seq_run<0, GC><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, r, b->d_sched, b->d_bar, b->d_status); } while (0)
-        GC_DISPATCH(gseq, KXR);
-#undef KXR
-        if (b->prof) HIPCHK(hipEventRecord(e1, st));
+        pick_p(ic.max_points_per_voxel, [&](auto pc) {
+            pick_team<32, 16, 8, 4, 2, 1>(gseq, [&](auto gc) { kx_seq_run<pc(), gc()><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, r, b->d_sched, b->d_bar, b->d_status); });
+        });
+        HIPCHK(b->prof.end(st));
         // did every sequence reach scan k1?  (a team may have left the launch while holding one: no exit is silent)
         k_sched_check<<<1, 8 * SEQ_SLOTS, 0, st>>>(b->d_ctx, b->d_sched, S, (int)k1, b->d_status);
         for (int s = 0; s < S; ++s) {
@@ -2347,15 +2262,7 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
     for (int64_t k = b->next_scan; k < end; ++k) {
         if (with_ekf) {  // IMU samples before the first scan of a run (later ones ride on the previous scan's EKF launch)
             EkfBatchArgs ea;
-            memset(&ea, 0, sizeof ea);
-            bool any = false;
-            for (int s = 0; s < S; ++s) {
-                ea.e[s] = b->lane[s].ekf->st; ea.imu[s] = b->lane[s].d_imu;
-                ea.i0[s] = (int)b->lane[s].imu_pos; ea.i1[s] = (int)b->lane[s].imu_end[(size_t)k];
-                any = any || ea.i1[s] > ea.i0[s];
-                b->lane[s].imu_pos = b->lane[s].imu_end[(size_t)k] > b->lane[s].imu_pos ? b->lane[s].imu_end[(size_t)k] : b->lane[s].imu_pos;
-            }
-            if (any) {
+            if (ekf_args_fill(ea, b->lane, S, k)) {
                 if (b->ev_side_valid) HIPCHK(hipStreamWaitEvent(st, b->ev_side, 0));
                 kb_ekf_step<<<S, 384, 0, st>>>(ea);
             }
@@ -2371,40 +2278,21 @@ extern "C" int ptl_batch_enqueue(ptl_batch* b, int64_t n) {
         kb_count_w2<<<dim3(nb, S), 256, 0, st>>>(b->d_ctx, ki);
         kb_compact_src<<<dim3(nb, S), 256, 0, st>>>(b->d_ctx, ki);
         if (b->ev_side_valid) HIPCHK(hipStreamWaitEvent(st, b->ev_side, 0));  // the previous scan's map update and filter step
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (b->prof) {
-            if (b->ev_used + 2 > b->ev.size())
-                for (int q = 0; q < 2; ++q) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); b->ev.push_back(e); }
-            e0 = b->ev[b->ev_used++]; e1 = b->ev[b->ev_used++];
-            HIPCHK(hipEventRecord(e0, st));
-        }
+        HIPCHK(b->prof.begin(st));
         // one sequence per XCD: workgroups with blockIdx & 7 == s run sequence s's loop with gn_workgroups / 8 workgroups
-        if (ic.gn_lanes_per_point == 8) {
+        pick_p(ic.max_points_per_voxel, [&](auto pc) {
             const int gseq = (ic.gn_workgroups / 8) / (S <= 8 ? 1 : S <= 16 ? 2 : 4);  // workgroups per sequence
-            const bool p20 = ic.max_points_per_voxel == 20;
-#define KX8(GC) do { if (p20) kx_gn_loop8<20, GC><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki); \
-                     else kx_gn_loop8<0, GC><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki); } while (0)
-            GC_DISPATCH(gseq, KX8);
-#undef KX8
-        } else if (ic.max_points_per_voxel == 20) kx_gn_loop<20><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki);
-        else kx_gn_loop<0><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki);
-        if (b->prof) HIPCHK(hipEventRecord(e1, st));
+            if (ic.gn_lanes_per_point == 8) pick_team<32, 16, 8, 4, 2, 1>(gseq, [&](auto gc) { kx_gn_loop8<pc(), gc()><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki); });
+            else kx_gn_loop<pc()><<<ic.gn_workgroups, ic.gn_threads, 0, st>>>(b->d_ctx, S, ki);
+        });
+        HIPCHK(b->prof.end(st));
         HIPCHK(hipEventRecord(b->ev_gn, st));
         hipStream_t sd = b->side;
         HIPCHK(hipStreamWaitEvent(sd, b->ev_gn, 0));
         const int64_t o = b->n_out;
         if (with_ekf) {  // first: its pose is the next scan's guess
             EkfBatchArgs ea;
-            memset(&ea, 0, sizeof ea);
-            for (int s = 0; s < S; ++s) {
-                const int64_t e2 = (k + 1 < b->cfg.n_scans) ? b->lane[s].imu_end[(size_t)k + 1] : b->lane[s].imu_pos;
-                ea.e[s] = b->lane[s].ekf->st; ea.imu[s] = b->lane[s].d_imu;
-                ea.i0[s] = (int)b->lane[s].imu_pos; ea.i1[s] = (int)e2;
-                ea.pose[s] = b->lane[s].icp->c.traj + 16 * o;
-                ea.out_pose[s] = b->lane[s].d_res_poses + 16 * o; ea.out_t[s] = b->lane[s].d_res_t + o; ea.out_row8[s] = b->lane[s].d_rows + 8 * o;
-                b->lane[s].imu_pos = e2;
-            }
-            ea.update_first = 1;
+            ekf_args_fill(ea, b->lane, S, (k + 1 < b->cfg.n_scans) ? k + 1 : -1, o);
             kb_ekf_step<<<S, 384, 0, sd>>>(ea);
             if (b->dk_on) { HIPCHK(hipEventRecord(b->ev_filter, sd)); b->ev_filter_valid = true; }
         }
@@ -2451,13 +2339,9 @@ extern "C" int ptl_batch_wait(ptl_batch* b) {
     b->done_scans = b->next_scan;  // (every launch enqueued so far is through: their sweep slots may be overwritten)
     const int* flags = b->h_flags;
     const unsigned status = (unsigned)b->h_flags[GN_MAX_SEQ];
-    for (size_t i = 0; i + 1 < b->ev_used; i += 2) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, b->ev[i], b->ev[i + 1]) == hipSuccess) { b->gn_ms += ms; b->gn_launches++; }
-    }
-    b->ev_used = 0;
+    b->prof.collect();
     for (int s = 0; s < b->S; ++s)
-        if (flags[s]) return set_err(PTL_ERR_CAPACITY, "sequence %d: device capacity/error flags 0x%x (1 key range, 2 block pool, 4 map table, 8 vds table, 16 gn barrier timeout); batch status 0x%x", s, flags[s], status);
+        if (flags[s]) return set_err(PTL_ERR_CAPACITY, "sequence %d: " ERR_FLAGS_FMT "; batch status 0x%x", s, flags[s], status);
     // no sequence carries an error, but a team of the free-running kernel left a launch early (a workgroup that never reached a
     // barrier; teams that never got work): the scans are complete, the launch was not healthy - said, not swallowed
     // (a team that only ran out of its idle budget while the last sequences were in other teams' hands - bit 4 alone, every sequence at its last
@@ -2544,8 +2428,8 @@ extern "C" int ptl_batch_smoother_enable(ptl_batch* b, int32_t on) {
     HIPCHK(hipStreamSynchronize(b->side));
     HIPCHK(hipStreamSynchronize(b->stream));
     b->sm_done = false;
-    if (b->d_sm_jobs) { (void)hipFree(b->d_sm_jobs); b->d_sm_jobs = nullptr; }
-    if (b->d_sm_info) { (void)hipFree(b->d_sm_info); b->d_sm_info = nullptr; }
+    b->mem.release(&b->d_sm_jobs);
+    b->mem.release(&b->d_sm_info);
     for (int s = 0; s < b->S; ++s) {
         int rc = ekf_log_set(b->lane[s].ekf, on ? b->cfg.n_scans : 0);
         if (rc) {
@@ -2554,7 +2438,7 @@ extern "C" int ptl_batch_smoother_enable(ptl_batch* b, int32_t on) {
         }
     }
     if (!on) return PTL_OK;
-    if (dalloc(&b->d_sm_jobs, (size_t)b->S) != hipSuccess || dalloc(&b->d_sm_info, (size_t)b->S * 2) != hipSuccess) {
+    if (b->mem.alloc(&b->d_sm_jobs, (size_t)b->S) != hipSuccess || b->mem.alloc(&b->d_sm_info, (size_t)b->S * 2) != hipSuccess) {
         for (int q = 0; q < b->S; ++q) (void)ekf_log_set(b->lane[q].ekf, 0);
         return set_err(PTL_ERR_HIP, "smoother job allocation failed");
     }
@@ -2610,7 +2494,7 @@ extern "C" int ptl_batch_imu_deskew_enable(ptl_batch* b, int32_t on, int64_t kno
     HIPCHK(hipStreamSynchronize(b->stream));
     b->dk_on = false;
     b->ev_filter_valid = false;
-    if (on && !b->ev_filter) HIPCHK(hipEventCreateWithFlags(&b->ev_filter, hipEventDisableTiming));
+    if (on && !b->ev_filter) HIPCHK(b->ev_filter.create());
     for (int s = 0; s < b->S; ++s) {  // every sequence off first: a failure leaves none half on
         rc = lane_dk_set(b->lane[s], b->cfg.n_scans, 0);
         if (rc) return rc;
@@ -2680,10 +2564,7 @@ extern "C" int ptl_batch_profile(ptl_batch* b, int enable, double* gn_ms_total, 
     if (!b) return set_err(PTL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(b->cfg.icp.device_id));
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (gn_ms_total) *gn_ms_total = b->gn_ms;
-    if (gn_launches) *gn_launches = b->gn_launches;
-    if (reset) { b->gn_ms = 0; b->gn_launches = 0; }
-    b->prof = enable != 0;
+    b->prof.report(enable, gn_ms_total, gn_launches, reset);
     return PTL_OK;
 }
 
@@ -2759,14 +2640,15 @@ const char* rccl_why() { return g_rccl_why; }
     } while (0)
 
 struct ptl_comm {
-    ncclComm_t comm;
-    int world, rank, device_id;
-    hipStream_t stream;
+    ncclComm_t comm = nullptr;
+    int world = 0, rank = 0, device_id = 0;
+    Stream stream;
     // staging of the gather, kept between calls (grow-only): send [per_rank], recv [world x per_rank] on the device, the host mirror of recv
-    double *d_send, *d_recv;
-    size_t cap_send, cap_recv;
+    double *d_send = nullptr, *d_recv = nullptr;
+    size_t cap_send = 0, cap_recv = 0;
     std::vector<double> host;
-    bool broken;  // a local failure aborted the communicator (ncclCommAbort): the peers' collective fails instead of hanging, every later call is refused
+    bool broken = false;  // a local failure aborted the communicator (ncclCommAbort): the peers' collective fails instead of hanging, every later call is refused
+    DevOwner mem;
 };
 extern "C" int ptl_comm_unique_id(uint8_t id[PTL_COMM_ID_BYTES]) {
     if (!id) return set_err(PTL_ERR_ARG, "null argument");
@@ -2784,19 +2666,15 @@ extern "C" int ptl_comm_create(const uint8_t id[PTL_COMM_ID_BYTES], int32_t worl
     RcclApi* api = rccl_api();
     if (!api) return set_err(PTL_ERR_STATE, "%s", rccl_why());
     HIPCHK(hipSetDevice(device_id));
-    ptl_comm* c = new ptl_comm();
-    c->comm = nullptr; c->world = world; c->rank = rank; c->device_id = device_id; c->stream = nullptr;
-    c->d_send = nullptr; c->d_recv = nullptr; c->cap_send = 0; c->cap_recv = 0; c->broken = false;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return set_err(PTL_ERR_HIP, "stream creation failed"); }
+    std::unique_ptr<ptl_comm> owner(new ptl_comm());
+    ptl_comm* c = owner.get();
+    c->world = world; c->rank = rank; c->device_id = device_id;
+    if (c->stream.create() != hipSuccess) return set_err(PTL_ERR_HIP, "stream creation failed");
     ncclUniqueId u;
     memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
     ncclResult_t r = api->CommInitRank(&c->comm, world, u, rank);  // (collective: returns when every rank has called it)
-    if (r != ncclSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return set_err(PTL_ERR_HIP, "ncclCommInitRank(world %d, rank %d, device %d): %s", world, rank, device_id, api->GetErrorString(r));
-    }
-    *out = c;
+    if (r != ncclSuccess) return set_err(PTL_ERR_HIP, "ncclCommInitRank(world %d, rank %d, device %d): %s", world, rank, device_id, api->GetErrorString(r));
+    *out = owner.release();
     return PTL_OK;
 }
 extern "C" int ptl_comm_destroy(ptl_comm* c) {
@@ -2805,9 +2683,6 @@ extern "C" int ptl_comm_destroy(ptl_comm* c) {
     (void)hipSetDevice(c->device_id);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (api && c->comm && !c->broken) (void)api->CommDestroy(c->comm);
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PTL_OK;
 }
@@ -2834,15 +2709,15 @@ extern "C" int ptl_gather_trajectories(ptl_comm* c, const double* d_rows, int64_
     HIPCHK(hipSetDevice(c->device_id));
     const size_t per_rank = (size_t)S * (size_t)T * 8 + (size_t)S, all = per_rank * (size_t)c->world;
     if (c->cap_send < per_rank) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        c->d_send = nullptr; c->cap_send = 0;
-        if (dalloc(&c->d_send, per_rank) != hipSuccess) return comm_fail(c, api, set_err(PTL_ERR_HIP, "gather buffer allocation failed (%.1f MB)", per_rank * 8 / 1e6));
+        c->mem.release(&c->d_send);
+        c->cap_send = 0;
+        if (c->mem.alloc(&c->d_send, per_rank) != hipSuccess) return comm_fail(c, api, set_err(PTL_ERR_HIP, "gather buffer allocation failed (%.1f MB)", per_rank * 8 / 1e6));
         c->cap_send = per_rank;
     }
     if (c->cap_recv < all) {
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_recv = nullptr; c->cap_recv = 0;
-        if (dalloc(&c->d_recv, all) != hipSuccess) return comm_fail(c, api, set_err(PTL_ERR_HIP, "gather buffer allocation failed (%.1f MB)", all * 8 / 1e6));
+        c->mem.release(&c->d_recv);
+        c->cap_recv = 0;
+        if (c->mem.alloc(&c->d_recv, all) != hipSuccess) return comm_fail(c, api, set_err(PTL_ERR_HIP, "gather buffer allocation failed (%.1f MB)", all * 8 / 1e6));
         c->cap_recv = all;
     }
     if (c->host.size() < all + (size_t)S) c->host.resize(all + (size_t)S);
@@ -2885,7 +2760,8 @@ extern "C" int ptl_batch_gather_trajectories(ptl_batch* b, ptl_comm* c, double* 
     HIPCHK(hipStreamSynchronize(b->stream));
     const int64_t S = b->S, T = b->cfg.n_scans;
     double* d_rows = nullptr;
-    HIPCHK(dalloc(&d_rows, (size_t)S * T * 8));
+    DevOwner tmp;
+    HIPCHK(tmp.alloc(&d_rows, (size_t)S * T * 8));
     std::vector<int64_t> counts((size_t)S, b->n_out < T ? b->n_out : T);
     hipError_t e = hipMemsetAsync(d_rows, 0, (size_t)S * T * 64, b->stream);
     for (int64_t s = 0; s < S && e == hipSuccess; ++s) {
@@ -2895,20 +2771,19 @@ extern "C" int ptl_batch_gather_trajectories(ptl_batch* b, ptl_comm* c, double* 
         else { k_kiss_rows<<<(int)((n + 63) / 64), 64, 0, b->stream>>>(b->lane[s].icp->c.traj, (int)n, d_rows + (size_t)s * T * 8); e = hipGetLastError(); }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    if (e != hipSuccess) { (void)hipFree(d_rows); return set_err(PTL_ERR_HIP, "row staging failed: %s", hipGetErrorString(e)); }
-    const int rc = ptl_gather_trajectories(c, d_rows, S, T, counts.data(), rows_out, counts_out);
-    (void)hipFree(d_rows);
-    return rc;
+    if (e != hipSuccess) return set_err(PTL_ERR_HIP, "row staging failed: %s", hipGetErrorString(e));
+    return ptl_gather_trajectories(c, d_rows, S, T, counts.data(), rows_out, counts_out);
 }
 
 // ================================================================================================ posed scans into the map
 // The world map of a run, built on the device: a trajectory resident as knots, sweeps taken from where they already are (the caller's
 // host buffer once, or a runner's resident slots), every pass on the MAP handle's stream and in the map handle's buffers (fly_kernels.h).
 struct ptl_traj {
-    int device_id;  // (first member: the one-device rule is tested by changing it)
-    int n;
-    double *d_kt, *d_kp;
-    double before, after;
+    int device_id = 0;  // (first member: the one-device rule is tested by changing it)
+    int n = 0;
+    double *d_kt = nullptr, *d_kp = nullptr;
+    double before = 0, after = 0;
+    DevOwner mem;
 };
 extern "C" int ptl_traj_create(int device_id, const double* knot_ts, const double* knot_poses16, int64_t n_knots, double bound_before,
                                double bound_after, ptl_traj** out) {
@@ -2919,28 +2794,17 @@ extern "C" int ptl_traj_create(int device_id, const double* knot_ts, const doubl
         if (!(knot_ts[i] > knot_ts[i - 1])) return set_err(PTL_ERR_ARG, "knot timestamps must increase strictly (knot %lld)", (long long)i);
     if (device_id < 0 || ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
     HIPCHK(hipSetDevice(device_id));
-    ptl_traj* t = new ptl_traj();
-    t->device_id = device_id; t->n = (int)n_knots; t->d_kt = nullptr; t->d_kp = nullptr; t->before = bound_before; t->after = bound_after;
-    hipError_t e = dalloc(&t->d_kt, (size_t)n_knots);
-    if (e == hipSuccess) e = dalloc(&t->d_kp, (size_t)n_knots * 16);
+    std::unique_ptr<ptl_traj> t(new ptl_traj());
+    t->device_id = device_id; t->n = (int)n_knots; t->before = bound_before; t->after = bound_after;
+    t->mem.add(&t->d_kt, (size_t)n_knots); t->mem.add(&t->d_kp, (size_t)n_knots * 16);
+    hipError_t e = t->mem.err;
     if (e == hipSuccess) e = hipMemcpy(t->d_kt, knot_ts, (size_t)n_knots * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(t->d_kp, knot_poses16, (size_t)n_knots * 128, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ptl_traj_destroy(t);
-        return set_err(PTL_ERR_HIP, "ptl_traj_create: %s", hipGetErrorString(e));
-    }
-    *out = t;
+    if (e != hipSuccess) { (void)hipGetLastError(); return set_err(PTL_ERR_HIP, "ptl_traj_create: %s", hipGetErrorString(e)); }
+    *out = t.release();
     return PTL_OK;
 }
-extern "C" int ptl_traj_destroy(ptl_traj* t) {
-    if (!t) return PTL_OK;
-    if (t->d_kt || t->d_kp) (void)hipSetDevice(t->device_id);
-    if (t->d_kt) (void)hipFree(t->d_kt);
-    if (t->d_kp) (void)hipFree(t->d_kp);
-    delete t;
-    return PTL_OK;
-}
+extern "C" int ptl_traj_destroy(ptl_traj* t) { return t ? handle_destroy(t, t->device_id) : PTL_OK; }
 // what every posed-scan entry point checks (before any HIP call) and sets up: one device, the map handle's geometry, its FlyWs, and its
 // stream ordered behind a map update that may still run
 static int fly_prepare(ptl_icp* h, const ptl_traj* t, const ptl_lut* lut, int64_t H, int64_t W, const char* who) {
@@ -2951,7 +2815,7 @@ static int fly_prepare(ptl_icp* h, const ptl_traj* t, const ptl_lut* lut, int64_
     if (H * W > h->n_max) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the map handle's max_points_per_scan is %lld", who, (long long)(H * W), (long long)h->n_max);
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (!h->d_fly) {
-        HIPCHK(dalloc(&h->d_fly, 1));
+        HIPCHK(h->mem.alloc(&h->d_fly, 1));
         HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), h->stream));
     }
     return icp_join_map(h);
