@@ -50,10 +50,11 @@ extern "C" {
 #define PTL_CFG_EKF 1
 #define PTL_CFG_SEQ 2
 #define PTL_CFG_ICP_STATS 3
+#define PTL_CFG_PKT_FORMAT 4
 #define PTL_CFG_INIT(cfg_ptr) do { memset((cfg_ptr), 0, sizeof *(cfg_ptr)); (cfg_ptr)->struct_size = (uint32_t)sizeof *(cfg_ptr); (cfg_ptr)->abi_version = PTL_ABI_VERSION; } while (0)
 int ptl_abi_version(void);
-/* the library's sizeof for PTL_CFG_ICP / _EKF / _SEQ / _ICP_STATS (the three configuration structs and the per-scan counter row);
- * -1 for an unknown id */
+/* the library's sizeof for PTL_CFG_ICP / _EKF / _SEQ / _ICP_STATS (the three configuration structs and the per-scan counter row) and
+ * PTL_CFG_PKT_FORMAT (ptl_pkt_format); -1 for an unknown id */
 int64_t ptl_sizeof_cfg(int which);
 
 const char *ptl_last_error(void);
@@ -557,6 +558,61 @@ int ptl_seq_map_build(ptl_seq *s, ptl_icp *map, ptl_traj *t, const double *t0t1,
                       int64_t *n_skipped);
 int ptl_batch_map_build(ptl_batch *b, int32_t seq, ptl_icp *map, ptl_traj *t, const double *t0t1, int64_t first, int64_t last,
                         int64_t *n_valid, int64_t *n_skipped);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ouster lidar packets decoded on the device (what ouster-sdk's PacketFormat / ScanBatcher / LidarScan do for the
+ * reference's feed, data.py:31-77 - third party, restated from the published packet layouts).  The host decides which packets form a
+ * sweep (2 bytes read per packet, `sweep_of_packet`); the device turns the column-major payloads into the staggered range image
+ * u32[H][W] in mm (column = measurement_id), the column timestamps u64[W] in ns, the column status words u16[W] (LEGACY: the low half
+ * of its 32-bit status) and one summary record per sweep.  A column counts only with status bit 0 set and measurement_id < W; what no
+ * counted column supplies is 0; of two counted columns of a sweep with one measurement_id the later in arrival order wins (the owner is
+ * resolved before anything is written); otherwise the result does not depend on the order of the packets.
+ * ---------------------------------------------------------------------------------------------- */
+#define PTL_PKT_LEGACY 0                        /* 16-B column header, 12-B pixels (range: 20 bits), 32-bit status behind the pixels */
+#define PTL_PKT_RNG19_RFL8_SIG16_NIR16 1        /* 32-B packet header and footer, 12-B column header, 12-B pixels (range: 19 bits) */
+#define PTL_PKT_RNG15_RFL8_NIR8 2               /* ... 4-B pixels, range: 15 bits in units of 8 mm */
+#define PTL_PKT_RNG19_RFL8_SIG16_NIR16_DUAL 3   /* ... 16-B pixels, the FIRST return's range: 19 bits */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(ptl_pkt_format) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    int32_t profile;             /* PTL_PKT_* */
+    int32_t pixels_per_column;   /* H */
+    int32_t columns_per_frame;   /* W */
+    int32_t columns_per_packet;  /* C, <= 64 */
+} ptl_pkt_format;
+typedef struct {
+    uint32_t frame_id;         /* of the sweep's first packet in arrival order (0: the sweep got no packet) */
+    uint32_t valid_columns;    /* image columns supplied by a counted packet column */
+    uint32_t first_valid_id;   /* lowest / highest measurement_id among them (0 when there is none) ... */
+    uint32_t last_valid_id;
+    uint64_t first_valid_ts;   /* ... and their timestamps, ns; last_valid_ts is ouster client.last_valid_column_ts */
+    uint64_t last_valid_ts;
+    uint32_t nonzero_ranges;   /* pixels of the image with a return */
+    uint32_t ignored_columns;  /* packet columns with status bit 0 set and measurement_id >= W */
+} ptl_pkt_summary;
+/* bytes of one lidar packet of that format (24896 / 24832 / 8448 / 33024 for H = 128, C = 16), < 0 on a refused format (struct_size /
+ * abi_version mismatch, unknown profile, H, W or C < 1, C > 64, a packet above 60 KB) */
+int64_t ptl_pkt_packet_bytes(const ptl_pkt_format *fmt);
+typedef struct ptl_pktdec ptl_pktdec;
+/* a decoder for up to max_packets packets and max_sweeps sweeps per call: owns its stream and its device staging */
+int ptl_pktdec_create(const ptl_pkt_format *fmt, int32_t device_id, int64_t max_packets, int32_t max_sweeps, ptl_pktdec **out);
+int ptl_pktdec_destroy(ptl_pktdec *d);
+/* packets: n packets in HOST memory (pageable, or page-locked with ptl_host_pin), packet i at packets + i * stride_bytes; the buffer and the
+ * stride are 4-byte aligned, stride_bytes >= the packet size.  sweep_of_packet[i] in [0, n_sweeps) or < 0 = not part of any sweep.
+ * Outputs (host, any may be NULL): range_out n_sweeps x H x W, col_ts_out n_sweeps x W, col_status_out n_sweeps x W, summary_out
+ * n_sweeps.  Arguments are checked before any HIP call. */
+int ptl_pktdec_decode(ptl_pktdec *d, const void *packets, int64_t stride_bytes, int64_t n, const int32_t *sweep_of_packet, int32_t n_sweeps,
+                      uint32_t *range_out, uint64_t *col_ts_out, uint16_t *col_status_out, ptl_pkt_summary *summary_out);
+/* profiling: HIP-event time of the device work of the decoder's calls (the initialisation and the three passes, not the copies) since the last
+ * reset, and the number of calls timed; like ptl_icp_profile */
+int ptl_pktdec_profile(ptl_pktdec *d, int enable, double *ms_total, int64_t *calls, int reset);
+/* Sweep k of a runner that takes range images, decoded from its n packets (tightly packed: stride = the packet size) straight into the
+ * sweep's slot: afterwards the slot holds byte for byte what ptl_*_upload_range of the decoded image leaves, and the host never built the
+ * image.  Preconditions and sweep-ring order errors of ptl_*_upload_range; the decoder's H W must be the runner's points_per_scan and both
+ * live on one device (else PTL_ERR_ARG).  summary (1 record) and col_ts (W) are nullable. */
+int ptl_seq_upload_packets(ptl_seq *s, ptl_pktdec *dec, int64_t k, const void *packets, int64_t n, ptl_pkt_summary *summary, uint64_t *col_ts);
+int ptl_batch_upload_packets(ptl_batch *b, int32_t seq, ptl_pktdec *dec, int64_t k, const void *packets, int64_t n, ptl_pkt_summary *summary,
+                             uint64_t *col_ts);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ Module layout mirrors the reference so `ptudes.X` becomes `ptudes_lab_amd.X`:
   ins/data.py      IMU, NavState, calc_ate   (reference src/ptudes/ins/data.py)
   utils.py         pose-file writers/reader  (reference src/ptudes/utils.py)
   cli/ekf_bench.py `ekf-bench` commands      (reference src/ptudes/cli/ekf_bench.py)
+  packets.py       Ouster packet format, metadata, frame batching, PacketFeed (what the reference takes from ouster-sdk)
   sequence.py      whole-sequence device-resident runner (the reference's driver loop, ekf_bench.py:493-563)
   synth.py         synthetic sweeps + IMU (test/bench data; the reference ships none)
 """

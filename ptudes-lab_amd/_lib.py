@@ -61,6 +61,21 @@ class SeqCfg(_Cfg):
                 ("resident_scans", C.c_int32)]
 
 
+class PktFormat(_Cfg):
+    """ptl_pkt_format: profile = PTL_PKT_* (packets.PROFILES order)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("profile", C.c_int32), ("pixels_per_column", C.c_int32),
+                ("columns_per_frame", C.c_int32), ("columns_per_packet", C.c_int32)]
+
+
+class PktSummary(C.Structure):
+    _fields_ = [("frame_id", C.c_uint32), ("valid_columns", C.c_uint32), ("first_valid_id", C.c_uint32), ("last_valid_id", C.c_uint32),
+                ("first_valid_ts", C.c_uint64), ("last_valid_ts", C.c_uint64), ("nonzero_ranges", C.c_uint32),
+                ("ignored_columns", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -176,6 +191,14 @@ PROTOTYPES = {
     "ptl_icp_map_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
     "ptl_seq_map_build": (C.c_int, [_vp, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
     "ptl_batch_map_build": (C.c_int, [_vp, C.c_int32, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    # lidar packets decoded on the device (include/ptudes_mi.h)
+    "ptl_pkt_packet_bytes": (C.c_int64, [C.POINTER(PktFormat)]),
+    "ptl_pktdec_create": (C.c_int, [C.POINTER(PktFormat), C.c_int32, C.c_int64, C.c_int32, _vpp]),
+    "ptl_pktdec_destroy": (C.c_int, [_vp]),
+    "ptl_pktdec_decode": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp, _vp]),
+    "ptl_pktdec_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),
+    "ptl_seq_upload_packets": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
+    "ptl_batch_upload_packets": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -11,7 +11,8 @@ reference consumes itself:
   ouster_ros/PacketMsg     `uint8[] buf`; an Ouster IMU packet is 48 bytes: sys_ts, accel_ts, gyro_ts (u64 ns),
                            accel xyz (f32, g), angular velocity xyz (f32, deg/s)    (bag.py:149-156, ins/data.py:18-31)
 
-Lidar packets need ouster-sdk's `LidarPacket` (packet format tables) and are handed to it when it is importable.
+Lidar packets: `OusterRawBagSource` hands them to ouster-sdk's `LidarPacket` when it is importable; `OusterPacketBagSource` yields
+the raw payloads for the package's own decoder (packets.py).
 Message type names are normalised the way rosbags does (`pkg/Type` -> `pkg/msg/Type`) so that the reference's
 selection rules read the same here.  Parity: rosbags itself cannot run here, so the reader is pinned by round trips
 through `tests/bagwriter.py` (format-level, unpinned against rosbags); the loop that consumes `IMUBagSource`
@@ -348,6 +349,54 @@ class OusterRawBagSource:
                 yield self._sdk.LidarPacket(decode_packet_msg(rawdata), self._metadata, msg_ts_sec)
             elif conn.topic.endswith("imu_packets"):
                 yield self._sdk.ImuPacket(decode_packet_msg(rawdata), self._metadata, msg_ts_sec)
+
+    @property
+    def topics(self) -> List[str]:
+        return [c.topic for c in self._conns]
+
+    @property
+    def metadata(self):
+        return self._metadata
+
+    def close(self) -> None:
+        self._bag_reader.close()
+
+
+class OusterPacketBagSource:
+    """The same stream as `OusterRawBagSource` - topic selection, md5 check, pacing - as raw payloads: yields
+    ("lidar" | "imu", payload bytes, bag time in seconds), so nothing of ouster-sdk is needed.  `packets.PacketFeed` batches the lidar
+    payloads into sweeps and decodes them on the device."""
+
+    def __init__(self, data_path: Union[str, list], info=None, *, rate: float = 0.0, lidar_topic: str = "", imu_topic: str = "",
+                 _reader=None) -> None:
+        self._bag_reader = _reader if _reader is not None else Ros1BagReader(_paths(data_path))
+        self._bag_reader.open()
+        if not lidar_topic and not imu_topic:
+            self._conns = [c for c in self._bag_reader.connections
+                           if c.topic.endswith("lidar_packets") or c.topic.endswith("imu_packets")]
+        else:
+            topics = [t for t in [lidar_topic, imu_topic] if t]
+            self._conns = [c for c in self._bag_reader.connections if c.topic in topics]
+        self._metadata = info
+        self._rate = rate
+
+    def __iter__(self):
+        real_start_ts = time.monotonic()
+        bag_start_ts = None
+        for conn, ts, rawdata in self._bag_reader.messages(connections=self._conns):
+            msg_ts_sec = ts / 10**9
+            if self._rate:
+                if not bag_start_ts:
+                    bag_start_ts = msg_ts_sec
+                real_delta = time.monotonic() - real_start_ts
+                bag_delta = (msg_ts_sec - bag_start_ts) / self._rate
+                time.sleep(max(0, bag_delta - real_delta))
+            if conn.digest != OUSTER_PACKETMSG_MD5:
+                continue
+            if conn.topic.endswith("lidar_packets"):
+                yield "lidar", decode_packet_msg(rawdata), msg_ts_sec
+            elif conn.topic.endswith("imu_packets"):
+                yield "imu", decode_packet_msg(rawdata), msg_ts_sec
 
     @property
     def topics(self) -> List[str]:

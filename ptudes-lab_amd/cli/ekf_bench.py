@@ -6,8 +6,9 @@
   cmp     compare trajectories in Newer College format (reference :686-760)
 
 Same option names, printed lines and output files.  Differences, all because ouster-sdk / rosbags are not
-installable offline: `ouster` reads .pcap/.bag only when ouster-sdk is importable and otherwise (or with
---synthetic SEED) runs on a synthetic 128x1024 sequence; plotting options (-p) are not provided (the
+installable offline: `ouster` reads a .pcap only when ouster-sdk is importable; a .bag (or a directory of bags) goes through
+ouster-sdk when it is importable and otherwise (or with --native-packets) through the package's own packet decoder
+(packets.py); --synthetic SEED runs on a synthetic 128x1024 sequence; plotting options (-p) are not provided (the
 OpenGL / matplotlib viewers are outside the path).  `nc` reads the bag with the package's own ROS1 reader (bag.py)
 instead of rosbags.
 """
@@ -257,6 +258,9 @@ def _save_run_map(path, seq, first, rows_t, rows_p):
               help="write the resulting poses to this file, Newer College ground-truth format")
 @click.option("--synthetic", type=int, default=None,
               help="Run on the synthetic 128x1024 sequence with this seed instead of FILE (no ouster-sdk needed)")
+@click.option("--native-packets", is_flag=True,
+              help="read FILE (.bag, or a directory of bags) with the package's own packet decoder also when ouster-sdk is installed "
+                   "(without ouster-sdk this is what happens anyway)")
 @click.option("--save-smoothed-poses", required=False, type=click.Path(exists=False, dir_okay=False),
               help="also run the fixed-interval RTS smoother over the whole run and write its poses to this file, Newer College "
                    "ground-truth format, with the timestamps of --save-nc-gt-poses; with -g, print its ATE")
@@ -275,7 +279,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
                       kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None,
-                      imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter") -> None:
+                      imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter",
+                      native_packets: bool = False) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
@@ -289,13 +294,36 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
     if not gt_file and use_gt_guess:  # reference :416-418
         print("ERROR: --use-gt-guess requires the GT poses (--gt-file)")
         raise SystemExit(1)
+    have_sdk = False
     if synthetic is None:
         try:
             import ouster.client  # noqa: F401
             from ouster.sdk.util import resolve_metadata
+            have_sdk = True
         except Exception:
-            raise click.ClickException("reading .pcap/.bag needs ouster-sdk, which is not installed; "
-                                       "use --synthetic SEED to run the same path on a synthetic sequence")
+            pass
+    if synthetic is None and (native_packets or not have_sdk):
+        # the package's own feed (packets.py): raw payloads from the bag(s), batched on the host, decoded on the device
+        from pathlib import Path
+        from .. import packets as pk
+        from ..bag import OusterPacketBagSource
+        path = Path(file) if file else None
+        if path is None or not ((path.is_file() and path.suffix == ".bag") or path.is_dir()):
+            raise click.ClickException(f"'{file}': without ouster-sdk (or with --native-packets) FILE is a .bag or a directory of .bag files; "
+                                       "reading .pcap needs ouster-sdk" + ("" if have_sdk else ", which is not installed")
+                                       + " (IP-fragment reassembly is not built here); --synthetic SEED runs the same path on a synthetic sequence")
+        if not meta and path.is_file() and path.with_suffix(".json").is_file():
+            meta = str(path.with_suffix(".json"))
+        if not meta:
+            raise click.ClickException("File not found, please specify a metadata file with `-m`")
+        info = pk.read_metadata_json(meta)
+        bags = sorted(path.glob("*.bag")) if path.is_dir() else path
+        data_source = pk.PacketFeed(OusterPacketBagSource(bags, info), info)
+        seq = None
+        events = ((("imu", d) if hasattr(d, "lacc") else ("lidar_scan", d))
+                  for _, d in data_source.withScanIdx(start_scan=start_scan, end_scan=end_scan))
+        start_scan_feed = 0  # withScanIdx already applied the range
+    elif synthetic is None:
         # the reference's feed (ekf_bench.py:426-448): packets -> OusterLidarData -> (scan idx, LidarScan | IMU)
         from ..data import OusterLidarData
         from ..utils import read_metadata_json, read_packet_source
@@ -354,7 +382,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             elif ev[0] == "lidar_scan":  # ouster LidarScan (the packet feed applied start_scan / end_scan)
                 if beams:
                     from ..utils import reduce_active_beams
-                    reduce_active_beams(ev[1], beams)  # reference ekf_bench.py:520-521
+                    # reference ekf_bench.py:520-521 (a packets.PacketScan: its range image)
+                    reduce_active_beams(ev[1] if hasattr(ev[1], "field") else ev[1].range, beams)
                 yield ev
             elif scan_idx >= start_scan_feed:  # IMUs before start_scan are dropped (reference data.py:76)
                 yield ev

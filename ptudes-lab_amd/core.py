@@ -514,6 +514,99 @@ def host_unpin(array):
     L.check(L.lib().ptl_host_unpin(C.c_void_p(array.ctypes.data)))
 
 
+def pkt_format(fmt):
+    """ptl_pkt_format of a packets.OusterPacketFormat"""
+    f = L.PktFormat()
+    f.profile, f.pixels_per_column = fmt.profile_id, fmt.pixels_per_column
+    f.columns_per_frame, f.columns_per_packet = fmt.columns_per_frame, fmt.columns_per_packet
+    return f
+
+
+def pkt_packet_bytes(fmt):
+    """the library's size of a lidar packet of `fmt` (a packets.OusterPacketFormat or an L.PktFormat)"""
+    f = fmt if isinstance(fmt, L.PktFormat) else pkt_format(fmt)
+    n = L.lib().ptl_pkt_packet_bytes(C.byref(f))
+    if n < 0:
+        L.check(int(n))
+    return int(n)
+
+
+def _packet_rows(fmt_bytes, packets):
+    """(n, stride) u8 view of a packet buffer: rows are packets, the row stride is what the library is told"""
+    a = packets if isinstance(packets, np.ndarray) else np.frombuffer(packets, dtype=np.uint8)
+    if a.dtype != np.uint8:
+        raise ValueError("packets: a uint8 buffer")
+    if a.ndim == 1:
+        if a.size % fmt_bytes:
+            raise ValueError(f"packets: {a.size} bytes are not a whole number of {fmt_bytes}-byte packets")
+        a = a.reshape(-1, fmt_bytes)
+    if a.ndim != 2 or a.shape[1] < fmt_bytes or (len(a) and a.strides[1] != 1):
+        raise ValueError(f"packets: (n, >= {fmt_bytes}) uint8 rows")
+    return a
+
+
+class PacketDecoder:
+    """Lidar packets -> range images, column times, statuses and summaries on the device (include/ptudes_mi.h ptl_pktdec_*).
+    fmt: a packets.OusterPacketFormat.  One decode call takes up to max_packets packets of up to max_sweeps sweeps."""
+
+    def __init__(self, fmt, max_sweeps=8, max_packets=None, device_id=0):
+        self.format, self.device_id = fmt, int(device_id)
+        self._cfmt = pkt_format(fmt)
+        self.packet_bytes = pkt_packet_bytes(self._cfmt)
+        if self.packet_bytes != fmt.lidar_packet_size:
+            raise RuntimeError(f"packet size: the library says {self.packet_bytes}, packets.OusterPacketFormat {fmt.lidar_packet_size}")
+        per_sweep = -(-fmt.columns_per_frame // fmt.columns_per_packet)
+        self.max_sweeps = int(max_sweeps)
+        self.max_packets = int(max_packets) if max_packets else 2 * per_sweep * self.max_sweeps
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_pktdec_create(C.byref(self._cfmt), self.device_id, self.max_packets, self.max_sweeps, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_pktdec_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def profile(self, enable=True, reset=False):
+        """(device ms of the calls' four launches since the last reset, calls timed); include/ptudes_mi.h ptl_pktdec_profile"""
+        ms, n = C.c_double(), C.c_int64()
+        L.check(L.lib().ptl_pktdec_profile(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+    def decode_arrays(self, packets, sweep_of_packet, n_sweeps=None):
+        """(range (S, H, W) u32, timestamp (S, W) u64, status (S, W) u16, [summary dict] * S)"""
+        a = _packet_rows(self.packet_bytes, packets)
+        sop = np.ascontiguousarray(sweep_of_packet, dtype=np.int32)
+        if len(sop) != len(a):
+            raise ValueError("one sweep index per packet")
+        S = int(n_sweeps) if n_sweeps is not None else (int(sop.max()) + 1 if len(sop) else 0)
+        H, W = self.format.pixels_per_column, self.format.columns_per_frame
+        rng, ts, st = np.empty((S, H, W), np.uint32), np.empty((S, W), np.uint64), np.empty((S, W), np.uint16)
+        sums = (L.PktSummary * max(S, 1))()
+        L.check(L.lib().ptl_pktdec_decode(self._h, C.c_void_p(a.ctypes.data), a.strides[0] if len(a) else self.packet_bytes, len(a),
+                                          sop.ctypes.data_as(C.POINTER(C.c_int32)), S, C.c_void_p(rng.ctypes.data),
+                                          C.c_void_p(ts.ctypes.data), C.c_void_p(st.ctypes.data), C.cast(sums, C.c_void_p)))
+        return rng, ts, st, [sums[i].as_dict() for i in range(S)]
+
+    def decode(self, packets, sweep_of_packet, n_sweeps=None):
+        """-> [packets.PacketScan], one per sweep"""
+        from .packets import PacketScan
+        rng, ts, st, sums = self.decode_arrays(packets, sweep_of_packet, n_sweeps)
+        return [PacketScan(rng[i], ts[i], st[i], sums[i]["frame_id"], sums[i]) for i in range(len(sums))]
+
+
+def _upload_packets(call, dec, packets, W, want_ts):
+    """one sweep's packets (tightly packed) into a runner's slot -> (summary dict, column times or None)"""
+    a = _packet_rows(dec.packet_bytes, packets)
+    if len(a) and (a.shape[1] != dec.packet_bytes or not a.flags["C_CONTIGUOUS"]):
+        raise ValueError("upload_packets takes tightly packed packets")
+    summ = L.PktSummary()
+    ts = np.empty(W, np.uint64) if want_ts else None
+    L.check(call(dec._h, C.c_void_p(a.ctypes.data), len(a), C.byref(summ), None if ts is None else C.c_void_p(ts.ctypes.data)))
+    return summ.as_dict(), ts
+
+
 class _Runner:
     """What SeqRunner and BatchRunner share: the entry points without a sequence index (ptl_seq_* / ptl_batch_* by _PREFIX)."""
     _PREFIX = ""
@@ -611,6 +704,13 @@ class SeqRunner(_Runner):
 
     def upload_range(self, k, range_mm):
         L.check(L.lib().ptl_seq_upload_range(self._h, k, _range_u32(self.cfg, range_mm)))
+
+    def upload_packets(self, dec, k, packets, col_ts=False):
+        """sweep k decoded from its lidar packets straight into its slot (include/ptudes_mi.h ptl_seq_upload_packets): the slot then holds
+        what upload_range of the decoded image leaves.  Returns the sweep's summary (dict), with col_ts=True (summary, column times ns)"""
+        out = _upload_packets(lambda d, p, n, s, t: L.lib().ptl_seq_upload_packets(self._h, d, int(k), p, n, s, t), dec, packets,
+                              dec.format.columns_per_frame, col_ts)
+        return out if col_ts else out[0]
 
     def upload_imu(self, imu_rows, imu_end):
         L.check(L.lib().ptl_seq_upload_imu(self._h, *_imu_args(self.n_scans, imu_rows, imu_end)))
@@ -733,6 +833,12 @@ class BatchRunner(_Runner):
 
     def upload_range(self, s, k, range_mm):
         L.check(L.lib().ptl_batch_upload_range(self._h, s, k, _range_u32(self.cfg, range_mm)))
+
+    def upload_packets(self, s, dec, k, packets, col_ts=False):
+        """sweep k of sequence s decoded from its lidar packets straight into its slot (ptl_batch_upload_packets; see SeqRunner.upload_packets)"""
+        out = _upload_packets(lambda d, p, n, sm, t: L.lib().ptl_batch_upload_packets(self._h, int(s), d, int(k), p, n, sm, t), dec, packets,
+                              dec.format.columns_per_frame, col_ts)
+        return out if col_ts else out[0]
 
     def upload_imu(self, s, imu_rows, imu_end):
         L.check(L.lib().ptl_batch_upload_imu(self._h, s, *_imu_args(self.n_scans, imu_rows, imu_end)))

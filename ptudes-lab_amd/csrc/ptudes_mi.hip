@@ -7,6 +7,7 @@
 #include "icp_kernels.h"
 #include "seq_kernel.h"
 #include "fly_kernels.h"
+#include "packet_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -64,6 +65,7 @@ extern "C" int64_t ptl_sizeof_cfg(int which) {
         case PTL_CFG_EKF: return (int64_t)sizeof(ptl_ekf_cfg);
         case PTL_CFG_SEQ: return (int64_t)sizeof(ptl_seq_cfg);
         case PTL_CFG_ICP_STATS: return (int64_t)sizeof(ptl_icp_stats);
+        case PTL_CFG_PKT_FORMAT: return (int64_t)sizeof(ptl_pkt_format);
     }
     return -1;
 }
@@ -2922,4 +2924,181 @@ extern "C" int ptl_batch_map_build(ptl_batch* b, int32_t seq, ptl_icp* map, ptl_
     const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
     return fly_build(map, t, b->lane[seq], slot, nullptr, b->is_range != 0, b->is_range ? b->lut : nullptr, b->cfg.points_per_scan, t0t1, first, last,
                      n_valid, n_skipped, "ptl_batch_map_build");
+}
+
+// ================================================================================================ lidar packets
+// The byte layout of a profile (the table of DESIGN.md 3.16) and the decoder handle: packets are staged once at a 16-byte stride, the
+// three passes of packet_kernels.h run on the decoder's stream, and the image goes either to the decoder's own staging (ptl_pktdec_decode)
+// or straight into a runner's sweep slot (ptl_*_upload_packets).
+static_assert(sizeof(PktSummary) == sizeof(ptl_pkt_summary), "the device's summary record is the header's");
+static int pkt_layout(const ptl_pkt_format* f, PktLayout* out) {
+    if (!f) return set_err(PTL_ERR_ARG, "null packet format");
+    ABI_CHECK(ptl_pkt_format, f);
+    PktLayout L = {};
+    L.H = f->pixels_per_column; L.W = f->columns_per_frame; L.C = f->columns_per_packet;
+    if (L.H < 1 || L.W < 1 || L.C < 1 || L.C > PKT_MAX_COLS || L.H > 4096 || L.W > (1 << 16))
+        return set_err(PTL_ERR_ARG, "packet format: H = %d, W = %d, C = %d (need H in [1, 4096], W in [1, 65536], C in [1, %d])", L.H, L.W, L.C, PKT_MAX_COLS);
+    int trailer = 0, footer = 32;
+    L.pkt_hdr = 32; L.col_hdr = 12; L.pix = 12; L.mask = 0x0007ffffu; L.shift = 0; L.status_off = 10; L.frame_off = 2;
+    switch (f->profile) {
+        case PTL_PKT_LEGACY:
+            L.pkt_hdr = 0; footer = 0; L.col_hdr = 16; trailer = 4; L.mask = 0x000fffffu; L.status_off = 16 + 12 * L.H; L.frame_off = 10;
+            break;
+        case PTL_PKT_RNG19_RFL8_SIG16_NIR16: break;
+        case PTL_PKT_RNG15_RFL8_NIR8: L.pix = 4; L.mask = 0x7fffu; L.shift = 3; break;
+        case PTL_PKT_RNG19_RFL8_SIG16_NIR16_DUAL: L.pix = 16; break;
+        default: return set_err(PTL_ERR_ARG, "unknown lidar packet profile %d (PTL_PKT_*)", f->profile);
+    }
+    L.col_stride = L.col_hdr + L.H * L.pix + trailer;
+    const int64_t bytes = (int64_t)L.pkt_hdr + (int64_t)L.C * L.col_stride + footer;
+    if (bytes > PKT_MAX_BYTES) return set_err(PTL_ERR_ARG, "a packet of %lld bytes is above the %d the decoder stages", (long long)bytes, PKT_MAX_BYTES);
+    L.bytes = (int)bytes;
+    L.stride = (L.bytes + 15) & ~15;
+    *out = L;
+    return PTL_OK;
+}
+extern "C" int64_t ptl_pkt_packet_bytes(const ptl_pkt_format* fmt) {
+    PktLayout L;
+    const int rc = pkt_layout(fmt, &L);
+    return rc ? rc : L.bytes;
+}
+
+struct ptl_pktdec {
+    int device_id = 0;
+    PktLayout L = {};
+    int64_t max_packets = 0;
+    int max_sweeps = 0;
+    Stream stream;
+    GnTimer prof;                     // ptl_pktdec_profile: the device time of a call's four launches
+    unsigned char* d_pkts = nullptr;  // [max_packets] at L.stride
+    int* d_sop = nullptr;             // [max_packets]
+    PktOut o = {};                    // owner, first packet, timestamps, status, summaries: [max_sweeps]; o.img: the decoder's own images
+    unsigned* d_img = nullptr;        // [max_sweeps][H][W]
+    DevOwner mem;
+};
+extern "C" int ptl_pktdec_destroy(ptl_pktdec* d) { return d ? handle_destroy(d, d->device_id) : PTL_OK; }
+extern "C" int ptl_pktdec_create(const ptl_pkt_format* fmt, int32_t device_id, int64_t max_packets, int32_t max_sweeps, ptl_pktdec** out) {
+    if (!fmt || !out) return set_err(PTL_ERR_ARG, "null argument");
+    PktLayout L;
+    int rc = pkt_layout(fmt, &L);
+    if (rc) return rc;
+    if (max_packets < 1 || max_packets > (1 << 20) || max_sweeps < 1 || max_sweeps > (1 << 16) || max_packets * L.C > 0x7fffffffLL ||
+        (int64_t)max_sweeps * L.W > 0x7fffffffLL)
+        return set_err(PTL_ERR_ARG, "ptl_pktdec_create: max_packets = %lld (1 .. 2^20), max_sweeps = %d (1 .. 2^16)", (long long)max_packets, max_sweeps);
+    if (device_id < 0 || ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    std::unique_ptr<ptl_pktdec> d(new ptl_pktdec());
+    d->device_id = device_id; d->L = L; d->max_packets = max_packets; d->max_sweeps = max_sweeps;
+    if (d->stream.create() != hipSuccess) return set_err(PTL_ERR_HIP, "stream creation failed");
+    DevOwner& m = d->mem;
+    const size_t S = (size_t)max_sweeps, W = (size_t)L.W;
+    m.add(&d->d_pkts, (size_t)max_packets * L.stride); m.add(&d->d_sop, (size_t)max_packets);
+    m.add(&d->d_img, S * L.H * W); m.add(&d->o.ts, S * W); m.add(&d->o.status, S * W); m.add(&d->o.owner, S * W);
+    m.add(&d->o.first_pkt, S); m.add(&d->o.sum, S);
+    if (m.err != hipSuccess) return set_err(PTL_ERR_HIP, "ptl_pktdec_create: %s (%zu bytes)", hipGetErrorString(m.err), m.requested());
+    d->o.img = d->d_img;
+    d->o.img_stride = (size_t)L.H * W;
+    *out = d.release();
+    return PTL_OK;
+}
+// what both forms check before any HIP call
+static int pktdec_check(const ptl_pktdec* d, const void* packets, int64_t stride, int64_t n, const int32_t* sop, int32_t n_sweeps, const char* who) {
+    if (!d || !packets) return set_err(PTL_ERR_ARG, "%s: null argument", who);
+    if (((uintptr_t)packets & 3) || (stride & 3)) return set_err(PTL_ERR_ARG, "%s: the packet buffer and its stride must be 4-byte aligned", who);
+    if (stride < d->L.bytes) return set_err(PTL_ERR_ARG, "%s: stride of %lld bytes, a packet has %d", who, (long long)stride, d->L.bytes);
+    if (n < 0 || n > d->max_packets) return set_err(PTL_ERR_ARG, "%s: %lld packets, the decoder was created for %lld", who, (long long)n, (long long)d->max_packets);
+    if (n_sweeps < 1 || n_sweeps > d->max_sweeps) return set_err(PTL_ERR_ARG, "%s: %d sweeps, the decoder was created for %d", who, n_sweeps, d->max_sweeps);
+    if (sop)
+        for (int64_t i = 0; i < n; ++i)
+            if (sop[i] >= n_sweeps) return set_err(PTL_ERR_ARG, "%s: packet %lld names sweep %d of %d", who, (long long)i, sop[i], n_sweeps);
+    return PTL_OK;
+}
+// the three passes for n staged packets into `o` (its img: the decoder's staging or a runner's slot); nothing here waits
+static int pktdec_run(ptl_pktdec* d, const void* packets, int64_t stride, int64_t n, const int32_t* sop, int32_t n_sweeps, const PktOut& o) {
+    const PktLayout& L = d->L;
+    const hipStream_t st = d->stream;
+    if (n > 0) {
+        if (stride == L.stride) HIPCHK(hipMemcpyAsync(d->d_pkts, packets, (size_t)n * L.stride, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemcpy2DAsync(d->d_pkts, (size_t)L.stride, packets, (size_t)stride, (size_t)L.bytes, (size_t)n, hipMemcpyHostToDevice, st));
+        if (sop) HIPCHK(hipMemcpyAsync(d->d_sop, sop, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(d->prof.begin(st));
+    hipLaunchKernelGGL(k_pkt_init, dim3((unsigned)((n_sweeps * L.W + PKT_THREADS - 1) / PKT_THREADS)), dim3(PKT_THREADS), 0, st, (int)n_sweeps, L.W, o);
+    const int* dsop = sop ? d->d_sop : nullptr;
+    if (n > 0) {
+        const int cols = (int)(n * L.C);
+        hipLaunchKernelGGL(k_pkt_owner, dim3((unsigned)((cols + PKT_THREADS - 1) / PKT_THREADS)), dim3(PKT_THREADS), 0, st, L, d->d_pkts, dsop, (int)n, o);
+        hipLaunchKernelGGL(k_pkt_decode, dim3((unsigned)n), dim3(PKT_THREADS), (size_t)L.stride, st, L, d->d_pkts, dsop, o);
+    }
+    hipLaunchKernelGGL(k_pkt_finish, dim3((unsigned)n_sweeps, (unsigned)L.H), dim3(PKT_THREADS), 0, st, L, d->d_pkts, o);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d->prof.end(st));
+    return PTL_OK;
+}
+extern "C" int ptl_pktdec_profile(ptl_pktdec* d, int enable, double* ms_total, int64_t* calls, int reset) {
+    if (!d) return set_err(PTL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(d->device_id));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    d->prof.report(enable, ms_total, calls, reset);
+    return PTL_OK;
+}
+extern "C" int ptl_pktdec_decode(ptl_pktdec* d, const void* packets, int64_t stride_bytes, int64_t n, const int32_t* sweep_of_packet, int32_t n_sweeps,
+                                 uint32_t* range_out, uint64_t* col_ts_out, uint16_t* col_status_out, ptl_pkt_summary* summary_out) {
+    if (!sweep_of_packet) return set_err(PTL_ERR_ARG, "ptl_pktdec_decode: null argument");
+    int rc = pktdec_check(d, packets, stride_bytes, n, sweep_of_packet, n_sweeps, "ptl_pktdec_decode");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(d->device_id));
+    rc = pktdec_run(d, packets, stride_bytes, n, sweep_of_packet, n_sweeps, d->o);
+    if (rc) return rc;
+    const size_t S = (size_t)n_sweeps, W = (size_t)d->L.W;
+    const hipStream_t st = d->stream;
+    if (range_out) HIPCHK(hipMemcpyAsync(range_out, d->d_img, S * d->L.H * W * 4, hipMemcpyDeviceToHost, st));
+    if (col_ts_out) HIPCHK(hipMemcpyAsync(col_ts_out, d->o.ts, S * W * 8, hipMemcpyDeviceToHost, st));
+    if (col_status_out) HIPCHK(hipMemcpyAsync(col_status_out, d->o.status, S * W * 2, hipMemcpyDeviceToHost, st));
+    if (summary_out) HIPCHK(hipMemcpyAsync(summary_out, d->o.sum, S * sizeof(PktSummary), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return PTL_OK;
+}
+// one sweep into a runner's slot (the image's first word at `slot`); returns when the slot is written, like the copy of ptl_*_upload_range
+static int pktdec_into_slot(ptl_pktdec* d, const void* packets, int64_t n, void* slot, ptl_pkt_summary* summary, uint64_t* col_ts) {
+    PktOut o = d->o;
+    o.img = (unsigned*)slot;
+    int rc = pktdec_run(d, packets, d->L.bytes, n, nullptr, 1, o);
+    if (rc) return rc;
+    if (summary) HIPCHK(hipMemcpyAsync(summary, o.sum, sizeof(PktSummary), hipMemcpyDeviceToHost, d->stream));
+    if (col_ts) HIPCHK(hipMemcpyAsync(col_ts, o.ts, (size_t)d->L.W * 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return PTL_OK;
+}
+extern "C" int ptl_seq_upload_packets(ptl_seq* s, ptl_pktdec* dec, int64_t k, const void* packets, int64_t n, ptl_pkt_summary* summary, uint64_t* col_ts) {
+    if (!s || !dec || k < 0 || k >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
+    int rc = pktdec_check(dec, packets, dec->L.bytes, n, nullptr, 1, "ptl_seq_upload_packets");
+    if (rc) return rc;
+    if ((int64_t)dec->L.H * dec->L.W != s->cfg.points_per_scan || dec->device_id != s->cfg.icp.device_id)
+        return set_err(PTL_ERR_ARG, "ptl_seq_upload_packets: the decoder (%d x %d, device %d) does not match the runner (points_per_scan %lld, device %d)",
+                       dec->L.H, dec->L.W, dec->device_id, (long long)s->cfg.points_per_scan, s->cfg.icp.device_id);
+    HIPCHK(hipSetDevice(s->cfg.icp.device_id));
+    const size_t slot = (size_t)s->cfg.points_per_scan * 12;
+    rc = pktdec_into_slot(dec, packets, n, (char*)s->lane.d_scans + (size_t)k * slot, summary, col_ts);
+    if (rc) return rc;
+    s->is_range[(size_t)k] = 1;
+    return PTL_OK;
+}
+extern "C" int ptl_batch_upload_packets(ptl_batch* b, int32_t s, ptl_pktdec* dec, int64_t k, const void* packets, int64_t n, ptl_pkt_summary* summary,
+                                        uint64_t* col_ts) {
+    if (!b || !dec || s < 0 || s >= b->S || k < 0 || k >= b->cfg.n_scans) return set_err(PTL_ERR_ARG, "bad argument");
+    int rc = pktdec_check(dec, packets, dec->L.bytes, n, nullptr, 1, "ptl_batch_upload_packets");
+    if (rc) return rc;
+    if ((int64_t)dec->L.H * dec->L.W != b->cfg.points_per_scan || dec->L.W != b->cfg.icp.scan_cols || dec->device_id != b->cfg.icp.device_id)
+        return set_err(PTL_ERR_ARG, "ptl_batch_upload_packets: the decoder (%d x %d, device %d) does not match the batch (points_per_scan %lld, scan_cols %d, device %d)",
+                       dec->L.H, dec->L.W, dec->device_id, (long long)b->cfg.points_per_scan, b->cfg.icp.scan_cols, b->cfg.icp.device_id);
+    if (!b->lut) return set_err(PTL_ERR_STATE, "set the LUT first (ptl_batch_set_lut)");
+    HIPCHK(hipSetDevice(b->cfg.icp.device_id));
+    rc = batch_ring_slot_free(b, s, k);
+    if (rc) return rc;
+    const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
+    rc = pktdec_into_slot(dec, packets, n, (char*)b->lane[s].d_scans + (size_t)(k % b->ring) * slot, summary, col_ts);
+    if (rc) return rc;
+    if (b->ring < b->cfg.n_scans) b->up_hi[s] = k + 1;
+    return PTL_OK;
 }

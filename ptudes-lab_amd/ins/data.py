@@ -146,8 +146,8 @@ def ekf_traj_ate(ekf_gt, ekf):
 
 class StreamStatsTracker:
     """Tracks the mean / std of the scans' ranges and of the IMU samples (reference ins/data.py:207-369, same
-    methods, properties and report).  `trackScan` takes an Ouster LidarScan (when ouster-sdk is importable), or a
-    (H, W) uint32 range image with the last valid column timestamp in ns; the per-scan count / mean / variance /
+    methods, properties and report).  `trackScan` takes an Ouster LidarScan (when ouster-sdk is importable), a
+    `packets.PacketScan` (its own last valid column time), or a (H, W) uint32 range image with the last valid column timestamp in ns; the per-scan count / mean / variance /
     min / max come from the HIP reduction `ptl_range_stats`, the pooling formula is the reference's (:310-316)."""
 
     def __init__(self, use_beams_num: Optional[int] = None, metadata=None, device_id: int = 0):
@@ -188,6 +188,10 @@ class StreamStatsTracker:
             rng = np.ascontiguousarray(ls.field(client.ChanField.RANGE), dtype=np.uint32)
             if last_valid_column_ts_ns is None:
                 last_valid_column_ts_ns = client.last_valid_column_ts(ls)
+        elif hasattr(ls, "range") and hasattr(ls, "last_valid_column_ts_ns"):  # packets.PacketScan: a sweep decoded on the device
+            rng = np.ascontiguousarray(ls.range, dtype=np.uint32)
+            if last_valid_column_ts_ns is None:
+                last_valid_column_ts_ns = ls.last_valid_column_ts_ns
         else:
             rng = np.ascontiguousarray(ls, dtype=np.uint32)
         if rng.ndim != 2:

@@ -89,7 +89,9 @@ def run_events(events, metadata, *, kiss_min_range=1.0, kiss_max_range=70.0, use
                 stats.trackScan(rng, last_valid_column_ts_ns=int(round(ev[3] * 1e9)))
             t_track += time.monotonic() - t1
         if ev[0] == "lidar_scan":  # an ouster LidarScan from the packet feed (data.OusterLidarData)
-            xyz, t01, ts = None, None, float(getattr(ev[1], "timestamp", [0])[-1]) * 1e-9 if hasattr(ev[1], "timestamp") else 0.0
+            # (a packets.PacketScan knows its time - the last VALID column's, reference kiss.py:62)
+            xyz, t01 = None, None
+            ts = float(ev[1].ts) if hasattr(ev[1], "ts") else (float(ev[1].timestamp[-1]) * 1e-9 if hasattr(ev[1], "timestamp") else 0.0)
         else:
             _, xyz, t01, ts = ev
         if fused and ev[0] != "lidar_scan":
