@@ -51,10 +51,11 @@ extern "C" {
 #define PTL_CFG_SEQ 2
 #define PTL_CFG_ICP_STATS 3
 #define PTL_CFG_PKT_FORMAT 4
+#define PTL_CFG_MAP_SCORE 5
 #define PTL_CFG_INIT(cfg_ptr) do { memset((cfg_ptr), 0, sizeof *(cfg_ptr)); (cfg_ptr)->struct_size = (uint32_t)sizeof *(cfg_ptr); (cfg_ptr)->abi_version = PTL_ABI_VERSION; } while (0)
 int ptl_abi_version(void);
-/* the library's sizeof for PTL_CFG_ICP / _EKF / _SEQ / _ICP_STATS (the three configuration structs and the per-scan counter row) and
- * PTL_CFG_PKT_FORMAT (ptl_pkt_format); -1 for an unknown id */
+/* the library's sizeof for PTL_CFG_ICP / _EKF / _SEQ / _ICP_STATS (the three configuration structs and the per-scan counter row),
+ * PTL_CFG_PKT_FORMAT (ptl_pkt_format) and PTL_CFG_MAP_SCORE (ptl_map_score_cfg); -1 for an unknown id */
 int64_t ptl_sizeof_cfg(int which);
 
 const char *ptl_last_error(void);
@@ -613,6 +614,56 @@ int ptl_pktdec_profile(ptl_pktdec *d, int enable, double *ms_total, int64_t *cal
 int ptl_seq_upload_packets(ptl_seq *s, ptl_pktdec *dec, int64_t k, const void *packets, int64_t n, ptl_pkt_summary *summary, uint64_t *col_ts);
 int ptl_batch_upload_packets(ptl_batch *b, int32_t seq, ptl_pktdec *dec, int64_t k, const void *packets, int64_t n, ptl_pkt_summary *summary,
                              uint64_t *col_ts);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sharpness of a voxel map without ground truth (no reference counterpart).  The score is of the map AS STORED: a voxel
+ * keeps its first max_points_per_voxel points, and only those are scored and counted as neighbours.
+ * Per stored point q:
+ *   membership  a stored point p (q included) is a neighbour iff (dx dx + dy dy) + dz dz <= radius radius, d = p - q, evaluated in that order
+ *               without contraction: an integer fact, the same everywhere;
+ *   covariance  n = number of neighbours, m = mean of the offsets d, Sigma = (1/n) sum d d^T - m m^T in fp64 (offsets from q: every term is
+ *               at most radius^2 in magnitude);
+ *   eigenvalues lambda0 <= lambda1 <= lambda2 of Sigma by cyclic Jacobi with a fixed number of sweeps (no closed trigonometric form: it loses
+ *               its digits at the planar neighbourhoods that matter here), each clipped below at 0;
+ *   outputs     plane_var = lambda0 (a crisp wall: about the sensor noise; a doubled wall: about (half the gap)^2);
+ *               entropy = 0.5 (3 ln(2 pi e) + sum_i ln(lambda_i + sigma_floor^2)), the differential entropy of the neighbourhood Gaussian -
+ *               the floor keeps a perfectly planar neighbourhood finite;
+ *   sparse      n < min_neighbours: counted, not scored; its per-point outputs are n and two NaNs.
+ * Parameters: 0 < radius <= the map's voxel size (with the truncating voxel index every point within radius of a point of voxel k lies in
+ * voxels k - 1 .. k + 1 on each axis: the 27-voxel search is then complete; otherwise PTL_ERR_ARG with both numbers), min_neighbours >= 1 (it
+ * counts the point itself), sigma_floor > 0.  The defaults (radius = voxel size, 5, voxel size / 100) are defaults a caller may change and the
+ * result echoes - not tuned values.
+ * Counts are exact.  The means are reduced on the device by a fixed tree over the per-point values in pool order: two builds of the same map
+ * may hand out block ids differently, so their means are equal only up to summation order (their per-point values are equal bit for bit). */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_map_score_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double radius;
+    int32_t min_neighbours;
+    double sigma_floor;
+} ptl_map_score_cfg;
+typedef struct {
+    int64_t n_points, n_scored, n_sparse;   /* stored points = scored + sparse */
+    double mean_plane_var, mean_entropy;    /* over the scored points; 0 when there is none */
+    double mean_neighbours;                 /* mean n over ALL stored points (0 for an empty map) */
+    double radius;                          /* the parameters as used */
+    int32_t min_neighbours;
+    double sigma_floor;
+    double device_ms;                       /* HIP-event time of the call's device work on the handle's own stream (0 for an empty map): the one
+                                             * field that is not a function of the map - only the library can bracket that stream, cf. ptl_icp_profile */
+} ptl_map_score_result;
+/* the defaults for a map of that voxel size; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is
+ * refused with PTL_ERR_ARG and nothing is written */
+int ptl_map_score_default_cfg(ptl_map_score_cfg *cfg, double voxel_size);
+/* Scores the map of `map` (cfg nullable: the defaults).  Waits for the handle's map update first, never writes to the map, keeps nothing in the
+ * handle: its work buffers live for the call.  xyz_out (3 per point), n_out, plane_var_out, entropy_out: all four or none; when given they
+ * receive every stored point with its values in one common order (pool order, unspecified) and *n_written (nullable) their number;
+ * max_points below the map's point count: PTL_ERR_CAPACITY naming the count, nothing written.  A handle whose max_points_per_voxel needs more
+ * than 64 KB of staging (27 P 24 bytes: P > 98): PTL_ERR_CAPACITY - a guard that no handle reaches today, since ptl_icp_create refuses more
+ * than 32 points per voxel.  PTL_ERR_STATE when the map table does not lead every voxel back to its block (nothing is scored then).  Arguments are checked before any HIP call; an empty map gives the all-zero
+ * summary (with the parameters). */
+int ptl_icp_map_score(ptl_icp *map, const ptl_map_score_cfg *cfg, ptl_map_score_result *out, double *xyz_out, int32_t *n_out,
+                      double *plane_var_out, double *entropy_out, int64_t max_points, int64_t *n_written);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,18 @@ class PktSummary(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MapScoreCfg(_Cfg):
+    """ptl_map_score_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("radius", C.c_double), ("min_neighbours", C.c_int32),
+                ("sigma_floor", C.c_double)]
+
+
+class MapScoreResult(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_scored", C.c_int64), ("n_sparse", C.c_int64), ("mean_plane_var", C.c_double),
+                ("mean_entropy", C.c_double), ("mean_neighbours", C.c_double), ("radius", C.c_double), ("min_neighbours", C.c_int32),
+                ("sigma_floor", C.c_double), ("device_ms", C.c_double)]
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -199,6 +211,10 @@ PROTOTYPES = {
     "ptl_pktdec_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),
     "ptl_seq_upload_packets": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
     "ptl_batch_upload_packets": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
+    # sharpness of a map without ground truth (include/ptudes_mi.h)
+    "ptl_map_score_default_cfg": (C.c_int, [C.POINTER(MapScoreCfg), C.c_double]),
+    "ptl_icp_map_score": (C.c_int, [_vp, C.POINTER(MapScoreCfg), C.POINTER(MapScoreResult), c_d_p, C.POINTER(C.c_int32), c_d_p, c_d_p,
+                                    C.c_int64, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -204,10 +204,8 @@ MAP_VOXEL_SIZE = 0.5
 MAP_TIME_BOUNDS = 1.5  # as the fly-by's pose_scans_from_nc_gt (reference utils.py:368)
 
 
-def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
-    """The world map of sweeps [first, n_scans) of a synthetic sequence under the trajectory `knots` [(ts, pose)]: the sweeps are
-    uploaded once and the map is built where they lie (SeqRunner.build_map), every column at its own pose, bounds 1.5 s.
-    Returns (map points (N, 3), voxels, n_skipped)."""
+def _run_map_handle(seq, first, knots, voxel_size, device_id):
+    """(map handle, n_skipped): the map of `run_map`, still on the device"""
     from .. import core
     from ..sequence import sweep_times
     traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
@@ -218,19 +216,74 @@ def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
     map_icp = core.Icp(1.0e9, 0.0, voxel_size=voxel_size, scan_cols=seq.W, max_points_per_scan=seq.H * seq.W, device_id=device_id,
                        map_block_capacity=1 << 21, map_table_capacity=1 << 23)
     _, n_skipped = runner.build_map(map_icp, traj, sweep_times(seq), first=first)
+    for h in (runner, traj):
+        h.close()
+    return map_icp, n_skipped
+
+
+def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
+    """The world map of sweeps [first, n_scans) of a synthetic sequence under the trajectory `knots` [(ts, pose)]: the sweeps are
+    uploaded once and the map is built where they lie (SeqRunner.build_map), every column at its own pose, bounds 1.5 s.
+    Returns (map points (N, 3), voxels, n_skipped)."""
+    map_icp, n_skipped = _run_map_handle(seq, first, knots, voxel_size, device_id)
     voxels, _ = map_icp.map_size()
     pts = map_icp.map_points()
-    for h in (runner, map_icp, traj):
-        h.close()
+    map_icp.close()
     return pts, voxels, n_skipped
 
 
-def _save_run_map(path, seq, first, rows_t, rows_p):
+def _bag_map(bags, info, start_scan, end_scan, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
+    """... of a raw packet bag: a second pass over the bag through the package's packet feed, every decoded sweep into the map by the fused
+    per-call path with its decoded column times (every column posed at its own firing time).  The LUT is the registration's
+    (lidar_to_sensor and the extrinsic, sequence.run_events).  Returns the fly.MapAccumulator."""
+    from .. import core, fly
+    lut = fly.sensor_lut(info, use_extrinsics=True, device_id=device_id)
+    traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
+    acc = fly.MapAccumulator(lut, voxel_size=voxel_size, device_id=device_id)
+    fly.add_packet_bag(acc, bags, info, traj, start_scan, end_scan, device_id=device_id)
+    traj.close()
+    lut.close()  # (the sweeps are in: the map no longer needs it)
+    return acc
+
+
+def _finish_map(path, map_icp, score):
+    """points (and, with `score` = keyword arguments of Icp.map_score, the per-point scalars) of a built map to `path` (nullable);
+    returns (voxels, points, MapScore | None)"""
+    from ..utils import save_map_ply
+    voxels, _ = map_icp.map_size()
+    ms, scalars = None, None
+    if score is not None:
+        ms, (pts, nb, pv, ent) = map_icp.map_score(per_point=True, **score)
+        scalars = (nb, pv, ent)
+    else:
+        pts = map_icp.map_points()
+    if path:
+        if scalars is not None and str(path).endswith(".npy"):
+            print("NOTE: a .npy map holds the points only; give --save-map a .ply path for the per-point scores")
+            scalars = None
+        save_map_ply(path, pts, scalars)
+    map_icp.close()
+    return voxels, len(pts), ms
+
+
+def _save_run_map(path, seq, first, rows_t, rows_p, score=None):
     """... under the rows as the poses file holds them (utils.nc_gt_file_rows): what `flyby --nc-gt-poses` of that file works with"""
-    from ..utils import nc_gt_file_rows, save_map_ply
-    pts, voxels, n_skipped = run_map(seq, first, nc_gt_file_rows(rows_t, rows_p))
-    save_map_ply(path, pts)
-    return voxels, len(pts), n_skipped
+    from ..utils import nc_gt_file_rows
+    map_icp, n_skipped = _run_map_handle(seq, first, nc_gt_file_rows(rows_t, rows_p), MAP_VOXEL_SIZE, 0)
+    voxels, points, ms = _finish_map(path, map_icp, score)
+    return voxels, points, n_skipped, ms
+
+
+def score_options(map_score, score_radius, voxel_size):
+    """the keyword arguments of Icp.map_score for --map-score / --score-radius, or None; refusals before any device is touched"""
+    if score_radius is not None and not map_score:
+        raise click.ClickException("--score-radius belongs to --map-score")
+    if not map_score:
+        return None
+    if score_radius is not None and not 0.0 < score_radius <= voxel_size:
+        raise click.ClickException(f"--score-radius {score_radius:g}: the 27-voxel neighbourhood search needs 0 < radius <= the map's voxel size "
+                                   f"{voxel_size:g}")
+    return dict(radius=score_radius)
 
 
 @click.command(name="ouster")
@@ -270,24 +323,29 @@ def _save_run_map(path, seq, first, rows_t, rows_p):
                    "the sweep times of real recordings are not decoded here")
 @click.option("--save-map", required=False, type=click.Path(dir_okay=False),
               help="after the run, build the world map of the sweeps (voxel size 0.5) with the poses of --map-from as they stand in the "
-                   "poses file, every column at its own pose, and write its points to this file (PLY, or .npy); needs --synthetic: "
-                   "the sweep times of real recordings are not decoded here")
+                   "poses file, every column at its own pose, and write its points to this file (PLY, or .npy); needs --synthetic or a "
+                   "raw packet .bag read by the package's own decoder (its column times are decoded)")
 @click.option("--map-from", type=click.Choice(["filter", "kiss", "smoothed"]), default="filter",
               help="trajectory of --save-map: the filter's poses (default), KissICP's own, or the RTS smoothed ones "
                    "(needs --save-smoothed-poses)")
+@click.option("--map-score", is_flag=True,
+              help="score the sharpness of that map without ground truth (mean plane variance and mean map entropy of the stored points' "
+                   "neighbourhoods) and print it; with --save-map the PLY carries the per-point values; works without --save-map too")
+@click.option("--score-radius", type=float, default=None, help="neighbourhood radius of --map-score, metres (default and upper bound: the "
+                                                               "map's voxel size, 0.5)")
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
                       kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None,
                       imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter",
-                      native_packets: bool = False) -> None:
+                      native_packets: bool = False, map_score: bool = False, score_radius: Optional[float] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
     from ..utils import TrajectoryEvaluator, active_beam_rows
-    if save_map and synthetic is None:
-        raise click.ClickException("--save-map needs --synthetic: the sweep times of real recordings are not decoded here")
-    if save_map and map_from == "smoothed" and not save_smoothed_poses:
+    score = score_options(map_score, score_radius, MAP_VOXEL_SIZE)
+    want_map = bool(save_map) or map_score
+    if want_map and map_from == "smoothed" and not save_smoothed_poses:
         raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
         raise click.ClickException("--imu-deskew needs --synthetic and the fused loop (no -p)")
@@ -302,6 +360,13 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             have_sdk = True
         except Exception:
             pass
+    if want_map and synthetic is None:
+        from pathlib import Path
+        native_bag = bool(file) and (native_packets or not have_sdk) and ((Path(file).is_file() and Path(file).suffix == ".bag") or Path(file).is_dir())
+        if not native_bag:
+            raise click.ClickException("--save-map needs --synthetic or a raw packet .bag read by the package's own decoder (--native-packets): "
+                                       "the sweep times of other recordings are not decoded here (the same holds for --map-score)")
+    bags = None
     if synthetic is None and (native_packets or not have_sdk):
         # the package's own feed (packets.py): raw payloads from the bag(s), batched on the host, decoded on the device
         from pathlib import Path
@@ -413,12 +478,25 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                 pose0 = sm_m[0] @ np.linalg.inv(gts_m[0][1])
                 ate_rot, ate_trans = calc_ate(sm_m, [pose0 @ g[1] for g in gts_m])
                 print(f"ATE of the RTS smoothed poses ({len(gts_m)} poses): rot {ate_rot:.04f} deg, trans {ate_trans:.04f} m")
-    if save_map:
+    if want_map:
         rows_t, rows_p = {"filter": (res_t, res_poses), "kiss": (res_t, kiss_poses),
                           "smoothed": (out.get("smoothed_t"), out.get("smoothed_poses"))}[map_from]
-        voxels, points, n_skipped = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p))
-        print(f"Map of scans {start_scan} - {seq.n_scans - 1} ({map_from} poses, {n_skipped} skipped): {voxels} voxels, {points} points")
-        print(f"Map saved to: {save_map}")
+        if seq is not None:
+            voxels, points, n_skipped, ms = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p), score=score)
+            print(f"Map of scans {start_scan} - {seq.n_scans - 1} ({map_from} poses, {n_skipped} skipped): {voxels} voxels, {points} points")
+        else:
+            from ..utils import nc_gt_file_rows
+            if len(rows_t) < 2:
+                raise click.ClickException("the map needs a trajectory of at least two poses")
+            if beams:
+                print("NOTE: --beams thins the scans of the registration only; the map takes every beam of every sweep")
+            acc = _bag_map(bags, info, start_scan, end_scan, nc_gt_file_rows(list(rows_t), list(rows_p)))
+            voxels, points, ms = _finish_map(save_map, acc.icp, score)
+            print(f"Map of {acc.scans} scans from {start_scan} ({map_from} poses, {acc.skipped} skipped): {voxels} voxels, {points} points")
+        if ms is not None:
+            print("\n".join(ms.lines()))
+        if save_map:
+            print(f"Map saved to: {save_map}")
     tm = out["timings"]
     if tm["n_imu"] and tm["n_corr"]:  # reference :590-595
         print("\nTimings:")

@@ -1,6 +1,7 @@
 """Thin object layer over the C-ABI: `Icp` (one KissICP-equivalent on one GPU), `Ekf`, `SeqRunner`
 (the reference's driver loop, cli/ekf_bench.py:493-563, on a sequence resident in HBM)."""
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -27,6 +28,34 @@ def ekf_cfg(init_grav=None, init_bacc=None, init_bgyr=None, device_id=0):
             setattr(cfg, name, (C.c_double * 3)(*v))
     cfg.device_id = device_id
     return cfg
+
+
+@dataclass
+class MapScore:
+    """Summary of `Icp.map_score` (include/ptudes_mi.h ptl_map_score_result): counts, the means over the scored points, the parameters as
+    used, and the HIP-event time of the call's kernels"""
+    n_points: int
+    n_scored: int
+    n_sparse: int
+    mean_plane_var: float
+    mean_entropy: float
+    mean_neighbours: float
+    radius: float
+    min_neighbours: int
+    sigma_floor: float
+    device_ms: float
+
+    @property
+    def thickness_mm(self):
+        """sqrt(mean plane variance) in millimetres: the "wall thickness" of the map"""
+        return 1000.0 * float(np.sqrt(self.mean_plane_var))
+
+    def lines(self):
+        """the block the commands print"""
+        return [f"map score: radius {self.radius:g} m, min neighbours {self.min_neighbours}, sigma floor {self.sigma_floor:g} m",
+                f"  points: {self.n_points} (scored {self.n_scored}, sparse {self.n_sparse}), mean neighbours {self.mean_neighbours:.2f}",
+                f"  mean plane variance: {self.mean_plane_var:.6e} m^2 (wall thickness {self.thickness_mm:.3f} mm)",
+                f"  mean map entropy: {self.mean_entropy:.6f}"]
 
 
 class Icp:
@@ -115,6 +144,29 @@ class Icp:
         w = C.c_int64()
         L.check(L.lib().ptl_icp_map_points(self._h, L.dptr(out), p, C.byref(w)))
         return out[:w.value]
+
+    def map_score(self, radius=None, min_neighbours=5, sigma_floor=None, per_point=False):
+        """sharpness of the stored map without ground truth (include/ptudes_mi.h ptl_icp_map_score): a `MapScore`; with
+        per_point also (xyz (N, 3), n (N,) int32, plane_var (N,), entropy (N,)) of every stored point in one common order (sparse points:
+        NaN).  radius defaults to the voxel size (its upper bound), sigma_floor to voxel size / 100"""
+        cfg = L.MapScoreCfg()
+        L.check(L.lib().ptl_map_score_default_cfg(C.byref(cfg), float(self.cfg.voxel_size)))
+        if radius is not None:
+            cfg.radius = float(radius)
+        cfg.min_neighbours = int(min_neighbours)
+        if sigma_floor is not None:
+            cfg.sigma_floor = float(sigma_floor)
+        res = L.MapScoreResult()
+        if not per_point:
+            L.check(L.lib().ptl_icp_map_score(self._h, C.byref(cfg), C.byref(res), None, None, None, None, 0, None))
+            return MapScore(*(getattr(res, k) for k, _ in res._fields_))
+        _, p = self.map_size()
+        xyz, n, pv, ent = np.empty((max(p, 1), 3)), np.empty(max(p, 1), dtype=np.int32), np.empty(max(p, 1)), np.empty(max(p, 1))
+        w = C.c_int64()
+        L.check(L.lib().ptl_icp_map_score(self._h, C.byref(cfg), C.byref(res), L.dptr(xyz), n.ctypes.data_as(C.POINTER(C.c_int32)), L.dptr(pv),
+                                          L.dptr(ent), p, C.byref(w)))
+        k = w.value
+        return MapScore(*(getattr(res, f) for f, _ in res._fields_)), (xyz[:k], n[:k], pv[:k], ent[:k])
 
     def _cloud(self, fn):
         cap = int(self.cfg.max_points_per_scan)

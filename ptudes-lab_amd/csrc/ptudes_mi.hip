@@ -8,6 +8,7 @@
 #include "seq_kernel.h"
 #include "fly_kernels.h"
 #include "packet_kernels.h"
+#include "score_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -66,6 +67,7 @@ extern "C" int64_t ptl_sizeof_cfg(int which) {
         case PTL_CFG_SEQ: return (int64_t)sizeof(ptl_seq_cfg);
         case PTL_CFG_ICP_STATS: return (int64_t)sizeof(ptl_icp_stats);
         case PTL_CFG_PKT_FORMAT: return (int64_t)sizeof(ptl_pkt_format);
+        case PTL_CFG_MAP_SCORE: return (int64_t)sizeof(ptl_map_score_cfg);
     }
     return -1;
 }
@@ -2924,6 +2926,107 @@ extern "C" int ptl_batch_map_build(ptl_batch* b, int32_t seq, ptl_icp* map, ptl_
     const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
     return fly_build(map, t, b->lane[seq], slot, nullptr, b->is_range != 0, b->is_range ? b->lut : nullptr, b->cfg.points_per_scan, t0t1, first, last,
                      n_valid, n_skipped, "ptl_batch_map_build");
+}
+
+// ================================================================================================ map score
+// The definition is in include/ptudes_mi.h, the kernels in score_kernels.h.  Everything is checked on the host before the first HIP call; the
+// work buffers (chunk counts and offsets, the per-point values) are sized from the map's point count and live for the call.
+static void map_score_defaults(ptl_map_score_cfg* cfg, double voxel_size) {
+    PTL_CFG_INIT(cfg);
+    cfg->radius = voxel_size;
+    cfg->min_neighbours = 5;
+    cfg->sigma_floor = voxel_size / 100.0;
+}
+extern "C" int ptl_map_score_default_cfg(ptl_map_score_cfg* cfg, double voxel_size) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_map_score_cfg, cfg);
+    if (!(voxel_size > 0.0)) return set_err(PTL_ERR_ARG, "voxel_size must be positive (got %g)", voxel_size);
+    map_score_defaults(cfg, voxel_size);
+    return PTL_OK;
+}
+extern "C" int ptl_icp_map_score(ptl_icp* map, const ptl_map_score_cfg* cfg, ptl_map_score_result* out, double* xyz_out, int32_t* n_out,
+                                 double* plane_var_out, double* entropy_out, int64_t max_points, int64_t* n_written) {
+    if (!map || !out) return set_err(PTL_ERR_ARG, "null argument");
+    ptl_map_score_cfg use;
+    if (cfg) { ABI_CHECK(ptl_map_score_cfg, cfg); use = *cfg; } else map_score_defaults(&use, map->cfg.voxel_size);
+    const int given = (xyz_out != nullptr) + (n_out != nullptr) + (plane_var_out != nullptr) + (entropy_out != nullptr);
+    if (given != 0 && given != 4) return set_err(PTL_ERR_ARG, "the four per-point arrays (xyz, n, plane_var, entropy) are given together or not at all");
+    if (given && max_points < 0) return set_err(PTL_ERR_ARG, "max_points must not be negative");
+    const double vs = map->cfg.voxel_size;
+    if (!(use.radius > 0.0) || !(use.radius <= vs))
+        return set_err(PTL_ERR_ARG, "radius = %g: the 27-voxel search needs 0 < radius <= the map's voxel size = %g", use.radius, vs);
+    if (use.min_neighbours < 1) return set_err(PTL_ERR_ARG, "min_neighbours = %d: must be >= 1 (it counts the point itself)", use.min_neighbours);
+    if (!(use.sigma_floor > 0.0) || !(use.sigma_floor < 1.0e150)) return set_err(PTL_ERR_ARG, "sigma_floor = %g: must be positive and finite", use.sigma_floor);
+    const int P = map->cfg.max_points_per_voxel;
+    if (P < 1) return set_err(PTL_ERR_ARG, "max_points_per_voxel = %d", P);
+    const size_t stage_bytes = (size_t)27 * (size_t)P * 24;
+    if (stage_bytes > SCORE_LDS_LIMIT)
+        return set_err(PTL_ERR_CAPACITY, "max_points_per_voxel = %d needs %zu bytes of staging (27 voxels x P points x 24 bytes); the limit is %d bytes: P <= %d",
+                       P, stage_bytes, SCORE_LDS_LIMIT, SCORE_LDS_LIMIT / (27 * 24));
+    HIPCHK(hipSetDevice(map->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, map->stream));
+    HIPCHK(hipStreamSynchronize(map->stream));
+    const int64_t n = st.map_points;
+    if (n < 0 || n > (int64_t)0x7fffffff) return set_err(PTL_ERR_STATE, "the map reports %lld points", (long long)n);
+    if (given && max_points < n)
+        return set_err(PTL_ERR_CAPACITY, "the map holds %lld points, max_points = %lld", (long long)n, (long long)max_points);
+    memset(out, 0, sizeof *out);
+    out->radius = use.radius; out->min_neighbours = use.min_neighbours; out->sigma_floor = use.sigma_floor;
+    if (n_written) *n_written = 0;
+    if (n == 0) return PTL_OK;
+    const Ctx& c = map->c;
+    const int n_chunks = (c.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr, *d_nb = nullptr;
+    double *d_pv = nullptr, *d_ent = nullptr, *d_xyz = nullptr, *d_sum = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1);
+    tmp.add(&d_nb, (size_t)n); tmp.add(&d_pv, (size_t)n); tmp.add(&d_ent, (size_t)n);
+    if (given) tmp.add(&d_xyz, (size_t)n * 3);
+    int* d_bad = nullptr;
+    tmp.add(&d_sum, 4); tmp.add(&d_bad, 1);
+    HIPCHK(tmp.err);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventDefault)); HIPCHK(e1.create(hipEventDefault));
+    hipStream_t s = map->stream;
+    ScoreArgs a = {};
+    a.radius = use.radius; a.r2 = use.radius * use.radius; a.floor2 = use.sigma_floor * use.sigma_floor; a.min_nb = use.min_neighbours;
+    a.n_chunks = n_chunks; a.n_alloc = (int)n; a.stage_pts = 27 * P;
+    a.chunk_off = d_off; a.xyz = d_xyz; a.nb = d_nb; a.pv = d_pv; a.ent = d_ent; a.bad = d_bad;
+    HIPCHK(hipEventRecord(e0, s));  // (all of the call's device work lies between the two events; every per-point slot is written by k_score_points)
+    HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    k_score_count<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    k_score_points<<<n_chunks < 8192 ? n_chunks : 8192, 64, stage_bytes, s>>>(c, a);
+    k_score_reduce<<<1, 1024, 0, s>>>(d_nb, d_pv, d_ent, (int)n, use.min_neighbours, d_sum);
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipGetLastError());
+    int total = 0, bad = 0;
+    double sums[4];
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sums, d_sum, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad) return set_err(PTL_ERR_STATE, "the map table does not lead back to %d of the map's voxels: nothing was scored", bad);
+    if (total != (int)n) return set_err(PTL_ERR_STATE, "the block directory holds %d points, the map state %lld", total, (long long)n);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    out->n_points = n;
+    out->n_scored = (int64_t)sums[0];
+    out->n_sparse = n - out->n_scored;
+    out->mean_plane_var = out->n_scored ? sums[1] / sums[0] : 0.0;
+    out->mean_entropy = out->n_scored ? sums[2] / sums[0] : 0.0;
+    out->mean_neighbours = sums[3] / (double)n;
+    out->device_ms = ms;
+    if (given) {
+        HIPCHK(hipMemcpy(xyz_out, d_xyz, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(n_out, d_nb, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(plane_var_out, d_pv, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(entropy_out, d_ent, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (n_written) *n_written = n;
+    }
+    return PTL_OK;
 }
 
 // ================================================================================================ lidar packets

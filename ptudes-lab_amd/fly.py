@@ -47,8 +47,10 @@ class MapAccumulator:
         the sweep goes up once and nothing but the count comes back: returns n_valid (0 for a scan skipped as outside the bounds,
         counted in `skipped`) instead of the points.  The map is the same, bit for bit."""
         if traj is not None:
+            # (a packets.PacketScan calls its range image `range`; a PosedScan `range_mm`)
+            range_mm = scan.range_mm if hasattr(scan, "range_mm") else scan.range
             n_valid, skipped = self._icp.map_add_posed(traj, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9,
-                                                       range_mm=scan.range_mm, lut=self.lut)
+                                                       range_mm=range_mm, lut=self.lut)
             self.skipped += int(skipped)
             self.scans += 0 if skipped else 1
             self.returns += n_valid
@@ -74,11 +76,23 @@ class MapAccumulator:
         self.returns += n_valid
         return n_valid, n_skipped
 
+    @property
+    def icp(self):
+        """the core.Icp whose voxel map this is (for Icp.map_score(per_point=True) and the like)"""
+        return self._icp
+
+    def close(self):
+        self._icp.close()
+
     def map_size(self):
         return self._icp.map_size()
 
     def map_points(self) -> np.ndarray:
         return self._icp.map_points()
+
+    def score(self, radius=None, min_neighbours=5, sigma_floor=None, per_point=False):
+        """sharpness of the accumulated map without ground truth: core.Icp.map_score of the map handle"""
+        return self._icp.map_score(radius=radius, min_neighbours=min_neighbours, sigma_floor=sigma_floor, per_point=per_point)
 
 
 def synthetic_range_scans(seq, first=0, last=None):
@@ -95,3 +109,27 @@ def synthetic_range_scans(seq, first=0, last=None):
         col_t = seq.t_base + (k + src / W) * seq.scan_dt
         scans.append(PosedScan(rng_mm, (col_t * 1e9).astype(np.int64)))
     return lut, scans
+
+
+def sensor_lut(info, use_extrinsics=False, device_id=0):
+    """core.Lut of a sensor's metadata (packets.read_metadata_json / ouster SensorInfo field names): beam angles, beam origin offset and
+    lidar_to_sensor; use_extrinsics: the metadata's extrinsic on top, as the registration of `sequence.run_events` has it"""
+    fmt = info.format
+    ext = np.array(info.extrinsic, dtype=np.float64) if use_extrinsics and hasattr(info, "extrinsic") else None
+    return core.Lut(fmt.pixels_per_column, fmt.columns_per_frame, info.beam_altitude_angles, info.beam_azimuth_angles,
+                    info.lidar_origin_to_beam_origin_mm, np.array(info.lidar_to_sensor_transform, dtype=np.float64), ext, device_id=device_id)
+
+
+def add_packet_bag(acc, bags, info, traj, start_scan=0, end_scan=None, device_id=0):
+    """every sweep [start_scan, end_scan] of a raw packet bag (or list of bags) into `acc`, decoded by the package's own packet feed and posed by
+    `traj` at its decoded column times (the fused per-call path); the feed is closed afterwards"""
+    from . import packets as pk
+    from .bag import OusterPacketBagSource
+    feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info, device_id=device_id)
+    try:
+        for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+            if not hasattr(d, "lacc"):
+                acc.update(d, traj=traj)
+    finally:
+        feed.close()
+

@@ -234,22 +234,45 @@ _PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {n}\n"
                "property double x\nproperty double y\nproperty double z\nend_header\n")
 
 
-def save_map_ply(path: str, xyz) -> None:
+_PLY_SCALARS = (("int", "neighbours"), ("double", "plane_var"), ("double", "entropy"))
+_PLY_XYZ = [("double", "x"), ("double", "y"), ("double", "z")]
+_PLY_SCORED_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("neighbours", "<i4"), ("plane_var", "<f8"), ("entropy", "<f8")])
+
+
+def save_map_ply(path: str, xyz, scalars=None) -> None:
     """A point map (N, 3) to disk: PLY `binary_little_endian 1.0`, `element vertex N`, three `property double` x y z - the doubles
-    as they are, so a map read back is bit-equal; a path ending in .npy uses np.save instead"""
+    as they are, so a map read back is bit-equal; a path ending in .npy uses np.save instead.
+    scalars = (neighbours (N,) int, plane_var (N,), entropy (N,)) - the per-point values of a map score: three more
+    properties behind x y z (`int neighbours`, `double plane_var`, `double entropy`); PLY only (a .npy map is the points and nothing else).
+    Without scalars the file is what it always was, byte for byte."""
     pts = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    if scalars is not None:
+        nb, pv, ent = (np.asarray(a).reshape(-1) for a in scalars)
+        if not len(nb) == len(pv) == len(ent) == len(pts):
+            raise ValueError("scalars: one neighbours / plane_var / entropy value per point")
     if str(path).endswith(".npy"):
+        if scalars is not None:
+            raise ValueError("per-point scalars are written to a PLY file only: a .npy map holds the points")
         np.save(path, pts)
         return
     with open(path, "wb") as f:
-        f.write(_PLY_HEADER.format(n=len(pts)).encode("ascii"))
-        f.write(pts.astype("<f8", copy=False).tobytes())
+        if scalars is None:
+            f.write(_PLY_HEADER.format(n=len(pts)).encode("ascii"))
+            f.write(pts.astype("<f8", copy=False).tobytes())
+            return
+        extra = "".join(f"property {t} {name}\n" for t, name in _PLY_SCALARS)
+        f.write(_PLY_HEADER.format(n=len(pts)).replace("end_header\n", extra + "end_header\n").encode("ascii"))
+        rec = np.empty(len(pts), dtype=_PLY_SCORED_DTYPE)
+        rec["xyz"], rec["neighbours"], rec["plane_var"], rec["entropy"] = pts, nb, pv, ent
+        f.write(rec.tobytes())
 
 
-def load_map_ply(path: str) -> np.ndarray:
-    """(N, 3) float64 of a map written by `save_map_ply` (.npy: np.load).  Reads the PLY subset that function writes."""
+def load_map_ply(path: str, scalars: bool = False):
+    """(N, 3) float64 of a map written by `save_map_ply` (.npy: np.load), with or without per-point scalars.  Reads the PLY subset that
+    function writes.  scalars=True: (points, (neighbours int32, plane_var, entropy)), the second None for a file without them."""
     if str(path).endswith(".npy"):
-        return np.load(path).reshape(-1, 3)
+        pts = np.load(path).reshape(-1, 3)
+        return (pts, None) if scalars else pts
     with open(path, "rb") as f:
         n, fmt, props = None, None, []
         if f.readline().strip() != b"ply":
@@ -268,12 +291,21 @@ def load_map_ply(path: str) -> np.ndarray:
                 props.append(tuple(w[1:]))
         else:
             raise ValueError(f"{path}: no end_header")
-        if fmt != "binary_little_endian" or n is None or props != [("double", "x"), ("double", "y"), ("double", "z")]:
-            raise ValueError(f"{path}: expected binary_little_endian, element vertex N, property double x y z")
-        data = f.read(n * 24)
-    if len(data) != n * 24:
-        raise ValueError(f"{path}: {n} vertices announced, {len(data) // 24} present")
-    return np.frombuffer(data, dtype="<f8").astype(np.float64).reshape(n, 3)
+        scored = props == _PLY_XYZ + list(_PLY_SCALARS)
+        if fmt != "binary_little_endian" or n is None or not (props == _PLY_XYZ or scored):
+            raise ValueError(f"{path}: expected binary_little_endian, element vertex N, property double x y z"
+                             " (optionally int neighbours, double plane_var, double entropy)")
+        size = _PLY_SCORED_DTYPE.itemsize if scored else 24
+        data = f.read(n * size)
+    if len(data) != n * size:
+        raise ValueError(f"{path}: {n} vertices announced, {len(data) // size} present")
+    if not scored:
+        pts = np.frombuffer(data, dtype="<f8").astype(np.float64).reshape(n, 3)
+        return (pts, None) if scalars else pts
+    rec = np.frombuffer(data, dtype=_PLY_SCORED_DTYPE)
+    pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
+    extras = (rec["neighbours"].astype(np.int32), rec["plane_var"].astype(np.float64), rec["entropy"].astype(np.float64))
+    return (pts, extras) if scalars else pts
 
 
 def nc_gt_file_rows(t, poses) -> List[Tuple[float, np.ndarray]]:
