@@ -222,6 +222,15 @@ int ptl_icp_debug_stall_workgroup(ptl_icp *h, int32_t wg);
 /* test hook: at most `free_blocks` free voxel blocks left in the pool (< 0: unchanged), `table_used` map-table entries declared
  * taken (< 0: unchanged): the following map updates raise the pool / table capacity flags (PTL_ERR_CAPACITY at the next wait) */
 int ptl_icp_debug_limit_capacity(ptl_icp *h, int32_t free_blocks, int64_t table_used);
+/* test hook: a read-only dump of the handle's map table.  Waits for the handle's map stream and main stream, then copies to the host
+ * (every array nullable): `entries` - the table's slots, 16 bytes each: u64 key (all ones = empty, all ones - 1 = tombstone; else the
+ * voxel's three indices + 2^20 in 21 bits each, x highest), i32 block id | stored count << 24 (-1 = none), i32 list head; `bhdr` - the block
+ * directory, 4 i32 per block: stored count, table slot, batch points pending, pad; `bfirst` - 3 doubles per block, the voxel's first point.
+ * info: [0] table entries created since the last rebuild (tombstones included), [1] live voxels, [2] the device error flags (returned,
+ * not raised), [3] slots - 1 of the map table, [4] / [5] of the pass-1 / pass-2 per-scan voxel tables, [6] blocks in the directory,
+ * [7] small blocks among them.  max_slots / max_blocks below [3] + 1 / [6]: PTL_ERR_CAPACITY.  No kernel runs and nothing on the device
+ * changes.  With ptl_batch_icp / ptl_seq_icp it serves the members of a runner between its launches. */
+int ptl_icp_debug_table(ptl_icp *h, void *entries, int64_t max_slots, int32_t *bhdr, double *bfirst, int64_t max_blocks, int64_t info[8]);
 /* test hook: set the 22-bit launch epoch of the Gauss-Newton exchange (exercises its wrap-around) */
 int ptl_icp_debug_set_epoch(ptl_icp *h, uint32_t epoch);
 

@@ -754,6 +754,27 @@ extern "C" int ptl_icp_debug_limit_capacity(ptl_icp* h, int32_t free_blocks, int
     return PTL_OK;
 }
 
+// test hook: the handle's map table, block directory and table counters as they are, copied to the host.  Waits for the map stream and the
+// main stream, launches no kernel, writes nothing on the device and reports no error flag as an error (it returns the word)
+extern "C" int ptl_icp_debug_table(ptl_icp* h, void* entries, int64_t max_slots, int32_t* bhdr, double* bfirst, int64_t max_blocks, int64_t info[8]) {
+    if (!h || !info) return set_err(PTL_ERR_ARG, "null argument");
+    const Ctx& c = h->c;
+    const int64_t slots = (int64_t)c.tmask + 1;
+    if ((entries && max_slots < slots) || ((bhdr || bfirst) && max_blocks < c.pool_cap))
+        return set_err(PTL_ERR_CAPACITY, "the table has %lld slots and the directory %d blocks", (long long)slots, c.pool_cap);
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(h->map_stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    DevState st;
+    HIPCHK(hipMemcpy(&st, c.st, sizeof st, hipMemcpyDeviceToHost));
+    if (entries) HIPCHK(hipMemcpy(entries, c.tab, (size_t)slots * sizeof(TabEnt), hipMemcpyDeviceToHost));
+    if (bhdr) HIPCHK(hipMemcpy(bhdr, c.bhdr, (size_t)c.pool_cap * 4 * sizeof(int), hipMemcpyDeviceToHost));
+    if (bfirst) HIPCHK(hipMemcpy(bfirst, c.bfirst, (size_t)c.pool_cap * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    info[0] = (int64_t)st.tab_used; info[1] = st.n_live; info[2] = st.err_flags; info[3] = (int64_t)c.tmask;
+    info[4] = (int64_t)c.vmask; info[5] = (int64_t)c.vmask2; info[6] = c.pool_cap; info[7] = c.n_small;
+    return PTL_OK;
+}
+
 // diagnostic: ticks every GN workgroup spent in the search phase since creation: out[0..G) until its last wavefront
 // finished, out[G..2G) its first wavefront
 extern "C" int ptl_icp_gn_wg_clocks(ptl_icp* h, int64_t* out, int32_t max_wgs) {
