@@ -421,7 +421,9 @@ int ptl_batch_team_workgroups(ptl_batch *b, int32_t *team_workgroups, int32_t *t
  * settle), [1] probe rows rebuilt (27 hash probes each), [2] stored map points read by the searches, [3] Gauss-Newton
  * iterations, [4] / [5] voxel claims of down-sampling pass 1 / 2, [6] source point-iterations, [7] scans, [8] point-iterations settled as
  * "nothing in reach" (the point's last search found its 27 voxels empty and it has not left its voxel: neither a row evaluation nor a
- * search - exact, the map does not change inside a registration), [9..15] reserved (0). */
+ * search - exact, the map does not change inside a registration), [9] frame_downsample points the map update dropped where it found
+ * their voxel already holding max_points_per_voxel points (no list push, no world-frame copy, nothing for the later phases to walk),
+ * [10..15] reserved (0). */
 int ptl_batch_exec_counters(ptl_batch *b, int32_t seq, uint64_t out[16]);
 /* Where the scans of sequence `seq` ran in the free-running kernel, cumulative since the cold start: out[0] scans run by a
  * team of another XCD than the sequence's home XCD (seq & 7) - a team whose own XCD had nothing for it; out[1] scans that

@@ -847,7 +847,7 @@ class BatchRunner(_Runner):
         return g.value, t.value
 
     EXEC_COUNTERS = ("searches", "rows_rebuilt", "map_points_read", "gn_iterations", "vds1_claims", "vds2_claims",
-                     "point_iterations", "scans", "settled_nothing_in_reach")
+                     "point_iterations", "scans", "settled_nothing_in_reach", "dropped_full_voxel")
 
     def exec_counters(self, s):
         """executed-work counters of sequence s, cumulative since the cold start (include/ptudes_mi.h ptl_batch_exec_counters)"""

@@ -96,6 +96,7 @@ struct DevState {
     int pool_hw, pool_hw_s;   // high-water marks: full blocks (an id bound, >= n_small) | small blocks
     int free_top, n_live;
     int free_top_s, mig_n;    // free small blocks | small blocks waiting for their move to a full block (this scan)
+    int ulist_n, ulist_pad;   // free-running kernel: points of this scan's batch that insert a left with a slot (the compact list in plen[])
     long long map_points;
     unsigned tab_used;
     int err_flags;
@@ -111,6 +112,8 @@ struct DevState {
     // 8-lane Gauss-Newton loop, cumulative like exec_cnt: point-iterations settled as "nothing in reach" (the point's last search found its 27
     // voxels empty and it has not left its voxel since: no row evaluation, no search)
     unsigned long long empty_cnt;
+    // map update, cumulative like exec_cnt: points dropped by insert a because their voxel already held max_points_per_voxel points
+    unsigned long long full_cnt;
     // IMU deskew, off while dk_knots is null; a cold start (k_state_init) keeps these
     const double* dk_knots;       // the filter's knot list, [cap][8]: ts, pos[3], q xyzw[4] (EkfState::knots)
     const long long* dk_nknots;   // ... its length (EkfState::knot_count)
@@ -2643,18 +2646,25 @@ __global__ __launch_bounds__(GN8_MAX_THREADS) SEQ_OCC void k_gn_loop8(Ctx c, int
 
 // ------------------------------------------------------------------------------------------------ K7-K9
 // AddPoints, phase a: world transform, find-or-create the voxel's table entry, join its batch list.
+// A point whose voxel already holds P points is settled here: AddPoints stores nothing for it, so it joins no list, needs no
+// world-frame copy and gets "no slot" - phases b and c and the prune pass then treat its voxel as one the batch never touched.  In a
+// map that has filled up that is nine points of ten.
 // `pose` null => points are already in the world frame (stage-level API)
 // (U points per thread as in K1-K4: the first table read of each, then the compare-and-swaps, then the list pushes travel together)
-template <int U>
+// LIST (the free-running kernel): the points that keep a slot are appended to a compact list (plen[], which only the other drivers' phase
+// b / c use; st->ulist_n entries, in no particular order) - one atomic per wavefront and pass, ranks by ballot as in the pool pop below -
+// and phase b walks that list instead of all points.
+template <int U, bool LIST = false>
 __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_in, const int* n_ptr, int n_fixed,
                                                       int use_pose, const Slice sl) {
     const int n = n_ptr ? *n_ptr : n_fixed;
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
     DevState* st = c.st;
     int idx[U], slot[U];
-    bool act[U], keyed[U];
+    bool act[U], keyed[U], full[U];
     unsigned long long key[U], cur[U], old[U];
     unsigned s0[U];
+    int cb[U];
     V3 p[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -2666,21 +2676,30 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
     if (use_pose) T = rt_from16(st->new_pose);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        slot[u] = -1; keyed[u] = false; key[u] = EMPTY_KEY; s0[u] = 0u; cur[u] = 0ull;
+        slot[u] = -1; keyed[u] = false; key[u] = EMPTY_KEY; s0[u] = 0u; cur[u] = 0ull; cb[u] = -1;
         if (!act[u]) continue;
-        const size_t i = (size_t)idx[u];
         if (use_pose) p[u] = rt_apply(T, p[u]);
-        c.fdw[3 * i] = p[u].x; c.fdw[3 * i + 1] = p[u].y; c.fdw[3 * i + 2] = p[u].z;
         int kx, ky, kz;
         keyed[u] = vox_key(p[u], c.vs, key[u], kx, ky, kz);
         if (!keyed[u]) { atomicOr(&st->err_flags, ERR_KEY_RANGE); continue; }
         s0[u] = brick_slot(key[u], c.tmask);
         cur[u] = c.tab[s0[u]].key;  // plain (L2-cached) read: EMPTY -> key is the only change in this kernel, so the worst a stale line shows is EMPTY - and then the swap decides
+        // ... and the stored count beside it, in the same 16-byte entry and the same request.  Counts change only in the prune, migrate and
+        // rebuild passes, behind team barriers (stream order in the other drivers): this plain read is as fresh as the key's.  An entry
+        // created in this pass shows -1 or a count of 0 - never full.
+        cb[u] = c.tab[s0[u]].blk;
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         old[u] = key[u];
         if (keyed[u] && cur[u] == EMPTY_KEY) old[u] = atomicCAS(&c.tab[s0[u]].key, EMPTY_KEY, key[u]);
+        // the world-frame copy is for phase b (and the migration pass), which read it for points with a slot only: none for a point whose
+        // home entry shows its voxel full.  (Decided at the first read: held back until the probing rounds are over, the points spill.  The
+        // few points that find their full voxel further down the chain have left a copy nobody reads.)
+        if (keyed[u] && !(cur[u] == key[u] && cb[u] >= 0 && (cb[u] >> 24) >= c.P)) {
+            const size_t i = (size_t)idx[u];
+            c.fdw[3 * i] = p[u].x; c.fdw[3 * i + 1] = p[u].y; c.fdw[3 * i + 2] = p[u].z;
+        }
     }
     bool created[U], pend[U];
     unsigned sp[U];
@@ -2696,6 +2715,7 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
         const bool found = keyed[u] && (cur[u] == key[u] || (was_empty && old[u] == key[u]));
         created[u] = keyed[u] && was_empty && old[u] == EMPTY_KEY;
         slot[u] = (found || created[u]) ? (int)s0[u] : -1;
+        full[u] = keyed[u] && cur[u] == key[u] && cb[u] >= 0 && (cb[u] >> 24) >= c.P;  // (the count against P alone: a small block's capacity is below it)
         pend[u] = keyed[u] && !found && !created[u];  // occupied by another voxel or a tombstone (or the swap lost to another key): linear probing goes on
     }
     // ... in rounds: the next slot of every unsettled point is read, then the swaps on the empty ones are sent, then all are
@@ -2706,10 +2726,11 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
         for (int u = 0; u < U; ++u) anyp = anyp || pend[u];
         if (!anyp) break;
         unsigned long long ck[U], o[U];
+        int kb[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            ck[u] = 0ull;
-            if (pend[u]) { sp[u] = (sp[u] + 1) & c.tmask; ck[u] = c.tab[sp[u]].key; }
+            ck[u] = 0ull; kb[u] = -1;
+            if (pend[u]) { sp[u] = (sp[u] + 1) & c.tmask; ck[u] = c.tab[sp[u]].key; kb[u] = c.tab[sp[u]].blk; }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -2722,6 +2743,7 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
             const bool found = pend[u] && (ck[u] == key[u] || (was_empty && o[u] == key[u]));
             const bool made = pend[u] && was_empty && o[u] == EMPTY_KEY;
             slot[u] = (found || made) ? (int)sp[u] : slot[u];
+            full[u] = full[u] || (pend[u] && ck[u] == key[u] && kb[u] >= 0 && (kb[u] >> 24) >= c.P);
             created[u] = created[u] || made;
             pend[u] = pend[u] && !found && !made;
         }
@@ -2729,6 +2751,28 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
 #pragma unroll
     for (int u = 0; u < U; ++u)
         if (keyed[u] && slot[u] < 0) { atomicOr(&st->err_flags, ERR_TABLE); MAP_DIAG_AT(st, 0, idx[u], s0[u]); }
+    // (only now - a point of a full voxel HAS found its entry, it is no table error -) the points of full voxels give up their slot
+    {
+        int nd = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) { nd += __popcll(__ballot(full[u])); slot[u] = full[u] ? -1 : slot[u]; }
+        if ((threadIdx.x & 63) == 0 && nd) atomicAdd(&st->full_cnt, (unsigned long long)nd);  // executed-work counter, one atomic per wavefront and pass
+    }
+    if (LIST) {
+        const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+        unsigned long long mk[U];
+        int pre[U], tot = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) { mk[u] = __ballot(slot[u] >= 0); pre[u] = tot; tot += __popcll(mk[u]); }
+        if (tot > 0) {  // (uniform over the wavefront)
+            int at = 0;
+            if ((threadIdx.x & 63) == 0) at = atomicAdd(&st->ulist_n, tot);
+            at = __shfl(at, 0);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (slot[u] >= 0) c.plen[at + pre[u] + __popcll(mk[u] & below)] = idx[u];
+        }
+    }
     // the list pushes need the slot only - sent before the creation chain below (pool pop -> free-stack read -> header), whose round trips
     // they then share instead of following them
     int nx[U];
@@ -2821,19 +2865,30 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
-        if (act[u]) { c.pslot[idx[u]] = slot[u]; c.nxt[idx[u]] = nx[u]; }
+        if (act[u]) {
+            c.pslot[idx[u]] = slot[u];
+            if (slot[u] >= 0) c.nxt[idx[u]] = nx[u];  // (a point without a slot is on no list)
+        }
 }
 // phase b: rank among this batch's points of the same voxel (by scan order) -> slot in the block
 // FUSE (the free-running kernel, where the prune pass always follows): the voxel's first point of the batch leaves the batch's
 // length in the block header, and the prune pass - which reads every live header anyway - counts it in, mirrors the count in
 // the table entry and resets the list: phase c, its pass over the points with two dependent reads and its barrier are gone.
-template <int U, bool FUSE = false>
+// LIST: over the compact list insert a<.., true> left (n = its length): entry q names the point.  The rank is decided by comparing point
+// indices along the voxel's list, so the order of the compact list does not show.
+template <int U, bool FUSE = false, bool LIST = false>
 __device__ __forceinline__ void d_map_insert_b(const Ctx& c, const int* n_ptr, int n_fixed, const Slice sl) {
-    const int n = n_ptr ? *n_ptr : n_fixed;
+    const int nq = n_ptr ? *n_ptr : n_fixed;
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
     int idx[U], slot[U], j[U], rank[U], len[U], pb[U];
+    const int n = LIST ? 0x7FFFFFFF : nq;  // (a listed index is a point of the batch)
 #pragma unroll
-    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; slot[u] = (idx[u] < n) ? c.pslot[idx[u]] : -1; }
+    for (int u = 0; u < U; ++u) {
+        idx[u] = base + u * BS;
+        if (LIST) idx[u] = (idx[u] < nq) ? c.plen[idx[u]] : 0x7FFFFFFF;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) slot[u] = (idx[u] < n) ? c.pslot[idx[u]] : -1;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         rank[u] = 0; len[u] = 0; j[u] = -1; pb[u] = -1;
@@ -2856,7 +2911,7 @@ __device__ __forceinline__ void d_map_insert_b(const Ctx& c, const int* n_ptr, i
         if (idx[u] < n && slot[u] >= 0 && pb[u] >= 0) { w[u][0] = c.fdw[3 * i]; w[u][1] = c.fdw[3 * i + 1]; w[u][2] = c.fdw[3 * i + 2]; }
     }
     for (int steps = 0;; ++steps) {  // the U list walks step together: their reads of nxt[] are in flight at the same time
-        if (steps > n) { atomicOr(&c.st->err_flags, ERR_TABLE); MAP_DIAG_AT(c.st, 2, idx[0], n); break; }  // (a list longer than the batch: corrupted links must not hang the launch)
+        if (steps > (LIST ? c.n_max : n)) { atomicOr(&c.st->err_flags, ERR_TABLE); MAP_DIAG_AT(c.st, 2, idx[0], n); break; }  // (a list longer than the batch: corrupted links must not hang the launch)
         bool any = false;
 #pragma unroll
         for (int u = 0; u < U; ++u) any = any || j[u] >= 0;

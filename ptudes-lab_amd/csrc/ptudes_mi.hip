@@ -2578,7 +2578,7 @@ extern "C" int ptl_batch_exec_counters(ptl_batch* b, int32_t s, uint64_t out[16]
     HIPCHK(hipStreamSynchronize(b->stream));
     memset(out, 0, 16 * sizeof(uint64_t));
     HIPCHK(hipMemcpy(out, (char*)b->lane[s].icp->c.st + offsetof(DevState, exec_cnt), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out + 8, (char*)b->lane[s].icp->c.st + offsetof(DevState, empty_cnt), sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out + 8, (char*)b->lane[s].icp->c.st + offsetof(DevState, empty_cnt), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));  // [8] empty_cnt, [9] full_cnt
     return PTL_OK;
 }
 extern "C" int ptl_batch_gn_phases(ptl_batch* b, int64_t out[8]) {

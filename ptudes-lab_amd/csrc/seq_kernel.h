@@ -193,13 +193,17 @@ __device__ __noinline__ unsigned sq_map_update(const SeqCtx* a, int s, int k, in
     sl.nb = nbd; sl.clk = 0;
     const TeamEnv te = {word, &st->gn_abort, st, local};
     SQ_CLK_DECL;
-    for (sl.b = sq_grab(ctr); sl.b < nbd; sl.b = sq_grab(ctr)) d_map_insert_a<UM>(c, c.fd, &st->n_down_ins, 0, 1, sl);
+    for (sl.b = sq_grab(ctr); sl.b < nbd; sl.b = sq_grab(ctr)) d_map_insert_a<UM, true>(c, c.fd, &st->n_down_ins, 0, 1, sl);
     SQ_CLK(10);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
     SQ_CLK(11);
-    for (sl.b = sq_grab(ctr + 1); sl.b < nbd; sl.b = sq_grab(ctr + 1)) d_map_insert_b<UM, true>(c, &st->n_down_ins, 0, sl);
+    // phase b over the points insert a left with a slot only (in a map that has filled up a tenth of the batch): one pass or two
+    const int nbl = (st->ulist_n + BU - 1) / BU;
+    sl.nb = nbl;
+    for (sl.b = sq_grab(ctr + 1); sl.b < nbl; sl.b = sq_grab(ctr + 1)) d_map_insert_b<UM, true, true>(c, &st->ulist_n, 0, sl);
     SQ_CLK(12);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
+    if (wg == 0 && threadIdx.x == 0) st->ulist_n = 0;  // (everybody has read it: the next scan's insert a starts from an empty list)
     SQ_CLK(13);
     SQ_CLK(14);  // (phase c is part of the prune pass here: d_map_insert_b / d_map_prune, FUSE)
     SQ_CLK(15);
