@@ -214,8 +214,16 @@ int ptl_icp_gn_phases(ptl_icp *h, int64_t out[8]);
 /* diagnostic: ticks each Gauss-Newton workgroup spent in the search phase since creation; out holds 2 * gn_workgroups
  * values (until the last / the first wavefront finished) */
 int ptl_icp_gn_wg_clocks(ptl_icp *h, int64_t *out, int32_t max_wgs);
-/* diagnostic: the device state's 32 debug sums (phase-clock builds park sub-step clocks there) */
+/* diagnostic: what the handle's last ptl_icp_linear_system left on the device: [0..27) the sums, [27] the pair count, [28] the
+ * candidate count, the rest 0 (all 0 after a cold start).  The diagnostic builds' values are read with ptl_icp_diag. */
 int ptl_icp_debug_sums(ptl_icp *h, double out[32]);
+/* diagnostic builds (csrc/diag.h: make PHASES=1, IT0=1, STAGES=1, EXTRA=-DMAP_DIAG; ptl_build_info [13]): every value they collect has a
+ * named 64-bit slot.  ptl_diag_slots() of them, slot i named ptl_diag_slot_name(i) (a static string; null outside the range);
+ * ptl_icp_diag copies them all (max_slots >= ptl_diag_slots()), cumulative since the handle's cold start, all 0 in the product build.
+ * With ptl_batch_icp / ptl_seq_icp it reads a member of a runner between its launches. */
+int ptl_diag_slots(void);
+const char *ptl_diag_slot_name(int slot);
+int ptl_icp_diag(ptl_icp *h, int64_t *out, int32_t max_slots);
 /* test hook: workgroup `wg` of the following Gauss-Newton launches returns at once (-1 = back to normal, also clears the
  * time-out flag): the others must run into the exchange time-out, abort together and report it - not hang */
 int ptl_icp_debug_stall_workgroup(ptl_icp *h, int32_t wg);
@@ -463,7 +471,7 @@ int ptl_batch_debug_set_map_points_per_thread(ptl_batch *b, int32_t points, int3
  * and pass of K1 + map update / K2-K4 in the free-running kernel, [5] threads per workgroup of the 8-lane kernels,
  * [6] lanes per point of the full search, [7] nearest other boxes in its first round, [8] voxels per survivor round,
  * [9] chunks phase A requests ahead, [10] 1000 x the pruning margin, [11] / [12] bytes per map-table / voxel-table
- * entry, [13] 1 when diagnostic clocks are compiled in, [14] reserved (0; rounds 5's movement-budget experiment is gone from the sources). */
+ * entry, [13] the diagnostic flavours compiled in, a bit each: 1 PHASES, 2 IT0, 4 STAGES, 8 MAP_DIAG (0 = the product build), [14] reserved (0; rounds 5's movement-budget experiment is gone from the sources). */
 int ptl_build_info(int32_t out[16]);
 /* identity of what THIS library was built from: sha256 over the kernel sources, the Makefile and the experiment flags (12 hex digits,
  * csrc/Makefile CODE_ID).  bench.py records it in its line and tools/pmc_summary.py in every counter summary: a counter pass speaks

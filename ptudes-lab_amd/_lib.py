@@ -114,6 +114,9 @@ PROTOTYPES = {
     "ptl_range_stats": (C.c_int, [C.c_int, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_d_p]),
     "ptl_icp_debug_set_epoch": (C.c_int, [_vp, C.c_uint32]),
     "ptl_icp_debug_sums": (C.c_int, [_vp, c_d_p]),
+    "ptl_diag_slots": (C.c_int, []),
+    "ptl_diag_slot_name": (C.c_char_p, [C.c_int]),
+    "ptl_icp_diag": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int32]),
     "ptl_icp_debug_stall_workgroup": (C.c_int, [_vp, C.c_int32]),
     "ptl_icp_debug_limit_capacity": (C.c_int, [_vp, C.c_int32, C.c_int64]),
     "ptl_icp_debug_table": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int32), c_d_p, C.c_int64, c_i64_p]),

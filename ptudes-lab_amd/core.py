@@ -58,6 +58,15 @@ class MapScore:
                 f"  mean map entropy: {self.mean_entropy:.6f}"]
 
 
+def _diag(icp_handle):
+    """{name: value} of the named slots a diagnostic build collects for one registration handle (csrc/diag.h; all 0 in the product build),
+    cumulative since its cold start; the names are the library's own (include/ptudes_mi.h ptl_icp_diag)"""
+    n = L.lib().ptl_diag_slots()
+    out = (C.c_int64 * n)()
+    L.check(L.lib().ptl_icp_diag(icp_handle, out, n))
+    return {L.lib().ptl_diag_slot_name(i).decode(): int(out[i]) for i in range(n)}
+
+
 class Icp:
     def __init__(self, max_range=100.0, min_range=5.0, lazy_map_stats=False, **over):
         """lazy_map_stats: registrations return when the pose is there, before the scan's map update is complete (the per-scan rows then
@@ -243,6 +252,9 @@ class Icp:
         L.check(L.lib().ptl_icp_linear_system(self._h, L.dptr(s), len(s), max_dist, kernel, L.dptr(sums),
                                               C.byref(nc), C.byref(cand)))
         return sums, nc.value, cand.value
+
+    def diag(self):
+        return _diag(self._h)
 
     def align(self, frame, guess, max_dist, kernel):
         f = L.as_f64(frame)
@@ -767,6 +779,11 @@ class SeqRunner(_Runner):
     def upload_imu(self, imu_rows, imu_end):
         L.check(L.lib().ptl_seq_upload_imu(self._h, *_imu_args(self.n_scans, imu_rows, imu_end)))
 
+    def diag(self):
+        h = C.c_void_p()
+        L.check(L.lib().ptl_seq_icp(self._h, C.byref(h)))
+        return _diag(h)
+
     def advance(self, n):
         L.check(L.lib().ptl_seq_advance(self._h, n))
 
@@ -854,6 +871,11 @@ class BatchRunner(_Runner):
         out = (C.c_uint64 * 16)()
         L.check(L.lib().ptl_batch_exec_counters(self._h, s, out))
         return dict(zip(self.EXEC_COUNTERS, (int(v) for v in out)))
+
+    def diag(self, s):
+        h = C.c_void_p()
+        L.check(L.lib().ptl_batch_icp(self._h, int(s), C.byref(h)))
+        return _diag(h)
 
     def sched_counters(self, s):
         """where the scans of sequence s ran: scans taken by a team of another XCD, cross-XCD hand-overs, last XCC id + 1"""

@@ -24,6 +24,7 @@
 // ascending, insertion order) candidate order, voxel index by truncation toward zero.
 #pragma once
 #include "devmath.h"
+#include "diag.h"
 #include <stdint.h>
 #include <type_traits>
 
@@ -36,13 +37,6 @@
 #define ERR_TABLE 4
 #define ERR_VDS_TABLE 8
 #define ERR_GN_TIMEOUT 16
-// make EXTRA=-DMAP_DIAG: every site that raises ERR_TABLE counts itself in st->dbg_sums[24 + site] and leaves two values of its first
-// occurrence in dbg_sums[28..31] (tools/um_diag.py reads them)
-#ifdef MAP_DIAG
-#define MAP_DIAG_AT(st_, site, a_, b_) do { if (atomicAdd(&(st_)->dbg_sums[24 + (site)], 1.0) == 0.0) { (st_)->dbg_sums[28] = (double)(site); (st_)->dbg_sums[29] = (double)(a_); (st_)->dbg_sums[30] = (double)(b_); } } while (0)
-#else
-#define MAP_DIAG_AT(st_, site, a_, b_) do { } while (0)
-#endif
 
 struct TabEnt {
     unsigned long long key;
@@ -73,7 +67,7 @@ struct DevState {
     long long gn_cand;
     double gn_max_dist, gn_kernel;
     double T_icp[16];
-    double dbg_sums[32];
+    double lin_sums[32];        // ptl_icp_linear_system (k_gn_loop in mode 1): the 27 sums, the pair count, the candidate count
     long long gn_phase_clk[8];  // accumulated s_memtime ticks of WG0: nn, wg-reduce, barrier, grid-reduce, solve
     long long seq_clk[8];       // free-running kernel, 100 MHz wall-clock ticks summed over scans: workgroup 0's K0-K4 | wait before GN |
                                 // GN | wait after GN | map update; [5] the filter workgroup's step; [6] scans; [7] stage-internal barrier waits of workgroup 0
@@ -174,7 +168,8 @@ struct Ctx {
     unsigned long long* gn_rows_ll;  // [2][G][64]      per-workgroup sums as (32 data bits | 32 flag bits) words
     unsigned long long* gn_xsum_ll;  // [2][8][8][64]   per-group sums, one copy per consumer slot
     int overlap_pre;          // the next scan's K0-K4 run beside this scan's map update (own stream): see flush_map_stats
-    long long* wg_clk;        // [2 G] diagnostic: ticks each GN workgroup spent in the search phase (all waves / first wave)
+    long long* wg_clk;        // [2 G] ticks each GN workgroup spent in the search phase (all waves / first wave), indexed [wg] and [team size + wg];
+                              // behind them [DIAG_SLOTS] the named slots of the diagnostic builds (diag.h), empty in the product build
     int traj_cap;
 };
 
@@ -548,11 +543,6 @@ __device__ __forceinline__ int block_count_u(const bool (&f)[U]) {
 }
 
 // ------------------------------------------------------------------------------------------------ K1
-#ifdef SEQ_STAGE_CLOCKS
-#define K1_CLK(i) do { __builtin_amdgcn_s_waitcnt(0); const long long n_ = (long long)wall_clock64(); if (k1_me) st->dbg_sums[i] += (double)(n_ - k1_t); k1_t = n_; } while (0)
-#else
-#define K1_CLK(i) do { } while (0)
-#endif
 // the raw f32 points of one block, as a pass of K1 wants them: the free-running kernel requests the NEXT pass's while the
 // current pass waits for its hash atomics (one dependent memory round trip per pass less)
 template <int U> struct RawF32 { float v[U][3]; };
@@ -572,10 +562,7 @@ template <int U>
 __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, const RawF32<U>* pre = nullptr, int* wave_valid = nullptr) {
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
     DevState* st = c.st;
-#ifdef SEQ_STAGE_CLOCKS
-    long long k1_t = (long long)wall_clock64();
-    const bool k1_me = sl.clk != 0 && threadIdx.x == 0;  // (workgroup 0 of the team)
-#endif
+    DiagLap<diag::stages, false, true> k1(sl.clk != 0 && threadIdx.x == 0);  // (workgroup 0 of the team)
     const int do_deskew = st->do_deskew;
     int idx[U];
     bool valid[U], keyed[U];
@@ -585,7 +572,7 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
     for (int u = 0; u < U; ++u) idx[u] = base + u * BS;
     // (the pass-2 voxel slots of the previous scan are released by their winners in K4 since round 4 - until then this pass began
     // with a read of every point's slot word and the stores that release the winners' entries: 34 of K1's 343 us)
-    K1_CLK(20);
+    k1.lap(c, D_k1_entry);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = idx[u];
@@ -645,7 +632,7 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
     // same-address atomics serialise at the memory side.  Only the first lane of each run of equal keys within the
     // wavefront - the lowest index of the run, the only one that can win - claims the slot and bids for it; the others
     // take the slot from it.
-    K1_CLK(21);
+    k1.lap(c, D_k1_load_deskew_store);
     {
         const int lane = threadIdx.x & 63;
         bool head[U];
@@ -663,9 +650,9 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
             for (int u = 0; u < U; ++u) nh += __popcll(__ballot(head[u]));
             if (lane == 0 && nh) atomicAdd(&st->exec_cnt[4], (unsigned long long)nh);
         }
-        K1_CLK(22);
+        k1.lap(c, D_k1_claim);
         vds_bid_u<U>(c.vtab1, slot, head, idx, &st->err_flags);
-        K1_CLK(23);
+        k1.lap(c, D_k1_bid);
         // Only the HEAD of a run of equal keys can be its voxel's first point in scan order (every other point of the run has a lower
         // index of the same voxel right beside it in this wavefront), so only heads keep their slot: K3 then reads the slot's winner
         // for 46 k points of a sweep instead of 120 k (scattered 16-byte reads), and the heads' slots need not be handed down the runs
@@ -674,7 +661,7 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
         for (int u = 0; u < U; ++u)
             if (idx[u] < c.n_in) c.slot1[idx[u]] = head[u] ? slot[u] : -1;
     }
-    K1_CLK(24);
+    k1.lap(c, D_k1_slot1);
     if (wave_valid) {
         // the caller walks many blocks (free-running kernel): this wavefront's valid points are summed in a register over all of them and
         // added to the scan's counter once at the end - no workgroup-wide count (two barriers) and no atomic per block (55 of K1's 343 us)
@@ -686,7 +673,7 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
         const int nv = block_count_u<U>(valid);
         if (threadIdx.x == 0 && nv) atomicAdd(&st->n_valid, nv);
     }
-    K1_CLK(25);
+    k1.lap(c, D_k1_count);
 }
 
 // the per-point word a pass of K2 / K3 / K4 starts from (slot1 / slot2), requested a pass ahead like K1's raw points
@@ -1352,14 +1339,8 @@ __device__ __forceinline__ double gn_ll_join(unsigned half) {
     return __longlong_as_double((long long)(((unsigned long long)other << 32) | half));  // meaningful in even lanes
 }
 
-// In-kernel phase clocks (tools_phase.py, ptl_icp_gn_phases / ptl_icp_gn_wg_clocks) are compiled in only with
-// -DGN_PHASE_CLOCKS (make PHASES=1): eight 64-bit accumulators and the counter reads otherwise compete with the loop's
-// live values for scalar and vector registers (the 32-lane kernel runs at its 128-VGPR cap and spills).
-#if defined(GN_PHASE_CLOCKS) || defined(GN_IT0_CLOCK)  /* (make IT0=1: only the split first iteration / other iterations of the point loop) */
-#define GN_CLK() ((long long)__builtin_readcyclecounter())
-#else
-#define GN_CLK() (0ll)
-#endif
+// In-kernel phase clocks (tools/phase.py, ptl_icp_gn_phases / ptl_icp_gn_wg_clocks) read GN_CLK() (diag.h): the cycle counter in a
+// make PHASES=1 / IT0=1 build, 0 in the product build.
 
 // ---- what the two persistent Gauss-Newton loops share: gn_loop_body (32 lanes per point, rows of GN32_ROW_ENTRIES) and gn8_body
 // (8 lanes per point, rows of GN8_ROW_ENTRIES) must agree bit for bit on the totals, on dx, on convergence and on the result (a
@@ -1548,7 +1529,7 @@ __device__ __forceinline__ void gn_store_result(DevState* st, const double* Tsh,
 // bit-for-bit on dx and on convergence.  Within a 32-lane group lane k accumulates entry k of the 27 sums (21 JTJ
 // upper triangle + 6 JTr); lane 27 counts pairs.
 // mode 0: a scan: source = guess * src0, loop to convergence, then the post-ICP bookkeeping.
-// mode 1: src_cur given in world frame, one pass, sums exported to st->dbg_sums (teacher-forced entry).
+// mode 1: src_cur given in world frame, one pass, sums exported to st->lin_sums (teacher-forced entry).
 // mode 2: like 0 without touching the trajectory (ptl_icp_align).
 #ifndef GN_MAX_THREADS
 #define GN_MAX_THREADS 512
@@ -1730,7 +1711,7 @@ __device__ __forceinline__ void gn_loop_body(const Ctx& c, int mode, const int G
         if (tid == (int)blockDim.x - 1) cand_total_sh += (long long)tot[GN_TOT_CAND];  // (a lane of the last wavefront: off the serial path)
         iters = it + 1;
         const int done = flag_done2[it & 1];
-        if (mode == 1 && wg == 0 && tid < GN32_ROW_ENTRIES) st->dbg_sums[tid] = tot[tid];
+        if (mode == 1 && wg == 0 && tid < GN32_ROW_ENTRIES) st->lin_sums[tid] = tot[tid];
         if (done) break;
     }
     if (tid == 64 && iters > 0) gn_compose(Esh2[(iters - 1) & 1], Tsh);  // the last increment
@@ -1901,13 +1882,9 @@ template <int PC, int LP>
 __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, double inv_vs, int laneL, int gb, V3& t, double& m, bool& found, int& ctot,
                                            unsigned* xc) {
     constexpr int RE = 32 / LP;  // row entries per lane
-#ifdef GN_PHASE_CLOCKS
-#define SRCH_CLK(k) do { __builtin_amdgcn_s_waitcnt(0); const long long n_ = GN_CLK(); if (srch_me) atomicAdd((unsigned long long*)&c.wg_clk[61 + (k)], (unsigned long long)(n_ - srch_t)); srch_t = n_; } while (0)
-    const bool srch_me = it > 0 && blockIdx.x < 8 && threadIdx.x == 0;  // (thread 0 of workgroup 0 of the sequences on the first teams)
-    long long srch_t = GN_CLK();
-#else
-#define SRCH_CLK(k) do { } while (0)
-#endif
+    // (the lap timer runs in thread 0 of workgroup 0 of the sequences on the first teams)
+    [[maybe_unused]] const bool srch_me = diag::phases && it > 0 && blockIdx.x < 8 && threadIdx.x == 0;
+    [[maybe_unused]] DiagLap<diag::phases, true, true> srch(srch_me);
     const int kx = voxel_index(s.x, c.vs, inv_vs), ky = voxel_index(s.y, c.vs, inv_vs), kz = voxel_index(s.z, c.vs, inv_vs);
     const unsigned long long key = pack_key(kx, ky, kz);
     int r[RE];
@@ -1919,7 +1896,7 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         for (int k = 0; k < RE / 4; ++k) { const int4 v = rp[k]; r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w; }
     }
     const bool same_voxel = it > 0 && c.pc_key[i] == key;
-    SRCH_CLK(0);  // row + key
+    if constexpr (diag::phases) { srch.lap(c, D_search_row_key); }  // row + key
     if (!same_voxel) {  // uniform over the group: probe this lane's neighbour voxels, rebuild the row
         int cs = 0;
         {   // this lane's RE probes with their first table reads in flight together; a collision walks on by itself
@@ -1967,7 +1944,7 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         for (int k = 0; k < RE / 4; ++k) wp[k] = make_int4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
         if (laneL == 0) { c.pc_key[i] = key; atomicAdd(xc + 1, 1u); }
     }
-    SRCH_CLK(1);  // rebuild (some group of the wavefront changed voxel)
+    if constexpr (diag::phases) { srch.lap(c, D_search_rebuild); }  // rebuild (some group of the wavefront changed voxel)
     const int lv_raw = __shfl(r[27 % RE], gb + 27 / RE);
     ctot = __shfl(r[28 % RE], gb + 28 / RE);
     const int lv = (lv_raw != 13) ? lv_raw : -1;
@@ -2031,7 +2008,7 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         if (laneL == 0) atomicAdd(xc + 2, pb_count(pbc) + pb_count(pbl));
         scan_voxelsL<PC, LP, 2>(c, pb2, vx2, s, laneL, bd, sd, border, bp, b2d, b2o, b2p);
     }
-    SRCH_CLK(2);  // box distances + first round
+    if constexpr (diag::phases) { srch.lap(c, D_search_first_round); }  // box distances + first round
     // the other voxels: dropped when their box lies farther than the best distance so far (exact, see nn_scan32)
     unsigned mine = 0u;
     double gdrop = 1.7976931348623157e308;  // smallest squared box distance among the voxels this lane dropped
@@ -2056,16 +2033,12 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
             npts += pb_count(pbS[j]);
         }
         if (vxS[0] == 0xFF) break;
-#ifdef GN_PHASE_CLOCKS
-        if (laneL == 0) atomicAdd((unsigned long long*)&c.wg_clk[41], 1ull);  // survivor rounds (wg_clk[40]: searches)
-#endif
+        if constexpr (diag::phases) { if (laneL == 0) diag_add<true>(c, D_survivor_rounds); }
         if (laneL == 0) atomicAdd(xc + 2, npts);
         scan_voxelsL<PC, LP, GN8_SURV>(c, pbS, vxS, s, laneL, bd, sd, border, bp, b2d, b2o, b2p);
     }
-#ifdef GN_PHASE_CLOCKS
-    if (laneL == 0) { atomicAdd((unsigned long long*)&c.wg_clk[40], 1ull); if (!same_voxel) atomicAdd((unsigned long long*)&c.wg_clk[42], 1ull); }
-#endif
-    SRCH_CLK(3);  // survivors
+    if constexpr (diag::phases) { if (laneL == 0) { diag_add<true>(c, D_searches); if (!same_voxel) diag_add<true>(c, D_rows_rebuilt); } }
+    if constexpr (diag::phases) { srch.lap(c, D_search_survivors); }  // survivors
     // ---- the group's GN8_KCAND nearest candidates in (distance, visiting order) order.  Every lane holds its own two nearest
     // (bd / b2d) and the smallest distance that lost to both (sd): K rounds of "every lane offers the nearest it has not
     // given yet, the group's minimum takes it"; what is left - the lanes' next offers, sd, the boxes of the dropped voxels -
@@ -2102,16 +2075,14 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
     if (laneL == 27 / RE && lv_new != lv_raw) c.pc_pb[32 * (size_t)i + 27] = lv_new;
     const double rest = taken == 0 ? bd : taken == 1 ? b2d : sd;
     const double D2 = group_minL<LP>(fmin(rest, gdrop));
-#ifdef GN_PHASE_CLOCKS
-    {   // what bounds everybody else: a candidate that was scanned or the box of a dropped voxel?
+    if constexpr (diag::phases) {  // what bounds everybody else: a candidate that was scanned or the box of a dropped voxel?
         const double Dc = group_minL<LP>(rest), Dg = group_minL<LP>(gdrop);
         if (laneL == 0 && found) {
-            atomicAdd((unsigned long long*)&c.wg_clk[44 + (Dc <= Dg ? 0 : 1)], 1ull);
+            diag_add<true>(c, Dc <= Dg ? D_bound_candidate : D_bound_box);
             const double q = sqrt(D2 / m);  // bound / distance of the winner: [1,1.2) [1.2,1.5) [1.5,2) [2,3) [3,..)
-            atomicAdd((unsigned long long*)&c.wg_clk[46 + (q < 1.2 ? 0 : q < 1.5 ? 1 : q < 2.0 ? 2 : q < 3.0 ? 3 : 4)], 1ull);
+            diag_add<true>(c, D_bound_ratio + (q < 1.2 ? 0 : q < 1.5 ? 1 : q < 2.0 ? 2 : q < 3.0 ? 3 : 4));
         }
     }
-#endif
     double sl2 = -1.0;
     if (found && D2 < 1.0e300) sl2 = sqrt(D2) * (1.0 - 1e-6) - 1e-9;  // (a little less is stored: the margin of the test)
     else if (found) sl2 = 1.0e300;  // nobody else in reach of this voxel
@@ -2123,11 +2094,8 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         arow[GN8_ANS_D + 1] = __longlong_as_double((long long)meta);
         arow[GN8_ANS_D + 2] = __longlong_as_double((long long)key);  // (= pc_key[i]: the voxel this search looked around)
     }
-    SRCH_CLK(4);  // reductions + answer row
-#ifdef GN_PHASE_CLOCKS
-    if (srch_me) atomicAdd((unsigned long long*)&c.wg_clk[66], 1ull);
-#endif
-#undef SRCH_CLK
+    if constexpr (diag::phases) { srch.lap(c, D_search_answer_row); }  // reductions + answer row
+    if constexpr (diag::phases) { if (srch_me) diag_add<true>(c, D_searches_timed); }
 }
 
 // packed upper triangle of JTJ (21) + JTr (6) from the 16 moments
@@ -2269,7 +2237,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
     const int nblk = (n + 63) >> 6;
     const int my_blocks = (nblk - wg + G - 1) / G;  // blocks wg, wg + G, ...
     int iters = 0;
-    [[maybe_unused]] long long ph_miss = 0, ph_a = 0, pb_t[5] = {0, 0, 0, 0, 0};
+    long long ph_miss = 0, ph_a = 0;    // (only with -DGN_PHASE_CLOCKS) workgroup 0's misses | its ticks of phase A until the compaction
     long long ph[5] = {0, 0, 0, 0, 0};  // (only with -DGN_PHASE_CLOCKS) point loop | wg reduce + publish | exchange | - | totals + solve
     // this lane's point of chunk qb: block qb + wavefront of this workgroup, i.e. global block (qb + wavefront) G + wg
     // tl = tid, made opaque at the top of every iteration: what the loop derives from the lane number (LDS and row addresses of the
@@ -2302,9 +2270,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
             int nempty = 0;  // ... 1 when it was settled as "nothing in reach" (executed-work counter)
             bool rebA = true;  // ... and whether its probe row has to be rebuilt (first iteration, or the point changed voxel)
             int liA = -1;      // ... and where its position lives: slot in posL, or -1 = src_cur
-#ifdef GN_PHASE_CLOCKS
-            const long long pa0 = GN_CLK();
-#endif
+            [[maybe_unused]] const long long pa0 = diag::phases ? GN_CLK() : 0ll;
             // ---- phase A, ONE LANE PER POINT (one pass, one memory round trip): apply the increment, look at the point's
             // answer row.  The last full search of the point (at s0, same voxel => same 27-voxel candidate set) found t and
             // every other candidate - scanned, or inside a dropped voxel's box - at >= D from s0.  After a move by
@@ -2378,9 +2344,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                 }
                 missA = miss;
             }
-#ifdef GN_PHASE_CLOCKS
-            const long long pa1 = GN_CLK();
-#endif
+            [[maybe_unused]] const long long pa1 = diag::phases ? GN_CLK() : 0ll;
             // The noted points join the queue: every wavefront has its own region and fills it in point order - points whose probe
             // row is still valid from the front, points that need the 27 hash probes first from the back (a wavefront of the
             // search serves 8 points and pays for whatever ONE of them needs: sorted by kind only the wavefronts at the seams
@@ -2401,14 +2365,10 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                 nq += __popcll(bf);   // (this wavefront's counts)
                 nqr += __popcll(br);
                 nemp += __popcll(__ballot(nempty != 0));
-#ifdef GN_PHASE_CLOCKS
-                ph_miss += __popcll(bm); ph_a += GN_CLK() - c0;
-#endif
+                if constexpr (diag::phases) { ph_miss += __popcll(bm); ph_a += GN_CLK() - c0; }
             }
-#ifdef GN_PHASE_CLOCKS
-            const long long pa2 = GN_CLK();
-            if (wg == 0 && tl == 0 && it > 0) { atomicAdd((unsigned long long*)&c.wg_clk[56], (unsigned long long)(pa1 - pa0)); atomicAdd((unsigned long long*)&c.wg_clk[57], (unsigned long long)(pa2 - pa1)); atomicAdd((unsigned long long*)&c.wg_clk[59], 1ull); }
-#endif
+            [[maybe_unused]] const long long pa2 = diag::phases ? GN_CLK() : 0ll;
+            if constexpr (diag::phases) { if (wg == 0 && tl == 0 && it > 0) { diag_add<true>(c, D_phase_a_eval, pa1 - pa0); diag_add<true>(c, D_phase_a_compact, pa2 - pa1); diag_add<true>(c, D_phase_a_chunks); } }
             if (qb + NW < my_blocks && ((qb / NW + 1) % GN8_QCHUNKS) != 0) continue;  // (a region holds GN8_QCHUNKS chunks whatever they bring)
             if ((tl & 63) == 0) { qcount[0][tl >> 6] = nq; qcount[1][tl >> 6] = nqr; }
             nq = 0; nqr = 0;
@@ -2423,9 +2383,7 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
             }
             const int kback0 = (nfront + 7) & ~7, nmiss = kback0 + nback;
             if (tl == 0) xcnt[0] += (unsigned)(nfront + nback);
-#ifdef GN_PHASE_CLOCKS
-            if (wg == 0 && tl == 0 && it < 24) st->dbg_sums[8 + it] += (double)(nfront + nback);  // misses by iteration index
-#endif
+            if constexpr (diag::phases) { if (wg == 0 && tl == 0 && it < 24) diag_add<true>(c, D_misses_at_iteration + it, nfront + nback); }
             // queue slot of search slot k
             auto qslot = [&](int k) -> int {
                 int j = k < nfront ? k : k - kback0, q = -1;
@@ -2443,7 +2401,6 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                 const int laneL = tl & (LPB - 1), gb = (tl & 63) & ~(LPB - 1);
                 for (int k = tl / LPB; __any(k < nmiss); k += NT / LPB) {
                   if (k < nfront || (k >= kback0 && k < nmiss)) {
-                    [[maybe_unused]] const long long b0 = GN_CLK();
                     const int2 qe = missq[qslot(k)];
                     const int i = qe.x;
                     const V3 s = qe.y >= 0 ? v3(posL[0][qe.y], posL[1][qe.y], posL[2][qe.y])  // (the point's position now: from the LDS copy,
@@ -2452,40 +2409,30 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                     double m;
                     bool found;
                     int ctot;
-#ifdef GN_PHASE_CLOCKS
-                    // why did the answer row not settle this point?  (wg 0, iterations > 0): voxel changed | same neighbour again | another one
-                    double old_t[3] = {0, 0, 0}, old_sl = -1.0;
-                    bool old_same_key = false;
-                    if (wg == 0 && it > 0 && laneL == 0) {
+                    // (diagnostic) why did the answer row not settle this point?  (wg 0, iterations > 0): voxel changed | same neighbour again | another one
+                    [[maybe_unused]] double old_t[3] = {0, 0, 0}, old_sl = -1.0;
+                    [[maybe_unused]] bool old_same_key = false;
+                    if constexpr (diag::phases) if (wg == 0 && it > 0 && laneL == 0) {
                         const int kx0 = voxel_index(s.x, c.vs, inv_vs), ky0 = voxel_index(s.y, c.vs, inv_vs), kz0 = voxel_index(s.z, c.vs, inv_vs);
                         old_same_key = c.pc_key[i] == pack_key(kx0, ky0, kz0);
                         old_t[0] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 3]; old_t[1] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 4]; old_t[2] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 5];
                         old_sl = c.pc_ans[GN8_ANS_ROW * (size_t)i + GN8_ANS_D];
                     }
-#endif
                     gn8_search<PC, LPB>(c, i, it, s, inv_vs, laneL, gb, t, m, found, ctot, xcnt);
-#ifdef GN_PHASE_CLOCKS
-                    if (wg == 0 && it > 0 && laneL == 0) {
-                        const int cat = !old_same_key ? 5 : (old_sl < 0.0) ? 6 : (found && t.x == old_t[0] && t.y == old_t[1] && t.z == old_t[2]) ? 7 : 4;
-                        atomicAdd(&st->dbg_sums[cat], 1.0);  // 5 voxel changed | 6 no answer stored | 7 same neighbour | 4 another neighbour
-                    }
-#endif
+                    if constexpr (diag::phases) if (wg == 0 && it > 0 && laneL == 0)
+                        diag_add<true>(c, !old_same_key ? D_miss_voxel_changed : (old_sl < 0.0) ? D_miss_no_answer
+                                          : (found && t.x == old_t[0] && t.y == old_t[1] && t.z == old_t[2]) ? D_miss_same_neighbour : D_miss_other_neighbour);
                     if (laneL == 0) {
                         M[17] += (double)ctot;
                         if (found && m < gate2) gn8_accumulate(M, s, t, kern, k2);
                     }
-#ifdef GN_PHASE_CLOCKS
-                    { pb_t[0] += GN_CLK() - b0; pb_t[4] += 1; }
-#endif
                   }
                 }
             };
             if (GN8_IT0_LP != GN8_LPB && it == 0) phaseB(std::integral_constant<int, GN8_IT0_LP>{});  // (every point searches: more points per pass)
             else phaseB(std::integral_constant<int, GN8_LPB>{});
             __syncthreads();  // the queue is reused by the next chunk
-#ifdef GN_PHASE_CLOCKS
-            if (wg == 0 && tl == 0 && it > 0) { atomicAdd((unsigned long long*)&c.wg_clk[58], (unsigned long long)(GN_CLK() - pa2)); atomicAdd((unsigned long long*)&c.wg_clk[60], (unsigned long long)((nmiss + NT / GN8_LPB - 1) / (NT / GN8_LPB))); }
-#endif
+            if constexpr (diag::phases) { if (wg == 0 && tl == 0 && it > 0) { diag_add<true>(c, D_search_pass_ticks, GN_CLK() - pa2); diag_add<true>(c, D_search_passes, (nmiss + NT / GN8_LPB - 1) / (NT / GN8_LPB)); } }
             {   // (queue flushed before the last chunk: its loads are requested again rather than carried across the search;
                 // after the last chunk nothing is loaded - chunk_point says so - and the stale values are dead for the compiler too)
                 pre = preload_chunk(qb + NW, it == 0);
@@ -2590,21 +2537,14 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-#ifdef GN_PHASE_CLOCKS
-            const long long s1 = GN_CLK();
-#endif
+            [[maybe_unused]] const long long s1 = diag::phases ? GN_CLK() : 0ll;
             [[maybe_unused]] const long long s2 = gn_solve_publish(tot, tl, conv2, ok, Esh2[it & 1], &flag_done2[it & 1]);
-#ifdef GN_PHASE_CLOCKS
-            if (tl == 0 && wg == 0) { const long long s3 = GN_CLK(); atomicAdd((unsigned long long*)&c.wg_clk[67], (unsigned long long)(s1 - c3)); atomicAdd((unsigned long long*)&c.wg_clk[68], (unsigned long long)(s2 - s1));
-                                       atomicAdd((unsigned long long*)&c.wg_clk[69], (unsigned long long)(s3 - s2)); atomicAdd((unsigned long long*)&c.wg_clk[70], 1ull); }
-#endif
+            if constexpr (diag::phases) { if (tl == 0 && wg == 0) { diag_add<true>(c, D_tail_sums, s1 - c3); diag_add<true>(c, D_tail_solve, s2 - s1); diag_add<true>(c, D_tail_exp_flags, GN_CLK() - s2); diag_add<true>(c, D_tails); } }
         }
         __syncthreads();
         const long long c5 = GN_CLK();
         ph[0] += c1 - c0; ph[1] += c2 - c1; ph[2] += c3 - c2; ph[4] += c5 - c3;
-#if defined(GN_PHASE_CLOCKS) || defined(GN_IT0_CLOCK)
-        if (tl == 0 && wg == 0) atomicAdd((unsigned long long*)&c.wg_clk[52 + (it == 0 ? 0 : 1)], (unsigned long long)(c1 - c0));  // point loop of the first iteration / of the others
-#endif
+        if (tl == 0 && wg == 0) diag_add<diag::cycles>(c, it == 0 ? D_point_loop_first : D_point_loop_others, c1 - c0);
         if (tl == NT - 1) cand_total_sh += (long long)tot[GN_TOT_CAND];
         iters = it + 1;
         if (flag_done2[it & 1]) break;
@@ -2622,9 +2562,6 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
         for (int k = 0; k < 5; ++k) st->gn_phase_clk[k] += ph[k];
         st->gn_phase_clk[5] += iters;
         st->gn_phase_clk[6] += ph_miss; st->gn_phase_clk[7] += ph_a;
-#ifdef GN_PHASE_CLOCKS
-        for (int k = 0; k < 4; ++k) st->dbg_sums[k] += (double)pb_t[k];
-#endif
         gn_post(c, st, false, mode == 0);
     }
 }
@@ -2750,7 +2687,7 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
-        if (keyed[u] && slot[u] < 0) { atomicOr(&st->err_flags, ERR_TABLE); MAP_DIAG_AT(st, 0, idx[u], s0[u]); }
+        if (keyed[u] && slot[u] < 0) { atomicOr(&st->err_flags, ERR_TABLE); diag_map_site(c, 0, idx[u], s0[u]); }
     // (only now - a point of a full voxel HAS found its entry, it is no table error -) the points of full voxels give up their slot
     {
         int nd = 0;
@@ -2859,7 +2796,7 @@ __device__ __forceinline__ void d_map_insert_a(const Ctx& c, const double* pts_i
                 if (hw_s > 0) atomicMax(&st->pool_hw_s, hw_s);
                 if (hw_f > 0) atomicMax(&st->pool_hw, hw_f);
                 const unsigned used = atomicAdd(&st->tab_used, (unsigned)tot) + (unsigned)tot;
-                if (used > (c.tmask + 1u) / 4u * 3u) { atomicOr(&st->err_flags, ERR_TABLE); MAP_DIAG_AT(st, 1, used, c.tmask); }
+                if (used > (c.tmask + 1u) / 4u * 3u) { atomicOr(&st->err_flags, ERR_TABLE); diag_map_site(c, 1, used, c.tmask); }
             }
         }
     }
@@ -2911,7 +2848,7 @@ __device__ __forceinline__ void d_map_insert_b(const Ctx& c, const int* n_ptr, i
         if (idx[u] < n && slot[u] >= 0 && pb[u] >= 0) { w[u][0] = c.fdw[3 * i]; w[u][1] = c.fdw[3 * i + 1]; w[u][2] = c.fdw[3 * i + 2]; }
     }
     for (int steps = 0;; ++steps) {  // the U list walks step together: their reads of nxt[] are in flight at the same time
-        if (steps > (LIST ? c.n_max : n)) { atomicOr(&c.st->err_flags, ERR_TABLE); MAP_DIAG_AT(c.st, 2, idx[0], n); break; }  // (a list longer than the batch: corrupted links must not hang the launch)
+        if (steps > (LIST ? c.n_max : n)) { atomicOr(&c.st->err_flags, ERR_TABLE); diag_map_site(c, 2, idx[0], n); break; }  // (a list longer than the batch: corrupted links must not hang the launch)
         bool any = false;
 #pragma unroll
         for (int u = 0; u < U; ++u) any = any || j[u] >= 0;
@@ -3129,7 +3066,7 @@ __device__ __forceinline__ void d_map_rebuild(const Ctx& c, const Slice sl) {
         s = (s + 1) & c.tmask;
     }
     atomicOr(&c.st->err_flags, ERR_TABLE);
-    MAP_DIAG_AT(c.st, 3, b, s);
+    diag_map_site(c, 3, b, s);
 }
 
 // export of the map points (KissICPWrapper.local_map_points)

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <memory>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -232,6 +233,7 @@ static int icp_reset_device(ptl_icp* h) {
     HIPCHK(hipMemsetAsync(c.bcnt2, 0, m.bytes_of(c.bcnt2), h->stream));
     HIPCHK(hipMemsetAsync(c.gn_rows_ll, 0, m.bytes_of(c.gn_rows_ll), h->stream));  // the launch epoch restarts with the state
     HIPCHK(hipMemsetAsync(c.gn_xsum_ll, 0, m.bytes_of(c.gn_xsum_ll), h->stream));
+    HIPCHK(hipMemsetAsync(c.wg_clk + 2 * c.G, 0, DIAG_SLOTS * sizeof *c.wg_clk, h->stream));  // (the per-workgroup clocks in front count since creation)
     k_fill_free_stack<<<(c.pool_cap - c.n_small + 255) / 256, 256, 0, h->stream>>>(c.free_stack, c.pool_cap - c.n_small, c.n_small);
     if (c.n_small > 0) k_fill_free_stack<<<(c.n_small + 255) / 256, 256, 0, h->stream>>>(c.free_stack_s, c.n_small, 0);
     k_state_init<<<1, 64, 0, h->stream>>>(c.st, c.pool_cap - c.n_small, c.n_small);
@@ -307,7 +309,7 @@ static void icp_alloc(DevOwner& m, ptl_icp* h, int64_t traj_rows) {
     m.add_pinned(&h->n_src_hint, 1);
     m.add(&c.gn_rows_ll, (size_t)2 * c.G * 64);
     m.add(&c.gn_xsum_ll, (size_t)2 * 8 * 8 * 64);
-    m.add(&c.wg_clk, (size_t)c.G * 2);
+    m.add(&c.wg_clk, (size_t)c.G * 2 + DIAG_SLOTS);  // the per-workgroup clocks, then the named slots of the diagnostic builds (diag.h)
     m.add(&c.st, 1);
     h->traj_cap = traj_rows;
     c.traj_cap = (int)traj_rows;
@@ -685,7 +687,7 @@ extern "C" int ptl_icp_linear_system(ptl_icp* h, const double* src_world, int64_
     k_set_gn<<<1, 64, 0, h->stream>>>(c, (int)n, max_dist, kernel, nullptr);
     pick_p(c.P, [&](auto pc) { k_gn_loop<pc(), false><<<c.G, h->cfg.gn_threads, 0, h->stream>>>(c, 1); });
     double out[32];
-    HIPCHK(hipMemcpyAsync(out, (char*)c.st + offsetof(DevState, dbg_sums), sizeof out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out, (char*)c.st + offsetof(DevState, lin_sums), sizeof out, hipMemcpyDeviceToHost, h->stream));
     int rc = icp_check_flags(h);
     if (rc) return rc;
     memcpy(sums, out, 27 * 8);
@@ -785,11 +787,30 @@ extern "C" int ptl_icp_gn_wg_clocks(ptl_icp* h, int64_t* out, int32_t max_wgs) {
     return PTL_OK;
 }
 
-// diagnostic: the 32 debug sums of the handle's device state (phase-clock builds park sub-step clocks there)
+// diagnostic: what the handle's last ptl_icp_linear_system left on the device: the 27 sums, the pair count, the candidate count (nothing else
+// is kept there: the diagnostic builds' values are read with ptl_icp_diag)
 extern "C" int ptl_icp_debug_sums(ptl_icp* h, double out[32]) {
     if (!h || !out) return set_err(PTL_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipMemcpyAsync(out, (char*)h->c.st + offsetof(DevState, dbg_sums), 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out, (char*)h->c.st + offsetof(DevState, lin_sums), 256, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PTL_OK;
+}
+// diagnostic: the named slots of diag.h (all 0 in the product build), cumulative since the handle's cold start
+extern "C" int ptl_diag_slots(void) { return DIAG_SLOTS; }
+extern "C" const char* ptl_diag_slot_name(int slot) {
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v;
+        for (const DiagSlotName& e : DIAG_SLOT_NAMES)
+            for (int k = 0; k < e.words; ++k) v.push_back(e.words == 1 ? std::string(e.base) : std::string(e.base) + "_" + std::to_string(k));
+        return v;
+    }();
+    return slot >= 0 && slot < (int)names.size() ? names[slot].c_str() : nullptr;
+}
+extern "C" int ptl_icp_diag(ptl_icp* h, int64_t* out, int32_t max_slots) {
+    if (!h || !out || max_slots < DIAG_SLOTS) return set_err(PTL_ERR_ARG, "bad argument (ptl_diag_slots() words are written)");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    HIPCHK(hipMemcpyAsync(out, h->c.wg_clk + 2 * h->c.G, DIAG_SLOTS * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PTL_OK;
 }
@@ -2413,7 +2434,8 @@ extern "C" int ptl_batch_sched_counters(ptl_batch* b, int32_t s, uint64_t out[4]
 }
 // compile-time constants of this build that callers' byte models depend on (bench.py EXEC_COST):
 //   [0] GN8_KCAND  [1] doubles per answer row  [2] GN8_LDS_PTS  [3] SEQ_U  [4] SEQ_U2  [5] GN8_MAX_THREADS  [6] GN8_LPB  [7] GN8_SPEC
-//   [8] GN8_SURV  [9] GN8_PREFETCH  [10] 1000 x GN8_KEEP  [11] bytes per map table entry  [12] bytes per VDS entry  [13] diagnostics compiled in
+//   [8] GN8_SURV  [9] GN8_PREFETCH  [10] 1000 x GN8_KEEP  [11] bytes per map table entry  [12] bytes per VDS entry
+//   [13] diagnostic flavours compiled in (diag.h): 1 PHASES | 2 IT0 | 4 STAGES | 8 MAP_DIAG, 0 = the product build
 #ifndef PTL_CODE_ID
 #define PTL_CODE_ID "unknown"
 #endif
@@ -2423,10 +2445,7 @@ extern "C" int ptl_build_info(int32_t out[16]) {
     for (int i = 0; i < 16; ++i) out[i] = 0;
     out[0] = GN8_KCAND; out[1] = GN8_ANS_ROW; out[2] = GN8_LDS_PTS; out[3] = SEQ_U; out[4] = SEQ_U2; out[5] = GN8_MAX_THREADS;
     out[6] = GN8_LPB; out[7] = GN8_SPEC; out[8] = GN8_SURV; out[9] = GN8_PREFETCH; out[10] = (int32_t)(1000.0 * GN8_KEEP + 0.5);
-    out[11] = (int32_t)sizeof(TabEnt); out[12] = (int32_t)sizeof(VdsEnt); out[14] = 0;
-#if defined(GN_PHASE_CLOCKS) || defined(SEQ_STAGE_CLOCKS) || defined(GN_IT0_CLOCK)
-    out[13] = 1;
-#endif
+    out[11] = (int32_t)sizeof(TabEnt); out[12] = (int32_t)sizeof(VdsEnt); out[13] = diag::flavours; out[14] = 0;
     return PTL_OK;
 }
 extern "C" int ptl_batch_run(ptl_batch* b, int64_t n) {

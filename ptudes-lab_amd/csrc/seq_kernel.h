@@ -96,15 +96,8 @@ __device__ __forceinline__ unsigned xcc_id() {
 #ifndef SEQ_U2
 #define SEQ_U2 16  /* ... in K3 / K3b / K4 (a few registers per point: an index, a slot, two flags); they share their block size through bcnt1 / bcnt2 */
 #endif
-// make STAGES=1: workgroup 0 of every sequence adds the wall-clock ticks of every stage and of every barrier wait to
-// st->dbg_sums[0..19] (tools/free_vs_lockstep.py prints them)
-#ifdef SEQ_STAGE_CLOCKS
-#define SQ_CLK_DECL long long sq_t = (long long)wall_clock64(); const bool sq_me = wg == 0 && threadIdx.x == 0
-#define SQ_CLK(i) do { const long long n_ = (long long)wall_clock64(); if (sq_me) st->dbg_sums[i] += (double)(n_ - sq_t); sq_t = n_; } while (0)
-#else
-#define SQ_CLK_DECL do { } while (0)
-#define SQ_CLK(i) do { } while (0)
-#endif
+// make STAGES=1: workgroup 0 of every sequence adds the wall-clock ticks of every stage and of every barrier wait to the sq_ slots of
+// diag.h (tools/stage_clocks.py and tools/free_vs_lockstep.py print them)
 // K0 of a scan whose prologue the filter workgroup has not run (the first scan after a cold start, or no filter): a call of its own, so
 // that the prologue's body (and the IMU deskew's call inside it) stays out of sq_prepare's registers
 __device__ __noinline__ void sq_prologue(const SeqCtx* a, int s, int k) { d_scan_prologue(load_seq_ctx(a, s, k), true); }
@@ -117,11 +110,11 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
     Slice sl;
     sl.nb = nbs; sl.clk = wg == 0 ? 1 : 0;
     const TeamEnv te = {word, &st->gn_abort, st, local};
-    SQ_CLK_DECL;
+    DiagLap<diag::stages, false, false> sq(wg == 0 && threadIdx.x == 0);
     if (wg == 0 && st->pro_next != k + 1) sq_prologue(a, s, k);  // (with a filter it has usually been run already: sq_filter)
-    SQ_CLK(0);
+    sq.lap(c, D_sq_prologue);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
-    SQ_CLK(1);
+    sq.lap(c, D_sq_wait_prologue);
     int wave_valid = 0;  // this wavefront's valid points over all its blocks (integer sum: any grouping gives the same total)
     if (c.in_f32 && !c.in_range) {  // (uniform) the next pass's raw points travel while this pass waits for its atomics
         RawF32<SEQ_U> raw;
@@ -138,9 +131,9 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
         for (sl.b = wg; sl.b < nbs; sl.b += nw) d_deskew_vds1<SEQ_U>(c, sl, nullptr, &wave_valid);
     }
     if ((threadIdx.x & 63) == 0 && wave_valid) atomicAdd(&st->n_valid, wave_valid);
-    SQ_CLK(2);
+    sq.lap(c, D_sq_deskew_vds1);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
-    SQ_CLK(3);
+    sq.lap(c, D_sq_wait_deskew_vds1);
     sl.nb = nbs2;
     const unsigned tag = lookback_tag(k);
     {   // K3: pass-1 winners -> frame_downsample, one pass with look-back (the next pass's first loads a pass ahead, as in K1)
@@ -155,18 +148,18 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
             d_compact_fd<SEQ_U2, true>(c, sl, &cur, tag);
         }
     }
-    SQ_CLK(4);
+    sq.lap(c, D_sq_compact_fd);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
-    SQ_CLK(5);
+    sq.lap(c, D_sq_wait_compact_fd);
     // K3b / K4 walk the COMPACT frame_downsample (N_d entries, a quarter of the raw indices)
     const int nbf = (st->n_down + BS2 - 1) / BS2;
     sl.nb = nbf;
     for (sl.b = wg; sl.b < nbf; sl.b += nw) d_vds2_fd<SEQ_U2>(c, sl);
-    SQ_CLK(6);
+    sq.lap(c, D_sq_vds2);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
-    SQ_CLK(7);
+    sq.lap(c, D_sq_wait_vds2);
     for (sl.b = wg; sl.b < nbf; sl.b += nw) d_compact_src<SEQ_U2, true>(c, sl, tag);
-    SQ_CLK(8);
+    sq.lap(c, D_sq_compact_src);
     return target;
 }
 // K7-K11 of scan k by all `nw` workgroups of the team.  The blocks of a phase are handed out through a counter (`ctr`, five
@@ -192,26 +185,25 @@ __device__ __noinline__ unsigned sq_map_update(const SeqCtx* a, int s, int k, in
     Slice sl;
     sl.nb = nbd; sl.clk = 0;
     const TeamEnv te = {word, &st->gn_abort, st, local};
-    SQ_CLK_DECL;
+    DiagLap<diag::stages, false, false> sq(wg == 0 && threadIdx.x == 0);
     for (sl.b = sq_grab(ctr); sl.b < nbd; sl.b = sq_grab(ctr)) d_map_insert_a<UM, true>(c, c.fd, &st->n_down_ins, 0, 1, sl);
-    SQ_CLK(10);
+    sq.lap(c, D_sq_insert_a);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
-    SQ_CLK(11);
+    sq.lap(c, D_sq_wait_insert_a);
     // phase b over the points insert a left with a slot only (in a map that has filled up a tenth of the batch): one pass or two
     const int nbl = (st->ulist_n + BU - 1) / BU;
     sl.nb = nbl;
     for (sl.b = sq_grab(ctr + 1); sl.b < nbl; sl.b = sq_grab(ctr + 1)) d_map_insert_b<UM, true, true>(c, &st->ulist_n, 0, sl);
-    SQ_CLK(12);
+    sq.lap(c, D_sq_insert_b);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
     if (wg == 0 && threadIdx.x == 0) st->ulist_n = 0;  // (everybody has read it: the next scan's insert a starts from an empty list)
-    SQ_CLK(13);
-    SQ_CLK(14);  // (phase c is part of the prune pass here: d_map_insert_b / d_map_prune, FUSE)
-    SQ_CLK(15);
+    sq.lap(c, D_sq_wait_insert_b);
+    // (phase c is part of the prune pass here: d_map_insert_b / d_map_prune, FUSE)
     const int nvb = blk_virtual_count(c, st);  // small blocks below their high-water mark, then the full ones below theirs
     const int nbpu = (nvb + BU - 1) / BU;
     sl.nb = nbpu;
     for (sl.b = sq_grab(ctr + 3); sl.b < nbpu; sl.b = sq_grab(ctr + 3)) d_map_prune<UM, true>(c, nullptr, 1, sl);
-    SQ_CLK(16);
+    sq.lap(c, D_sq_prune);
     if (c.n_small > 0) {  // (uniform) two block classes: the voxels the batch took past a small block's capacity move to full blocks
         if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
         const int nm = st->mig_n < c.n_small ? st->mig_n : c.n_small, nbm = (nm + BS - 1) / BS;

@@ -24,45 +24,41 @@ print("S",S,"grid iters",it,"ticks/iter: nn %.0f wgred %.0f barrier %.0f gridred
 
 print("wg0 of seq 0: misses/iter %.1f, phase A until compaction %.0f ticks/iter" % (o[6]/it, o[7]/it))
 icp = C.c_void_p()
-G = 32
+G = b.team_geometry()[0]
 try:
     # per-workgroup point-loop ticks and misses of sequence 0 (needs ptl_batch_icp)
     L.check(L.lib().ptl_batch_icp(b._h, 0, C.byref(icp)))
     wc = (C.c_int64 * 512)(); L.check(L.lib().ptl_icp_gn_wg_clocks(icp, wc, 256))
     w = np.array(list(wc), dtype=float)
+    D = {k: float(v) for k, v in b.diag(0).items()}  # the named slots of a PHASES=1 / IT0=1 build (csrc/diag.h)
     print("point loop per workgroup, ticks/iter:", np.round(w[:G] / it).astype(int).tolist())
     print("misses per workgroup per iter:", np.round(w[G:2 * G] / it, 1).tolist())
-    if w[40] > 0:
-        print("searches (all workgroups of sequence 0): %.0f per scan, survivor rounds per search %.2f, row rebuilt (voxel changed / first iteration) %.1f %%" % (w[40] / n, w[41] / w[40], 100 * w[42] / w[40]))
-    if w[52] > 0:
-        print("point loop of workgroup 0: first iteration %.0f ticks per scan, the others %.0f per iteration" % (w[52] / nscan_all, w[53] / max(it - nscan_all, 1)))
-    if w[59] > 0:
+    if D["searches"] > 0:
+        print("searches (all workgroups of sequence 0): %.0f per scan, survivor rounds per search %.2f, row rebuilt (voxel changed / first iteration) %.1f %%" % (D["searches"] / n, D["survivor_rounds"] / D["searches"], 100 * D["rows_rebuilt"] / D["searches"]))
+    if D["point_loop_first"] > 0:
+        print("point loop of workgroup 0: first iteration %.0f ticks per scan, the others %.0f per iteration" % (D["point_loop_first"] / nscan_all, D["point_loop_others"] / max(it - nscan_all, 1)))
+    if D["phase_a_chunks"] > 0:
         print("workgroup 0 of sequence 0, iterations > 0: per chunk of phase A: wait for the loads + evaluation %.0f ticks, compaction %.0f; chunks per iteration %.1f;  per search pass %.0f ticks (%.1f passes per iteration)"
-              % (w[56] / w[59], w[57] / w[59], w[59] / max(it - nscan_all, 1), w[58] / max(w[60], 1), w[60] / max(it - nscan_all, 1)))
-    if w[70] > 0:
-        print("serial tail of an iteration (workgroup 0 of sequence 0), ticks: sums from the moments %.0f | 6x6 solve %.0f | Exp + flags %.0f" % tuple(w[67:70] / w[70]))
-    if w[66] > 0:
+              % (D["phase_a_eval"] / D["phase_a_chunks"], D["phase_a_compact"] / D["phase_a_chunks"], D["phase_a_chunks"] / max(it - nscan_all, 1),
+                 D["search_pass_ticks"] / max(D["search_passes"], 1), D["search_passes"] / max(it - nscan_all, 1)))
+    if D["tails"] > 0:
+        print("serial tail of an iteration (workgroup 0 of sequence 0), ticks: sums from the moments %.0f | 6x6 solve %.0f | Exp + flags %.0f" % tuple(D[k] / D["tails"] for k in ("tail_sums", "tail_solve", "tail_exp_flags")))
+    if D["searches_timed"] > 0:
         print("one search (thread 0 of the first teams' workgroup 0, iterations > 0, every step waited out), ticks: row + key %.0f | rebuild %.0f | boxes + first round %.0f | survivors %.0f | reductions + answer row %.0f   (%d searches)"
-              % tuple(list(w[61:66] / w[66]) + [int(w[66])]))
-    if w[44] + w[45] > 0:
+              % tuple([D["search_" + k] / D["searches_timed"] for k in ("row_key", "rebuild", "first_round", "survivors", "answer_row")] + [int(D["searches_timed"])]))
+    if D["bound_candidate"] + D["bound_box"] > 0:
+        bound, ratio = D["bound_candidate"] + D["bound_box"], np.array([D["bound_ratio_%d" % i] for i in range(5)])
         print("bound of the others after a search: third-nearest candidate %.1f %%, box of a dropped voxel %.1f %%;  bound / winner's distance in [1,1.2) [1.2,1.5) [1.5,2) [2,3) [3,..): %s %%"
-              % (100 * w[44] / (w[44] + w[45]), 100 * w[45] / (w[44] + w[45]), np.round(100 * w[46:51] / max(w[46:51].sum(), 1), 1).tolist()))
+              % (100 * D["bound_candidate"] / bound, 100 * D["bound_box"] / bound, np.round(100 * ratio / max(ratio.sum(), 1), 1).tolist()))
 except Exception as e:
     print("no per-wg clocks:", e)
 
 try:
-    import ctypes
-    class _DS(ctypes.Structure): pass
-    # dbg_sums of sequence 0's DevState: phase-B sub-steps of workgroup 0 / group 0 (ticks summed over its passes)
-    st = np.zeros(2048, dtype=np.uint8)
-    from ptudes_lab_amd import _lib
-    print("phase B sub-steps: see ptl_icp_debug_sums")
-    ds = (C.c_double * 32)(); L.check(L.lib().ptl_icp_debug_sums(icp, ds))
-    d = np.array(list(ds)); n = max(d[4], 1)
     nscan = max(sum(1 for st in b.results(0)["stats"] if st["iterations"] > 0), 1)
-    print("misses of workgroup 0 by iteration index (mean per scan):", np.round(d[8:32] / nscan, 1).tolist())
-    tot = max(d[4] + d[5] + d[6] + d[7], 1)
+    print("misses of workgroup 0 by iteration index (mean per scan):", np.round(np.array([D["misses_at_iteration_%d" % i] for i in range(24)]) / nscan, 1).tolist())
+    cat = {k: D["miss_" + k] for k in ("voxel_changed", "no_answer", "same_neighbour", "other_neighbour")}
+    tot = max(sum(cat.values()), 1)
     print("searches of workgroup 0 after iteration 0: %.0f per scan; voxel changed %.1f %%, no answer stored %.1f %%, SAME neighbour again %.1f %%, another neighbour %.1f %%"
-          % (tot / nscan, 100 * d[5] / tot, 100 * d[6] / tot, 100 * d[7] / tot, 100 * d[4] / tot))
+          % (tot / nscan, 100 * cat["voxel_changed"] / tot, 100 * cat["no_answer"] / tot, 100 * cat["same_neighbour"] / tot, 100 * cat["other_neighbour"] / tot))
 except Exception as e:
     print("no sub-steps:", e)

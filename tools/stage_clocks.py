@@ -2,7 +2,6 @@
 
     PTL_LIB_PATH=.../libptudes_mi_stages.so python tools/stage_clocks.py S TEAM_WGS [N_SCANS]
 """
-import ctypes as C
 import os
 import sys
 import time
@@ -40,14 +39,15 @@ print("S %d, teams of %d x %d: %.0f scans/s" % ((S,) + b.team_geometry() + ((n -
 clk = np.array([b.seq_clocks(s) for s in range(S)])
 print("per scan, us (mean | min | max over sequences):  K0-K4 %s  wait %s  GN %s  wait %s  map %s  filter %s" % tuple(
     "%.0f|%.0f|%.0f" % (clk[:, i].mean(), clk[:, i].min(), clk[:, i].max()) for i in range(6)))
-icp = C.c_void_p()
-L.check(L.lib().ptl_batch_icp(b._h, 0, C.byref(icp)))
-ds = (C.c_double * 32)()
-L.check(L.lib().ptl_icp_debug_sums(icp, ds))
-d = np.array(list(ds)) / n / 100.0
-if d[:20].sum() > 0:
+# the named slots of a STAGES=1 build (csrc/diag.h), in the order of the printed lines
+SQ = ["sq_prologue", "sq_wait_prologue", "sq_deskew_vds1", "sq_wait_deskew_vds1", "sq_compact_fd", "sq_wait_compact_fd", "sq_vds2", "sq_wait_vds2", "sq_compact_src", None,
+      "sq_insert_a", "sq_wait_insert_a", "sq_insert_b", "sq_wait_insert_b", None, None, "sq_prune"]  # (None: printed for the line's sake, timed by nobody)
+K1 = ["k1_entry", "k1_load_deskew_store", "k1_claim", "k1_bid", "k1_slot1", "k1_count"]
+D = b.diag(0)
+d = np.array([D[k] if k else 0 for k in SQ + K1]) / n / 100.0
+if d.sum() > 0:
     names = ["prologue", "w", "deskew+vds1", "w", "compact_fd (look-back)", "w", "vds2 on frame_down", "w", "compact_src (look-back)", "-", "insert_a", "w", "insert_b", "w", "insert_c", "w", "prune"]
     print("stages of sequence 0 (workgroup 0), us/scan:", "  ".join("%s %.0f" % (nm, v) for nm, v in zip(names, d[:17])))
-    print("inside K1 (thread 0 of workgroup 0, its own waits): - %.0f | load + deskew + store %.0f | claim %.0f | bid %.0f | slot1 %.0f | count %.0f" % tuple(d[20:26]))
+    print("inside K1 (thread 0 of workgroup 0, its own waits): - %.0f | load + deskew + store %.0f | claim %.0f | bid %.0f | slot1 %.0f | count %.0f" % tuple(d[17:23]))
 else:
     print("(no stage clocks: not a STAGES=1 build)")

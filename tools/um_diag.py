@@ -1,6 +1,6 @@
 """Diagnostic for the free-running map update at another points-per-thread value (make EXTRA="-DSEQ_UM=4 -DMAP_DIAG"): runs a batch
 scan by scan (one launch per scan), and after every scan records per sequence the error flags, the ERR_TABLE site counters of a
-MAP_DIAG build (dbg_sums[24..31]), the map's size and a digest of its sorted points.  Two runs (PTL_LIB_PATH = the variant / the
+MAP_DIAG build (the map_ slots of csrc/diag.h), the map's size and a digest of its sorted points.  Two runs (PTL_LIB_PATH = the variant / the
 default build) are compared by `um_diag.py cmp A.json B.json`: first scan and sequence where the maps differ.
 
     PTL_LIB_PATH=... python tools/um_diag.py run OUT.json S N [TEAM_WGS]
@@ -14,6 +14,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+MAP_SLOTS = ["map_site_0", "map_site_1", "map_site_2", "map_site_3", "map_first_site", "map_first_a", "map_first_b"]
 
 
 def run(out, S, n, team):
@@ -44,8 +47,7 @@ def run(out, S, n, team):
             err = str(e)
         row = dict(k=k, err=err, seqs=[])
         for s in range(S):
-            dbg = (C.c_double * 32)()
-            L.lib().ptl_icp_debug_sums(hs[s], dbg)
+            D = core._diag(hs[s])
             nv, npnt = C.c_int64(), C.c_int64()
             L.lib().ptl_icp_map_size(hs[s], C.byref(nv), C.byref(npnt))
             pts = np.empty((max(npnt.value, 1) + 64, 3))
@@ -54,7 +56,7 @@ def run(out, S, n, team):
             p = pts[:w.value]
             p = p[np.lexsort((p[:, 2], p[:, 1], p[:, 0]))]
             row["seqs"].append(dict(voxels=nv.value, points=npnt.value, exported=w.value, digest=hashlib.sha1(p.tobytes()).hexdigest()[:16],
-                                    diag=[float(dbg[i]) for i in range(24, 32)]))
+                                    diag=[float(D[k]) for k in MAP_SLOTS]))
         rec["scans"].append(row)
         if err:
             print("scan", k, "error:", err)
