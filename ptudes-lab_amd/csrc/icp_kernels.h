@@ -4,9 +4,12 @@
 //   K0 scan_prologue   deskew twist, adaptive threshold, initial guess          (kiss.py:90,99,102-105)
 //   K1 k_deskew_vds1   DeSkewScan + Preprocess + VoxelDownsample(0.5 vs) claim  (kiss.py:90,93,96)
 //   K2 k_count_w1      winners of pass 1 counted per block (only the drivers with one launch per stage; the free-running kernel looks back in K3)
-//   K3 k_compact_fd    ordered compaction -> frame_downsample
+//   K3 k_compact_fd    ordered compaction -> frame_downsample, pass-1 slots released
 //   K3b k_vds2_fd      frame_downsample (compact) claims VoxelDownsample(1.5 vs)   [+ k_count_w2: its winners per block, as K2]
 //   K4 k_compact_src   ordered compaction -> source, pass-2 slots released
+//      The two down-sampling passes are ONE definition: a VdsPass names what a pass reads and writes (vds_pass1 / vds_pass2
+//      are the only places that tell the passes apart), vds_claim_run_heads is the claim of K1 and K3b, d_count_winners is K2 and K3b's
+//      count, d_compact_winners is K3 and K4.  The kernels above keep their names: they are those bodies at a pass.
 //   K5 k_gn_loop       persistent Gauss-Newton loop: 27-voxel NN + robust 6x6 system + solve (kiss.py:108-114)
 //      (tail of K5)    new pose, innovation log, threshold model deviation      (kiss.py:116-130)
 //   K7-9 k_map_*       VoxelHashMap::AddPoints, order-preserving, cap per voxel (kiss.py:129)
@@ -136,10 +139,13 @@ struct Ctx {
     int n_in, n_max;
     // scan work buffers
     double* pts;
-    int *slot1, *slot2;
-    VdsEnt *vtab1, *vtab2;
-    unsigned vmask, vmask2;      // slots - 1 of the pass-1 / pass-2 per-scan voxel tables
-    int *bcnt1, *bcnt2;
+    // ... of the two down-sampling passes (VdsPass, vds_pass1 / vds_pass2 below)
+    int *slot1, *slot2;          // per-point slot words
+    VdsEnt* vtab1;               // per-scan voxel tables
+    VdsEnt* vtab2;
+    unsigned vmask, vmask2;      // ... their slots - 1
+    int* bcnt1;                  // per-block winner counts / look-back words
+    int* bcnt2;
     double *fd, *src0, *src_cur, *fdw;
     double* coltab;  // [12][W] per-column deskew transforms (R row-major 9, t 3), entry-major
     int *pslot, *nxt, *prank, *plen;
@@ -479,6 +485,26 @@ __device__ __forceinline__ Slice launch_slice() { Slice s; s.b = (int)blockIdx.x
 #define STAGE_MAX_WAVES 16  /* blockDim.x <= 1024 */
 #define STAGE_MAX_U 16
 
+// A voxel down-sampling PASS: the first point in scan order of every voxel of `in` goes to `out`, in scan order.  A claiming stage
+// (K1 for pass 1, K3b for pass 2; vds_claim_run_heads) leaves slot[i] = the voxel's slot in `tab` if point i heads a run of equal keys,
+// else -1, and tab[slot].vmin = the smallest index that bid for the voxel: its winner.  d_count_winners / d_compact_winners then
+// write `out` and its length.  The two passes differ in these fields and in what their claiming stage does before it has a key:
+//   pass 1  VoxelDownsample(0.5 vs) over the n_in deskewed points      pts -> frame_downsample (fd),  n_down
+//   pass 2  VoxelDownsample(1.5 vs) over the compact frame_downsample  fd  -> source (src0),          n_src
+struct VdsPass {
+    int* slot;
+    VdsEnt* tab;
+    unsigned mask;     // slots of tab - 1
+    int* bcnt;         // per-block winner counts (d_count_winners), or the look-back words
+    const double* in;
+    double* out;
+    int DevState::*n_out;  // the counter of `st` that receives the length of `out`
+    int n;             // points of `in`
+    DevState* st;
+};
+__device__ __forceinline__ VdsPass vds_pass1(const Ctx& c) { return VdsPass{c.slot1, c.vtab1, c.vmask, c.bcnt1, c.pts, c.fd, &DevState::n_down, c.n_in, c.st}; }
+__device__ __forceinline__ VdsPass vds_pass2(const Ctx& c) { return VdsPass{c.slot2, c.vtab2, c.vmask2, c.bcnt2, c.fd, c.src0, &DevState::n_src, c.st->n_down, c.st}; }
+
 // U find-or-claims in a per-scan VDS table in flight together: the compare-and-swap on the hashed slot straight away (it
 // returns what was there: empty -> claimed, the key -> found; a look at the slot first would be one more dependent memory
 // round trip per pass).  What that does not settle (the slot holds another voxel) walks on by linear probing IN ROUNDS: every
@@ -526,6 +552,40 @@ __device__ __forceinline__ void vds_bid_u(VdsEnt* tab, const int (&slot)[U], con
         if (slot[u] < 0) atomicOr(err_flags, ERR_VDS_TABLE);
         else atomicMin(&tab[slot[u]].vmin, (unsigned)idx[u]);
     }
+}
+// Neighbours along a beam (pass 1) and along the compact frame_downsample (pass 2) fall into the same voxel in long runs (hundreds
+// of returns close to the sensor), and same-address atomics serialise at the memory side.  Only the first lane of each run of equal
+// keys within the wavefront - the lowest index of the run, the only one that can be its voxel's first point in scan order (every
+// other point of the run has a lower index of the same voxel right beside it) - claims the slot and bids for it, and only it keeps
+// the slot: slot_out = -1 for everybody else, so the compaction reads the slot's winner for 46 k points of a sweep instead of
+// 120 k (scattered 16-byte reads), and the heads' slots need not be handed down the runs (round 6).
+// exec_counter: the pass's executed-work counter (one claim per run head).  between(): called after the claims and before the bids
+// (K1's stage clocks time the two separately).
+struct VdsNoLap { __device__ __forceinline__ void operator()() const {} };
+template <int U, class Between = VdsNoLap>
+__device__ __forceinline__ void vds_claim_run_heads(VdsEnt* tab, unsigned mask, const unsigned long long (&key)[U], const bool (&has_key)[U],
+                                                    const int (&idx)[U], int (&slot_out)[U], unsigned long long* exec_counter, int* err_flags,
+                                                    Between between = Between()) {
+    const int lane = threadIdx.x & 63;
+    bool head[U];
+    int slot[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned long long prev = __shfl_up(key[u], 1);
+        const bool prev_has_key = __shfl_up(has_key[u] ? 1 : 0, 1) != 0;
+        head[u] = has_key[u] && (lane == 0 || !prev_has_key || prev != key[u]);
+    }
+    vds_claim_u<U>(tab, mask, key, head, slot);
+    {
+        int nh = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) nh += __popcll(__ballot(head[u]));
+        if (lane == 0 && nh) atomicAdd(exec_counter, (unsigned long long)nh);
+    }
+    between();
+    vds_bid_u<U>(tab, slot, head, idx, err_flags);
+#pragma unroll
+    for (int u = 0; u < U; ++u) slot_out[u] = head[u] ? slot[u] : -1;
 }
 // number of set flags over the workgroup's U * blockDim.x points (every thread gets it)
 template <int U>
@@ -628,38 +688,15 @@ __device__ __forceinline__ void d_deskew_vds1(const Ctx& c, const Slice sl, cons
             }
         }
     }
-    // Neighbours along a beam fall into the same voxel in long runs (hundreds of returns close to the sensor), and
-    // same-address atomics serialise at the memory side.  Only the first lane of each run of equal keys within the
-    // wavefront - the lowest index of the run, the only one that can win - claims the slot and bids for it; the others
-    // take the slot from it.
     k1.lap(c, D_k1_load_deskew_store);
     {
-        const int lane = threadIdx.x & 63;
-        bool head[U];
+        const VdsPass p1 = vds_pass1(c);
         int slot[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned long long prev = __shfl_up(key[u], 1);
-            const bool prev_keyed = __shfl_up(keyed[u] ? 1 : 0, 1) != 0;
-            head[u] = keyed[u] && (lane == 0 || !prev_keyed || prev != key[u]);
-        }
-        vds_claim_u<U>(c.vtab1, c.vmask, key, head, slot);
-        {   // executed-work counter: voxel claims (one per run head)
-            int nh = 0;
-#pragma unroll
-            for (int u = 0; u < U; ++u) nh += __popcll(__ballot(head[u]));
-            if (lane == 0 && nh) atomicAdd(&st->exec_cnt[4], (unsigned long long)nh);
-        }
-        k1.lap(c, D_k1_claim);
-        vds_bid_u<U>(c.vtab1, slot, head, idx, &st->err_flags);
+        vds_claim_run_heads<U>(p1.tab, p1.mask, key, keyed, idx, slot, &st->exec_cnt[4], &st->err_flags, [&] { k1.lap(c, D_k1_claim); });
         k1.lap(c, D_k1_bid);
-        // Only the HEAD of a run of equal keys can be its voxel's first point in scan order (every other point of the run has a lower
-        // index of the same voxel right beside it in this wavefront), so only heads keep their slot: K3 then reads the slot's winner
-        // for 46 k points of a sweep instead of 120 k (scattered 16-byte reads), and the heads' slots need not be handed down the runs
-        // (a ballot, a count and a shuffle per point).  Round 6.
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (idx[u] < c.n_in) c.slot1[idx[u]] = head[u] ? slot[u] : -1;
+            if (idx[u] < p1.n) p1.slot[idx[u]] = slot[u];
     }
     k1.lap(c, D_k1_slot1);
     if (wave_valid) {
@@ -760,95 +797,94 @@ __device__ __forceinline__ int lookback_offset(const int* bcnt, int b, unsigned 
 __device__ __forceinline__ unsigned lookback_tag(int scan_k) { return ((unsigned)scan_k % 0xFFFFu) + 1u; }  // 1 .. 65535 (0 = never published: the arrays are zeroed at a reset); a block holds <= 16 x 1024 points: 16 bits of count
 static_assert(STAGE_MAX_U * 1024 < (1 << 16), "the look-back word keeps a block's count in 16 bits");
 
-// ------------------------------------------------------------------------------------------------ K2
-// VoxelDownsample(0.5 vs) decided: the winner of a voxel is the point whose index stands in its slot.  The drivers that launch
-// every stage as a kernel of its own count the winners per block here (the prefix of K3); the free-running kernel does not run
-// this pass at all (K3 counts for itself and looks back).
+// ------------------------------------------------------------------------------------------------ K2 / K3 and K3b's count / K4
+// A voxel down-sampling pass (VdsPass) decided and compacted, once for both passes.
+// K2 (pass 1) and the second half of K3b (pass 2): the winners counted per block, the prefix of the compaction.  Only the drivers
+// that launch every stage as a kernel of its own run it; the free-running kernel's compaction counts for itself and looks back.
 template <int U>
-__device__ __forceinline__ void d_count_w1(const Ctx& c, const Slice sl) {
+__device__ __forceinline__ void d_count_winners(const VdsPass& p, const Slice sl) {
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
-    int idx[U], s1[U];
-    bool w1[U];
+    int idx[U], s[U];
+    bool w[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; s1[u] = (idx[u] < c.n_in) ? c.slot1[idx[u]] : -1; }
+    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; s[u] = (idx[u] < p.n) ? p.slot[idx[u]] : -1; }
     {
         unsigned vm[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) vm[u] = (s1[u] >= 0) ? c.vtab1[s1[u]].vmin : 0u;
+        for (int u = 0; u < U; ++u) vm[u] = (s[u] >= 0) ? p.tab[s[u]].vmin : 0u;
 #pragma unroll
-        for (int u = 0; u < U; ++u) w1[u] = (s1[u] >= 0) && (vm[u] == (unsigned)idx[u]);
+        for (int u = 0; u < U; ++u) w[u] = (s[u] >= 0) && (vm[u] == (unsigned)idx[u]);
     }
-    const int n1 = block_count_u<U>(w1);
-    if (threadIdx.x == 0) c.bcnt1[sl.b] = n1;
+    const int nw = block_count_u<U>(w);
+    if (threadIdx.x == 0) p.bcnt[sl.b] = nw;
 }
 
-// ------------------------------------------------------------------------------------------------ K3
-// frame_downsample = the pass-1 winners in scan order.  LB: one pass with look-back (tag = lookback_tag(scan)); else the block
-// counts of d_count_w1.
+// K3 (pass 1: frame_downsample) and K4 (pass 2: source): the winners in scan order; a winner releases its voxel slot for the next
+// scan (only it touches the slot).  LB: one pass with look-back (tag = lookback_tag(scan)); else the block counts of
+// d_count_winners.  pre: the block's slot words, loaded a pass ahead by the caller (stage_load_i32).
 template <int U, bool LB>
-__device__ __forceinline__ void d_compact_fd(const Ctx& c, const Slice sl, const PreI32<U>* pre = nullptr, unsigned tag = 0u) {
+__device__ __forceinline__ void d_compact_winners(const VdsPass& p, const Slice sl, const PreI32<U>* pre = nullptr, unsigned tag = 0u) {
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
-    int idx[U], s1[U], rk[U];
-    bool w1[U];
+    int idx[U], s[U], rk[U];
+    bool w[U];
     int off_part = 0;
-    if (!LB) off_part = block_offset_part(c.bcnt1, sl.b);
+    if (!LB) off_part = block_offset_part(p.bcnt, sl.b);
 #pragma unroll
-    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; s1[u] = pre ? pre->v[u] : ((idx[u] < c.n_in) ? c.slot1[idx[u]] : -1); }
+    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; s[u] = pre ? pre->v[u] : ((idx[u] < p.n) ? p.slot[idx[u]] : -1); }
     {
         unsigned vm[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) vm[u] = (s1[u] >= 0) ? c.vtab1[s1[u]].vmin : 0u;
+        for (int u = 0; u < U; ++u) vm[u] = (s[u] >= 0) ? p.tab[s[u]].vmin : 0u;
 #pragma unroll
-        for (int u = 0; u < U; ++u) w1[u] = (s1[u] >= 0) && (vm[u] == (unsigned)idx[u]);
+        for (int u = 0; u < U; ++u) w[u] = (s[u] >= 0) && (vm[u] == (unsigned)idx[u]);
     }
     double q[U][3];  // every winner's point requested before anything waits or is stored
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const size_t i = (size_t)idx[u];
-        if (w1[u]) { q[u][0] = c.pts[3 * i]; q[u][1] = c.pts[3 * i + 1]; q[u][2] = c.pts[3 * i + 2]; }
+        if (w[u]) { q[u][0] = p.in[3 * i]; q[u][1] = p.in[3 * i + 1]; q[u][2] = p.in[3 * i + 2]; }
     }
     int total;
-    block_rank_u<U>(w1, rk, total);
+    block_rank_u<U>(w, rk, total);
     int off;
     if (LB) {
-        lookback_publish(c.bcnt1, sl.b, tag, total);
-        off = lookback_offset(c.bcnt1, sl.b, tag, c.st);
+        lookback_publish(p.bcnt, sl.b, tag, total);
+        off = lookback_offset(p.bcnt, sl.b, tag, p.st);
     } else {
         off = block_offset(off_part);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        if (!w1[u]) continue;
+        if (!w[u]) continue;
         const size_t o = (size_t)(off + rk[u]) * 3;
-        c.fd[o] = q[u][0]; c.fd[o + 1] = q[u][1]; c.fd[o + 2] = q[u][2];
-        // release the pass-1 slot for the next scan (only its winner touches it)
-        c.vtab1[s1[u]].key = EMPTY_KEY;
-        c.vtab1[s1[u]].vmin = 0xFFFFFFFFu;
+        p.out[o] = q[u][0]; p.out[o + 1] = q[u][1]; p.out[o + 2] = q[u][2];
+        p.tab[s[u]].key = EMPTY_KEY;
+        p.tab[s[u]].vmin = 0xFFFFFFFFu;
     }
-    if (threadIdx.x == 0 && sl.b == sl.nb - 1) c.st->n_down = off + total;
+    if (threadIdx.x == 0 && sl.b == sl.nb - 1) p.st->*p.n_out = off + total;
 }
 
 // ------------------------------------------------------------------------------------------------ K3b
 // VoxelDownsample(1.5 vs) of frame_downsample, on the COMPACT array (N_d ~ 35 k entries instead of a pass over the 131 k raw
 // indices of which a quarter are winners): entry j claims its coarse voxel, the smallest j in a voxel wins - the first in
-// scan order, as before (frame_downsample is in scan order).  slot2[j] = the voxel's slot.  Runs as in pass 1: consecutive
-// entries of a wavefront mostly share the coarser voxel; only the first of a run of equal keys claims and bids.
+// scan order, as before (frame_downsample is in scan order).  Runs as in pass 1: consecutive entries of a wavefront mostly share
+// the coarser voxel.
 template <int U>
 __device__ __forceinline__ void d_vds2_fd(const Ctx& c, const Slice sl) {
     const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
-    const int nd = c.st->n_down;
+    const VdsPass p2 = vds_pass2(c);
     int idx[U];
     bool act[U];
     unsigned long long key[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; act[u] = idx[u] < nd; key[u] = EMPTY_KEY; }
+    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; act[u] = idx[u] < p2.n; key[u] = EMPTY_KEY; }
     {
         double q[U][3];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const size_t j = (size_t)idx[u];
             q[u][0] = q[u][1] = q[u][2] = 0.0;
-            if (act[u]) { q[u][0] = c.fd[3 * j]; q[u][1] = c.fd[3 * j + 1]; q[u][2] = c.fd[3 * j + 2]; }
+            if (act[u]) { q[u][0] = p2.in[3 * j]; q[u][1] = p2.in[3 * j + 1]; q[u][2] = p2.in[3 * j + 2]; }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -857,87 +893,13 @@ __device__ __forceinline__ void d_vds2_fd(const Ctx& c, const Slice sl) {
             vox_key(v3(q[u][0], q[u][1], q[u][2]), c.vds2, key[u], kx, ky, kz);
         }
     }
-    const int lane = threadIdx.x & 63;
-    bool head[U];
     int slot[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const unsigned long long prev = __shfl_up(key[u], 1);
-        const bool prev_act = __shfl_up(act[u] ? 1 : 0, 1) != 0;
-        head[u] = act[u] && (lane == 0 || !prev_act || prev != key[u]);
-    }
-    vds_claim_u<U>(c.vtab2, c.vmask2, key, head, slot);
-    {
-        int nh = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) nh += __popcll(__ballot(head[u]));
-        if (lane == 0 && nh) atomicAdd(&c.st->exec_cnt[5], (unsigned long long)nh);
-    }
-    vds_bid_u<U>(c.vtab2, slot, head, idx, &c.st->err_flags);
+    vds_claim_run_heads<U>(p2.tab, p2.mask, key, act, idx, slot, &c.st->exec_cnt[5], &c.st->err_flags);
 #pragma unroll
     for (int u = 0; u < U; ++u)
-        if (act[u]) c.slot2[idx[u]] = head[u] ? slot[u] : -1;  // (only a run's head can win its voxel: see K1)
-}
-// ... and its winners counted per block (the drivers with one launch per stage; the free-running kernel looks back in K4)
-template <int U>
-__device__ __forceinline__ void d_count_w2(const Ctx& c, const Slice sl) {
-    const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
-    const int nd = c.st->n_down;
-    bool w2[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int j = base + u * BS;
-        const int s2 = (j < nd) ? c.slot2[j] : -1;
-        w2[u] = s2 >= 0 && c.vtab2[s2].vmin == (unsigned)j;
-    }
-    const int n2 = block_count_u<U>(w2);
-    if (threadIdx.x == 0) c.bcnt2[sl.b] = n2;
+        if (act[u]) p2.slot[idx[u]] = slot[u];
 }
 
-// ------------------------------------------------------------------------------------------------ K4
-// source = the pass-2 winners in scan order, over the compact frame_downsample; a winner releases its voxel slot for the next scan
-template <int U, bool LB>
-__device__ __forceinline__ void d_compact_src(const Ctx& c, const Slice sl, unsigned tag = 0u) {
-    const int BS = (int)blockDim.x, base = sl.b * BS * U + (int)threadIdx.x;
-    const int nd = c.st->n_down;
-    int idx[U], s2[U], rk[U];
-    bool w2[U];
-    int off_part = 0;
-    if (!LB) off_part = block_offset_part(c.bcnt2, sl.b);
-#pragma unroll
-    for (int u = 0; u < U; ++u) { idx[u] = base + u * BS; s2[u] = (idx[u] < nd) ? c.slot2[idx[u]] : -1; }
-    {
-        unsigned vm[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) vm[u] = (s2[u] >= 0) ? c.vtab2[s2[u]].vmin : 0u;
-#pragma unroll
-        for (int u = 0; u < U; ++u) w2[u] = (s2[u] >= 0) && (vm[u] == (unsigned)idx[u]);
-    }
-    double q[U][3];  // every winner's point requested before anything waits or is stored
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const size_t j = (size_t)idx[u];
-        if (w2[u]) { q[u][0] = c.fd[3 * j]; q[u][1] = c.fd[3 * j + 1]; q[u][2] = c.fd[3 * j + 2]; }
-    }
-    int total;
-    block_rank_u<U>(w2, rk, total);
-    int off;
-    if (LB) {
-        lookback_publish(c.bcnt2, sl.b, tag, total);
-        off = lookback_offset(c.bcnt2, sl.b, tag, c.st);
-    } else {
-        off = block_offset(off_part);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        if (!w2[u]) continue;
-        const size_t o = (size_t)(off + rk[u]) * 3;
-        c.src0[o] = q[u][0]; c.src0[o + 1] = q[u][1]; c.src0[o + 2] = q[u][2];
-        c.vtab2[s2[u]].key = EMPTY_KEY;
-        c.vtab2[s2[u]].vmin = 0xFFFFFFFFu;
-    }
-    if (threadIdx.x == 0 && sl.b == sl.nb - 1) c.st->n_src = off + total;
-}
 // ------------------------------------------------------------------------------------------------ K5
 // map probe: block id of voxel `key` or -1
 template <class CT>
@@ -3170,8 +3132,9 @@ __device__ __forceinline__ Ctx load_seq_ctx(const SeqCtx* a, int s, int scan_k) 
     else { c.in_f32 = p; c.in_range = nullptr; }
     // the stage bodies' base pointers as explicit scalars (see gn8_body)
     c.in_f32 = uniform_ptr(c.in_f32); c.in_range = uniform_ptr(c.in_range);
-    c.pts = uniform_ptr(c.pts); c.slot1 = uniform_ptr(c.slot1); c.slot2 = uniform_ptr(c.slot2);
-    c.vtab1 = uniform_ptr(c.vtab1); c.vtab2 = uniform_ptr(c.vtab2); c.bcnt1 = uniform_ptr(c.bcnt1); c.bcnt2 = uniform_ptr(c.bcnt2);
+    c.pts = uniform_ptr(c.pts);
+    c.slot1 = uniform_ptr(c.slot1); c.vtab1 = uniform_ptr(c.vtab1); c.bcnt1 = uniform_ptr(c.bcnt1);
+    c.slot2 = uniform_ptr(c.slot2); c.vtab2 = uniform_ptr(c.vtab2); c.bcnt2 = uniform_ptr(c.bcnt2);
     c.fd = uniform_ptr(c.fd); c.fdw = uniform_ptr(c.fdw); c.src0 = uniform_ptr(c.src0); c.coltab = uniform_ptr(c.coltab);
     c.pslot = uniform_ptr(c.pslot); c.nxt = uniform_ptr(c.nxt); c.prank = uniform_ptr(c.prank); c.plen = uniform_ptr(c.plen);
     c.tab = uniform_ptr(c.tab); c.blocks = uniform_ptr(c.blocks); c.free_stack = uniform_ptr(c.free_stack); c.st = uniform_ptr(c.st);
@@ -3194,30 +3157,30 @@ __global__ __launch_bounds__(256) void kb_deskew_vds1(const SeqCtx* a, int scan_
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
     d_deskew_vds1<1>(c, launch_slice());
 }
-__global__ __launch_bounds__(256) void k_count_w1(Ctx c) { d_count_w1<1>(c, launch_slice()); }
+__global__ __launch_bounds__(256) void k_count_w1(Ctx c) { d_count_winners<1>(vds_pass1(c), launch_slice()); }
 __global__ __launch_bounds__(256) void kb_count_w1(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
-    d_count_w1<1>(c, launch_slice());
+    d_count_winners<1>(vds_pass1(c), launch_slice());
 }
-__global__ __launch_bounds__(256) void k_compact_fd(Ctx c) { d_compact_fd<1, false>(c, launch_slice()); }
+__global__ __launch_bounds__(256) void k_compact_fd(Ctx c) { d_compact_winners<1, false>(vds_pass1(c), launch_slice()); }
 __global__ __launch_bounds__(256) void kb_compact_fd(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
-    d_compact_fd<1, false>(c, launch_slice());
+    d_compact_winners<1, false>(vds_pass1(c), launch_slice());
 }
 __global__ __launch_bounds__(256) void k_vds2_fd(Ctx c) { d_vds2_fd<1>(c, launch_slice()); }
 __global__ __launch_bounds__(256) void kb_vds2_fd(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
     d_vds2_fd<1>(c, launch_slice());
 }
-__global__ __launch_bounds__(256) void k_count_w2(Ctx c) { d_count_w2<1>(c, launch_slice()); }
+__global__ __launch_bounds__(256) void k_count_w2(Ctx c) { d_count_winners<1>(vds_pass2(c), launch_slice()); }
 __global__ __launch_bounds__(256) void kb_count_w2(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
-    d_count_w2<1>(c, launch_slice());
+    d_count_winners<1>(vds_pass2(c), launch_slice());
 }
-__global__ __launch_bounds__(256) void k_compact_src(Ctx c) { d_compact_src<1, false>(c, launch_slice()); }
+__global__ __launch_bounds__(256) void k_compact_src(Ctx c) { d_compact_winners<1, false>(vds_pass2(c), launch_slice()); }
 __global__ __launch_bounds__(256) void kb_compact_src(const SeqCtx* a, int scan_k) {
     const Ctx c = load_seq_ctx(a, blockIdx.y, scan_k);
-    d_compact_src<1, false>(c, launch_slice());
+    d_compact_winners<1, false>(vds_pass2(c), launch_slice());
 }
 __global__ __launch_bounds__(256) void k_map_insert_a(Ctx c, const double* pts_in, const int* n_ptr, int n_fixed, int use_pose) { d_map_insert_a<1>(c, pts_in, n_ptr, n_fixed, use_pose, launch_slice()); }
 __global__ __launch_bounds__(256) void kb_map_insert_a(const SeqCtx* a, int scan_k) {

@@ -94,7 +94,7 @@ __device__ __forceinline__ unsigned xcc_id() {
 #define SEQ_UM_ALT 4  /* the map update's second instance (test hook: the result must not depend on the points per thread) */
 #endif
 #ifndef SEQ_U2
-#define SEQ_U2 16  /* ... in K3 / K3b / K4 (a few registers per point: an index, a slot, two flags); they share their block size through bcnt1 / bcnt2 */
+#define SEQ_U2 16  /* ... in K3 / K3b / K4 (a few registers per point: an index, a slot, two flags); K3 and K4 share their block size through the pass's block counts */
 #endif
 // make STAGES=1: workgroup 0 of every sequence adds the wall-clock ticks of every stage and of every barrier wait to the sq_ slots of
 // diag.h (tools/stage_clocks.py and tools/free_vs_lockstep.py print them)
@@ -145,7 +145,7 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
             Slice nx = sl;
             nx.b = sl.b + nw;
             if (nx.b < nbs2) pw = stage_load_i32<SEQ_U2>(c.slot1, c.n_in, nx);
-            d_compact_fd<SEQ_U2, true>(c, sl, &cur, tag);
+            d_compact_winners<SEQ_U2, true>(vds_pass1(c), sl, &cur, tag);
         }
     }
     sq.lap(c, D_sq_compact_fd);
@@ -158,7 +158,7 @@ __device__ __noinline__ unsigned sq_prepare(const SeqCtx* a, int s, int k, int w
     sq.lap(c, D_sq_vds2);
     if (!team_sync(te, (unsigned)nw, target)) return SEQ_FAIL;
     sq.lap(c, D_sq_wait_vds2);
-    for (sl.b = wg; sl.b < nbf; sl.b += nw) d_compact_src<SEQ_U2, true>(c, sl, tag);
+    for (sl.b = wg; sl.b < nbf; sl.b += nw) d_compact_winners<SEQ_U2, true>(vds_pass2(c), sl, nullptr, tag);
     sq.lap(c, D_sq_compact_src);
     return target;
 }
