@@ -684,6 +684,69 @@ int ptl_map_score_default_cfg(ptl_map_score_cfg *cfg, double voxel_size);
 int ptl_icp_map_score(ptl_icp *map, const ptl_map_score_cfg *cfg, ptl_map_score_result *out, double *xyz_out, int32_t *n_out,
                       double *plane_var_out, double *entropy_out, int64_t max_points, int64_t *n_written);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frames of the fly-by drawn on the device (the picture the reference's viewer shows, src/ptudes/fly.py and cli/flyby.py
+ * through ouster-sdk's PointViz - third party; the drawing here is this library's own).  Every stored point of a map, and optionally an
+ * overlay cloud the renderer owns, is projected through a pinhole camera and depth-tested into a frame; the map stays in HBM.
+ * Frame buffer: per pixel a 64-bit key = (bits of float32(view depth) << 32) | rgba, an empty pixel is all ones, a pixel's final key is the
+ * minimum over the splats that cover it - a function of the SET of points, not of their order.  Two points at the same float32 depth in a
+ * pixel resolve to the smaller rgba word.  rgba words are the bytes R, G, B, A in memory order (R the lowest byte of the word).
+ * Per point p (world) and camera: (xc, yc, zc) = view p with view a row-major 3 x 4 (world -> camera, +z forward, +x right, +y down),
+ * each row evaluated as ((v0 x + v1 y) + v2 z) + v3; rejected when !(zc > near_m) or zc >= far_m, before any division;
+ * u = fx (xc / zc) + cx, v = fy (yc / zc) + cy; pixel (floor(u), floor(v)); the footprint is point_px x point_px pixels (1 .. 5) whose top-left is
+ * (floor(u) - (point_px - 1) / 2, floor(v) - (point_px - 1) / 2) (integer division), clipped pixel by pixel to the image.  A map point's colour is
+ * palette[clamp(floor((z - z_lo) * (256 / (z_hi - z_lo))), 0, 255)], z its world height; an overlay point's colour is taken as given.
+ * With edl_strength > 0 the resolved colour is shaded by eye-dome lighting from the depths d of the four neighbours at edl_radius_px (left, right,
+ * up, down; those inside the image and not empty): s = exp(-edl_strength max(0, mean(log2 d - log2 d_nb))), channel c -> floor(c s + 0.5), alpha kept.
+ * All arithmetic is fp64 without contraction; csrc/render_kernels.h spells out the order. */
+typedef struct ptl_render ptl_render;
+#define PTL_RENDER_MAX_KEY_BYTES (1ll << 30) /* bound of width * height * max_frames_per_call * 8, the key buffer of one launch */
+typedef struct {
+    uint32_t struct_size;        /* sizeof(ptl_render_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    int32_t width, height;       /* pixels, 1 .. 16384 each */
+    int32_t point_px;            /* footprint of a map point, 1 .. 5 (default 2) */
+    int32_t max_frames_per_call; /* frames per launch (default 16) */
+    double z_lo, z_hi;           /* world heights of palette entries 0 and 255 (default -2, 10); z_hi > z_lo */
+    uint32_t background_rgba;    /* default 0xFF000000: opaque black */
+    double edl_strength;         /* 0 (default) = off */
+    int32_t edl_radius_px;       /* >= 1 (default 1) */
+} ptl_render_cfg;
+/* a plain array element, not a versioned struct */
+typedef struct {
+    double view[12];
+    double fx, fy, cx, cy, near_m, far_m;
+} ptl_render_cam;
+/* the library's sizeof(ptl_render_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_render_sizeof_cfg(void);
+/* the defaults above for a width x height frame; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is
+ * refused with PTL_ERR_ARG and nothing is written */
+int ptl_render_default_cfg(ptl_render_cfg *cfg, int32_t width, int32_t height);
+/* refused with the offending numbers, before any HIP call: width / height outside 1 .. 16384, point_px outside 1 .. 5, max_frames_per_call < 1,
+ * z_hi <= z_lo, edl_strength < 0 or not finite, edl_radius_px < 1, a key buffer above PTL_RENDER_MAX_KEY_BYTES.  The renderer owns a stream,
+ * the key buffer and the output staging of one launch, the palette and the overlay. */
+int ptl_render_create(const ptl_render_cfg *cfg, int32_t device_id, ptl_render **out);
+int ptl_render_destroy(ptl_render *r);
+/* 256 rgba words.  The default: entry i = {R = i, G = 255 - |2 i - 255|, B = 255 - i, A = 255} - blue at z_lo over green to red at z_hi */
+int ptl_render_set_palette(ptl_render *r, const uint32_t rgba[256]);
+/* the world heights of palette entries 0 and 255 for the frames that follow (cfg.z_lo, cfg.z_hi); z_hi <= z_lo: PTL_ERR_ARG with both numbers */
+int ptl_render_set_z_range(ptl_render *r, double z_lo, double z_hi);
+/* the overlay cloud (e.g. the trajectory's positions): n points xyz (n x 3 f64, world) with their colours, drawn point_px wide (1 .. 5) into
+ * every frame after the map under the same depth test; n = 0 clears it (xyz / rgba may then be NULL) */
+int ptl_render_set_overlay(ptl_render *r, const double *xyz, const uint32_t *rgba, int64_t n, int32_t point_px);
+/* n_frames frames of `map` (nullable: the overlay only) through cams[n_frames], in launches of max_frames_per_call frames.  Like
+ * ptl_icp_map_score it waits for the handle's map update, only reads the map and keeps nothing in the map handle.  Outputs (host): rgba_out
+ * n_frames x height x width words; depth_out (nullable) as many float32, +inf = empty; keys_out (nullable) as many raw 64-bit keys;
+ * in_view_out (nullable) n_frames counts of the points (map and overlay) that passed the depth test with at least one pixel of their footprint
+ * in the image; device_ms (nullable) the HIP-event time of the launches' device work.  Checked before any HIP call, refused with the numbers:
+ * n_frames < 0, a camera with near_m <= 0 or far_m <= near_m or a non-finite entry, renderer and map on different devices.  An empty map
+ * gives background frames and zero counts. */
+int ptl_render_frames(ptl_render *r, ptl_icp *map, const ptl_render_cam *cams, int64_t n_frames, uint32_t *rgba_out, float *depth_out,
+                      uint64_t *keys_out, int64_t *in_view_out, double *device_ms);
+/* measurement hook (tools/render_cost.py): on == 0 drops the plain load in front of the 64-bit atomicMin - the same frames, every covered
+ * pixel then costs an atomic */
+int ptl_render_debug_set_early_reject(ptl_render *r, int32_t on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,19 @@ class MapScoreResult(C.Structure):
                 ("sigma_floor", C.c_double), ("device_ms", C.c_double)]
 
 
+class RenderCfg(_Cfg):
+    """ptl_render_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("point_px", C.c_int32),
+                ("max_frames_per_call", C.c_int32), ("z_lo", C.c_double), ("z_hi", C.c_double), ("background_rgba", C.c_uint32),
+                ("edl_strength", C.c_double), ("edl_radius_px", C.c_int32)]
+
+
+class RenderCam(C.Structure):
+    """ptl_render_cam: view = the top three rows of the world -> camera matrix (+z forward, +x right, +y down), row-major"""
+    _fields_ = [("view", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("near_m", C.c_double), ("far_m", C.c_double)]
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -219,6 +232,17 @@ PROTOTYPES = {
     "ptl_map_score_default_cfg": (C.c_int, [C.POINTER(MapScoreCfg), C.c_double]),
     "ptl_icp_map_score": (C.c_int, [_vp, C.POINTER(MapScoreCfg), C.POINTER(MapScoreResult), c_d_p, C.POINTER(C.c_int32), c_d_p, c_d_p,
                                     C.c_int64, c_i64_p]),
+    # frames of the fly-by drawn on the device (include/ptudes_mi.h)
+    "ptl_render_sizeof_cfg": (C.c_int64, []),
+    "ptl_render_default_cfg": (C.c_int, [C.POINTER(RenderCfg), C.c_int32, C.c_int32]),
+    "ptl_render_create": (C.c_int, [C.POINTER(RenderCfg), C.c_int32, _vpp]),
+    "ptl_render_destroy": (C.c_int, [_vp]),
+    "ptl_render_set_palette": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "ptl_render_set_z_range": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "ptl_render_set_overlay":(C.c_int, [_vp, c_d_p, C.POINTER(C.c_uint32), C.c_int64, C.c_int32]),
+    "ptl_render_frames": (C.c_int, [_vp, _vp, C.POINTER(RenderCam), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_uint64), c_i64_p, c_d_p]),
+    "ptl_render_debug_set_early_reject": (C.c_int, [_vp, C.c_int32]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -1,5 +1,6 @@
 """`flyby`: the headless form of reference src/ptudes/cli/flyby.py - the map its BUILDING state accumulates (cli/flyby.py:71-131,
-utils.py:344-392, fly.py:75-111), without the viewer and the camera path.
+utils.py:344-392, fly.py:75-111), without the viewer's window; `--save-frames DIR` flies the reference's camera path (to the beginning, along
+the trajectory, up to the apex) and writes every frame, drawn on the GPU, as a PNG.
 
 Every scan gets the pose of each of its columns on the trajectory of a Newer College format poses file (moved to the start scan, as the
 reference does), is de-warped and accumulated - on the GPU, fused (`fly.MapAccumulator.update(scan, traj=...)`).  The map is the
@@ -18,6 +19,39 @@ import numpy as np
 from ..utils import read_newer_college_gt, save_map_ply
 
 TIME_BOUNDS = 1.5  # seconds a column may lie outside the poses file (reference utils.py:368)
+
+
+def frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_range):
+    """the options of --save-frames checked before a device is touched: None without it, else a dict with the defaults filled in"""
+    given = {"--frame-size": frame_size, "--fps": fps, "--max-frames": max_frames, "--point-size": point_size, "--edl": edl, "--z-range": z_range}
+    if not save_frames:
+        for name, v in given.items():
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --save-frames")
+        return None
+    import re
+    m = re.fullmatch(r"(\d+)x(\d+)", frame_size or "1280x720")
+    if not m or not (1 <= int(m.group(1)) <= 16384 and 1 <= int(m.group(2)) <= 16384):
+        raise click.ClickException(f"--frame-size {frame_size}: expected WxH with both in 1 .. 16384, like 1280x720")
+    out = dict(dir=save_frames, width=int(m.group(1)), height=int(m.group(2)), fps=30.0 if fps is None else fps, max_frames=max_frames,
+               point_px=2 if point_size is None else point_size, edl=0.0 if edl is None else edl, z_range=None)
+    if not out["fps"] > 0:
+        raise click.ClickException(f"--fps {fps}: must be positive")
+    if max_frames is not None and max_frames < 0:
+        raise click.ClickException(f"--max-frames {max_frames}: must not be negative")
+    if not 1 <= out["point_px"] <= 5:
+        raise click.ClickException(f"--point-size {point_size}: must be in 1 .. 5")
+    if not out["edl"] >= 0:
+        raise click.ClickException(f"--edl {edl}: must not be negative")
+    if z_range is not None:
+        try:
+            lo, hi = (float(x) for x in z_range.split(","))
+        except ValueError:
+            raise click.ClickException(f"--z-range {z_range}: expected LO,HI")
+        if not hi > lo:
+            raise click.ClickException(f"--z-range {z_range}: HI must be above LO")
+        out["z_range"] = (lo, hi)
+    return out
 
 
 @click.command(name="flyby")
@@ -46,14 +80,28 @@ TIME_BOUNDS = 1.5  # seconds a column may lie outside the poses file (reference 
                    "neighbourhoods) and print it; with --save-map the PLY carries the per-point values")
 @click.option("--score-radius", type=float, default=None,
               help="neighbourhood radius of --map-score, metres (default and upper bound: --voxel-size)")
+@click.option("--save-frames", required=False, type=click.Path(file_okay=False),
+              help="fly the reference's camera path (to the beginning, along the trajectory, up to the apex) and write every frame, drawn on "
+                   "the GPU, to this directory as frame_000000.png, ...; -r then scales the time step as in the viewer")
+@click.option("--frame-size", type=str, default=None, help="frame size WxH of --save-frames (default 1280x720)")
+@click.option("--fps", type=float, default=None, help="frames per second of --save-frames (default 30)")
+@click.option("--max-frames", type=int, default=None, help="stop --save-frames after this many frames")
+@click.option("--point-size", type=int, default=None, help="pixels per map point of --save-frames, 1 .. 5 (default 2)")
+@click.option("--edl", type=float, default=None, help="eye-dome lighting strength of --save-frames (default 0: off)")
+@click.option("--z-range", type=str, default=None,
+              help="heights LO,HI of the palette's ends for --save-frames (default: the map's own z extent once it is built; while it is "
+                   "being built, the sensor's height +- 10 m)")
 def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional[str], nc_gt_poses: Optional[str], rate: float,
                  accum_map_ratio: Optional[float], start_scan: int, end_scan: Optional[int], voxel_size: float,
                  save_map: Optional[str], synthetic: Optional[int], native_packets: bool = False, map_score: bool = False,
-                 score_radius: Optional[float] = None) -> None:
+                 score_radius: Optional[float] = None, save_frames: Optional[str] = None, frame_size: Optional[str] = None,
+                 fps: Optional[float] = None, max_frames: Optional[int] = None, point_size: Optional[int] = None,
+                 edl: Optional[float] = None, z_range: Optional[str] = None) -> None:
     """Map of the lidar scans with poses (the flyby visualizer's map, headless).
 
     Data is provided via FILE in Ouster raw packets formats (PCAP or BAG with lidar/imu packets), or --synthetic SEED.
     """
+    frames = frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_range)
     if kitti_poses:
         raise click.ClickException("--kitti-poses is not supported here: the column timing of one-pose-per-scan files is defined inside "
                                    "ouster-sdk's pose_scans_from_kitti, which this build cannot read; use --nc-gt-poses")
@@ -78,7 +126,10 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
             raise click.ClickException("reading .pcap needs ouster-sdk" + ("" if native_packets else ", which is not installed")
                                        + "; a raw packet .bag (or a directory of bags) is read by the package's own decoder; "
                                        "use --synthetic SEED to build the map of a synthetic sequence")
-    if rate != 1.0 or accum_map_ratio is not None:
+    if frames is not None:
+        if accum_map_ratio is not None:
+            print(f"NOTE: --accum-map-ratio belongs to the viewer's map: the voxel map (voxel size {voxel_size}) replaces the random subsample")
+    elif rate != 1.0 or accum_map_ratio is not None:
         print("NOTE: -r / --accum-map-ratio belong to the viewer: there is no playback, and the voxel map "
               f"(voxel size {voxel_size}) replaces the random subsample")
     from .. import core, fly
@@ -125,7 +176,39 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
 
     traj = core.Traj([t for t, _ in gts_poses], [p for _, p in gts_poses], TIME_BOUNDS, TIME_BOUNDS)
     acc = fly.MapAccumulator(lut, voxel_size=voxel_size)
-    if native:
+    if frames is not None:
+        import os
+        from ..utils import save_png
+        if native:
+            def packet_scans():
+                from ..bag import OusterPacketBagSource
+                feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info)
+                try:
+                    for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+                        if not hasattr(d, "lacc"):
+                            yield d
+                finally:
+                    feed.close()
+            scans = packet_scans()
+        os.makedirs(frames["dir"], exist_ok=True)
+        renderer = core.Renderer(frames["width"], frames["height"], point_px=frames["point_px"], edl=frames["edl"])
+
+        def osd(state):
+            # the lines of the viewer's OSD (reference cli/flyby.py:164-172), once per state change
+            print(f"map of scans: {start_scan} - {end_scan}")
+            print(f"map num points: {acc.map_size()[1]}")
+            print(f"state: {state.replace('_', '..')}")
+            print(f"playback: {rate}")
+
+        fb = fly.FlyBy(acc, renderer, gts_poses, fps=frames["fps"], rate=rate, time_bounds=TIME_BOUNDS, z_range=frames["z_range"],
+                       max_frames=frames["max_frames"], on_state=osd)
+        n_written = 0
+        for _, rgba in fb.frames(scans, traj=traj):
+            save_png(os.path.join(frames["dir"], f"frame_{n_written:06d}.png"), rgba)
+            n_written += 1
+        renderer.close()
+        print(f"{n_written} frames ({frames['width']}x{frames['height']}) saved to: {frames['dir']}")
+    elif native:
         fly.add_packet_bag(acc, bags, info, traj, start_scan, end_scan)
     else:
         for scan in scans:

@@ -343,6 +343,95 @@ class Traj:
     __del__ = close
 
 
+def rgba_word(rgba):
+    """(..., 4) uint8 R, G, B, A -> the uint32 words the renderer's keys carry (R the lowest byte)"""
+    a = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if a.shape[-1] != 4:
+        raise ValueError("rgba needs four bytes per colour")
+    return a.view("<u4").reshape(a.shape[:-1]).astype(np.uint32)
+
+
+def default_palette():
+    """(256, 4) uint8: the renderer's default ramp (include/ptudes_mi.h ptl_render_set_palette)"""
+    i = np.arange(256)
+    return np.stack([i, 255 - np.abs(2 * i - 255), 255 - i, np.full(256, 255)], axis=1).astype(np.uint8)
+
+
+class Renderer:
+    """Frames of a map drawn on the device (include/ptudes_mi.h ptl_render): point splats of point_px pixels with a depth
+    test, coloured by world height through a 256-entry palette over z_range, optionally shaded by eye-dome lighting (edl = its strength)."""
+
+    def __init__(self, width, height, point_px=2, z_range=(-2.0, 10.0), background=(0, 0, 0, 255), edl=0.0, device_id=0,
+                 max_frames_per_call=16, edl_radius_px=1):
+        cfg = L.RenderCfg()
+        L.check(L.lib().ptl_render_default_cfg(C.byref(cfg), int(width), int(height)))
+        cfg.point_px, cfg.max_frames_per_call = int(point_px), int(max_frames_per_call)
+        cfg.z_lo, cfg.z_hi = float(z_range[0]), float(z_range[1])
+        cfg.background_rgba = int(rgba_word(np.asarray(background, dtype=np.uint8).reshape(4)))
+        cfg.edl_strength, cfg.edl_radius_px = float(edl), int(edl_radius_px)
+        self.cfg, self.width, self.height, self.device_id = cfg, int(width), int(height), int(device_id)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_render_create(C.byref(cfg), int(device_id), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_render_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_palette(self, rgba):
+        """256 colours, (256, 4) uint8 R G B A"""
+        w = np.ascontiguousarray(rgba_word(np.asarray(rgba, dtype=np.uint8).reshape(256, 4)))
+        L.check(L.lib().ptl_render_set_palette(self._h, w.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def set_z_range(self, lo, hi):
+        """world heights of palette entries 0 and 255 for the frames that follow"""
+        L.check(L.lib().ptl_render_set_z_range(self._h, float(lo), float(hi)))
+        self.cfg.z_lo, self.cfg.z_hi = float(lo), float(hi)
+
+    def set_overlay(self, xyz, rgba=(255, 255, 255, 255), point_px=3):
+        """the overlay cloud: (n, 3) world points with one colour each ((n, 4) uint8, or one colour for all); no points clears it"""
+        x = L.as_f64(xyz).reshape(-1, 3)
+        if len(x) == 0:
+            L.check(L.lib().ptl_render_set_overlay(self._h, None, None, 0, int(point_px)))
+            return
+        col = np.asarray(rgba, dtype=np.uint8)
+        w = np.ascontiguousarray(np.broadcast_to(rgba_word(col.reshape(-1, 4)), (len(x),)))
+        L.check(L.lib().ptl_render_set_overlay(self._h, L.dptr(x), w.ctypes.data_as(C.POINTER(C.c_uint32)), len(x), int(point_px)))
+
+    def set_early_reject(self, on):
+        """measurement hook: the plain load in front of the atomic on or off (the frames do not change)"""
+        L.check(L.lib().ptl_render_debug_set_early_reject(self._h, 1 if on else 0))
+
+    def render(self, icp, cams, depth=False, keys=False, timing=False):
+        """the frames of `icp`'s map (None: the overlay only) through cams (a list of _lib.RenderCam): (n, H, W, 4) uint8, then the float32
+        depth (n, H, W; +inf = empty) and / or the raw uint64 keys when asked, then the per-frame in-view counts (n,) int64; timing=True
+        appends the HIP-event time of the launches in ms"""
+        cams = list(cams)
+        n = len(cams)
+        arr = (L.RenderCam * max(n, 1))(*cams)
+        H, W = self.height, self.width
+        rgba = np.empty((n, H, W), dtype=np.uint32)
+        d = np.empty((n, H, W), dtype=np.float32) if depth else None
+        k = np.empty((n, H, W), dtype=np.uint64) if keys else None
+        inv = np.zeros(n, dtype=np.int64)
+        ms = C.c_double()
+        L.check(L.lib().ptl_render_frames(self._h, None if icp is None else icp._h, arr, n, rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          None if d is None else d.ctypes.data_as(C.POINTER(C.c_float)),
+                                          None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          inv.ctypes.data_as(L.c_i64_p), C.byref(ms)))
+        out = [rgba.view(np.uint8).reshape(n, H, W, 4)]
+        if depth:
+            out.append(d)
+        if keys:
+            out.append(k)
+        out.append(inv)
+        if timing:
+            out.append(ms.value)
+        return tuple(out)
+
+
 class Ekf:
     def __init__(self, init_grav=None, init_bacc=None, init_bgyr=None, device_id=0):
         self.cfg = ekf_cfg(init_grav, init_bacc, init_bgyr, device_id)

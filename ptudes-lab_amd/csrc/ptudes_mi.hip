@@ -9,6 +9,7 @@
 #include "fly_kernels.h"
 #include "packet_kernels.h"
 #include "score_kernels.h"
+#include "render_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -3066,6 +3067,200 @@ extern "C" int ptl_icp_map_score(ptl_icp* map, const ptl_map_score_cfg* cfg, ptl
         HIPCHK(hipMemcpy(entropy_out, d_ent, (size_t)n * 8, hipMemcpyDeviceToHost));
         if (n_written) *n_written = n;
     }
+    return PTL_OK;
+}
+
+// ================================================================================================ fly-by frames
+// The definition is in include/ptudes_mi.h, the kernels in render_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// renderer owns what one launch needs: the keys and the resolved outputs of max_frames_per_call frames, their cameras and counters.
+static_assert(sizeof(RenderCam) == sizeof(ptl_render_cam), "the device's camera is the header's");
+struct ptl_render {
+    ptl_render_cfg cfg;
+    int device_id = 0;
+    bool early_reject = true;
+    Stream stream;
+    unsigned* d_palette = nullptr;            // [256]
+    RenderCam* d_cams = nullptr;              // [max_frames_per_call]
+    unsigned long long* d_keys = nullptr;     // [max_frames_per_call][height][width]
+    unsigned* d_rgba = nullptr;               // the same
+    float* d_depth = nullptr;                 // the same
+    unsigned long long* d_in_view = nullptr;  // [max_frames_per_call]
+    double* d_ov_xyz = nullptr;               // the overlay: [ov_n][3]
+    unsigned* d_ov_rgba = nullptr;            // [ov_n]
+    int64_t ov_n = 0;
+    int ov_px = 1;
+    DevOwner mem;
+};
+static void render_defaults(ptl_render_cfg* cfg, int32_t width, int32_t height) {
+    PTL_CFG_INIT(cfg);
+    cfg->width = width; cfg->height = height;
+    cfg->point_px = 2;
+    cfg->max_frames_per_call = 16;
+    cfg->z_lo = -2.0; cfg->z_hi = 10.0;
+    cfg->background_rgba = 0xFF000000u;
+    cfg->edl_strength = 0.0;
+    cfg->edl_radius_px = 1;
+}
+static int render_check_cfg(const ptl_render_cfg* c) {
+    if (c->width < 1 || c->width > 16384 || c->height < 1 || c->height > 16384)
+        return set_err(PTL_ERR_ARG, "frame of %d x %d pixels: width and height must be in [1, 16384]", c->width, c->height);
+    if (c->point_px < 1 || c->point_px > RENDER_MAX_PX) return set_err(PTL_ERR_ARG, "point_px = %d: must be in [1, %d]", c->point_px, RENDER_MAX_PX);
+    if (c->max_frames_per_call < 1) return set_err(PTL_ERR_ARG, "max_frames_per_call = %d: must be >= 1", c->max_frames_per_call);
+    if (!(c->z_hi > c->z_lo) || !(c->z_hi - c->z_lo < 1.0e300))
+        return set_err(PTL_ERR_ARG, "z_lo = %g, z_hi = %g: the palette needs finite z_hi > z_lo", c->z_lo, c->z_hi);
+    if (!(c->edl_strength >= 0.0) || !(c->edl_strength < 1.0e300)) return set_err(PTL_ERR_ARG, "edl_strength = %g: must be >= 0 and finite", c->edl_strength);
+    if (c->edl_radius_px < 1) return set_err(PTL_ERR_ARG, "edl_radius_px = %d: must be >= 1", c->edl_radius_px);
+    const long long key_bytes = (long long)c->width * c->height * 8 * (long long)c->max_frames_per_call;
+    if (key_bytes > PTL_RENDER_MAX_KEY_BYTES)
+        return set_err(PTL_ERR_ARG, "%d frames of %d x %d pixels per launch need a key buffer of %lld bytes; the bound is %lld",
+                       c->max_frames_per_call, c->width, c->height, key_bytes, (long long)PTL_RENDER_MAX_KEY_BYTES);
+    return PTL_OK;
+}
+extern "C" int64_t ptl_render_sizeof_cfg(void) { return (int64_t)sizeof(ptl_render_cfg); }
+extern "C" int ptl_render_default_cfg(ptl_render_cfg* cfg, int32_t width, int32_t height) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_render_cfg, cfg);
+    if (width < 1 || width > 16384 || height < 1 || height > 16384)
+        return set_err(PTL_ERR_ARG, "frame of %d x %d pixels: width and height must be in [1, 16384]", width, height);
+    render_defaults(cfg, width, height);
+    return PTL_OK;
+}
+extern "C" int ptl_render_destroy(ptl_render* r) { return r ? handle_destroy(r, r->device_id) : PTL_OK; }
+extern "C" int ptl_render_create(const ptl_render_cfg* cfg, int32_t device_id, ptl_render** out) {
+    if (!cfg || !out) return set_err(PTL_ERR_ARG, "null argument");
+    ABI_CHECK(ptl_render_cfg, cfg);
+    int rc = render_check_cfg(cfg);
+    if (rc) return rc;
+    if (device_id < 0 || ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    std::unique_ptr<ptl_render> r(new ptl_render());
+    r->cfg = *cfg; r->device_id = device_id;
+    if (r->stream.create() != hipSuccess) return set_err(PTL_ERR_HIP, "stream creation failed");
+    DevOwner& m = r->mem;
+    const size_t F = (size_t)cfg->max_frames_per_call, px = (size_t)cfg->width * (size_t)cfg->height;
+    m.add(&r->d_palette, 256); m.add(&r->d_cams, F); m.add(&r->d_keys, F * px); m.add(&r->d_rgba, F * px); m.add(&r->d_depth, F * px);
+    m.add(&r->d_in_view, F);
+    if (m.err != hipSuccess) return set_err(PTL_ERR_HIP, "ptl_render_create: %s (%zu bytes)", hipGetErrorString(m.err), m.requested());
+    uint32_t ramp[256];
+    for (int i = 0; i < 256; ++i) {
+        const int tri = 2 * i - 255;
+        ramp[i] = (uint32_t)i | (uint32_t)(255 - (tri < 0 ? -tri : tri)) << 8 | (uint32_t)(255 - i) << 16 | 0xFF000000u;
+    }
+    HIPCHK(hipMemcpy(r->d_palette, ramp, sizeof ramp, hipMemcpyHostToDevice));
+    *out = r.release();
+    return PTL_OK;
+}
+extern "C" int ptl_render_set_palette(ptl_render* r, const uint32_t rgba[256]) {
+    if (!r || !rgba) return set_err(PTL_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(r->device_id));
+    HIPCHK(hipStreamSynchronize(r->stream));
+    HIPCHK(hipMemcpy(r->d_palette, rgba, 256 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return PTL_OK;
+}
+extern "C" int ptl_render_set_z_range(ptl_render* r, double z_lo, double z_hi) {
+    if (!(z_hi > z_lo) || !(z_hi - z_lo < 1.0e300)) return set_err(PTL_ERR_ARG, "z_lo = %g, z_hi = %g: the palette needs finite z_hi > z_lo", z_lo, z_hi);
+    if (!r) return set_err(PTL_ERR_ARG, "null argument");
+    r->cfg.z_lo = z_lo; r->cfg.z_hi = z_hi;
+    return PTL_OK;
+}
+extern "C" int ptl_render_set_overlay(ptl_render* r, const double* xyz, const uint32_t* rgba, int64_t n, int32_t point_px) {
+    if (n < 0 || n > 0x7fffffffLL) return set_err(PTL_ERR_ARG, "ptl_render_set_overlay: n = %lld (0 .. 2^31 - 1)", (long long)n);
+    if (n > 0 && (point_px < 1 || point_px > RENDER_MAX_PX)) return set_err(PTL_ERR_ARG, "ptl_render_set_overlay: point_px = %d: must be in [1, %d]", point_px, RENDER_MAX_PX);
+    if (!r || (n > 0 && (!xyz || !rgba))) return set_err(PTL_ERR_ARG, "ptl_render_set_overlay: null argument");
+    HIPCHK(hipSetDevice(r->device_id));
+    HIPCHK(hipStreamSynchronize(r->stream));
+    r->mem.release(&r->d_ov_xyz);
+    r->mem.release(&r->d_ov_rgba);
+    r->ov_n = 0;
+    if (n == 0) return PTL_OK;
+    HIPCHK(r->mem.alloc(&r->d_ov_xyz, (size_t)n * 3));
+    HIPCHK(r->mem.alloc(&r->d_ov_rgba, (size_t)n));
+    HIPCHK(hipMemcpy(r->d_ov_xyz, xyz, (size_t)n * 24, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(r->d_ov_rgba, rgba, (size_t)n * 4, hipMemcpyHostToDevice));
+    r->ov_n = n; r->ov_px = point_px;
+    return PTL_OK;
+}
+extern "C" int ptl_render_debug_set_early_reject(ptl_render* r, int32_t on) {
+    if (!r) return set_err(PTL_ERR_ARG, "null argument");
+    r->early_reject = on != 0;
+    return PTL_OK;
+}
+extern "C" int ptl_render_frames(ptl_render* r, ptl_icp* map, const ptl_render_cam* cams, int64_t n_frames, uint32_t* rgba_out, float* depth_out,
+                                 uint64_t* keys_out, int64_t* in_view_out, double* device_ms) {
+    // (the values first: they are refused with their numbers whatever else is wrong with the call)
+    if (n_frames < 0) return set_err(PTL_ERR_ARG, "ptl_render_frames: n_frames = %lld: must not be negative", (long long)n_frames);
+    if (n_frames > 0 && !cams) return set_err(PTL_ERR_ARG, "ptl_render_frames: %lld frames without cameras", (long long)n_frames);
+    for (int64_t f = 0; f < n_frames; ++f) {
+        const ptl_render_cam& c = cams[f];
+        if (!(c.near_m > 0.0) || !(c.far_m > c.near_m))
+            return set_err(PTL_ERR_ARG, "ptl_render_frames: camera %lld: near_m = %g, far_m = %g (need 0 < near_m < far_m)", (long long)f, c.near_m, c.far_m);
+        double s = 0.0;
+        for (int k = 0; k < 12; ++k) s += c.view[k] * 0.0;
+        s += (c.fx + c.fy + c.cx + c.cy) * 0.0;
+        if (!(s == 0.0)) return set_err(PTL_ERR_ARG, "ptl_render_frames: camera %lld has a non-finite entry", (long long)f);
+    }
+    if (!r) return set_err(PTL_ERR_ARG, "ptl_render_frames: null renderer");
+    if (n_frames > 0 && !rgba_out) return set_err(PTL_ERR_ARG, "ptl_render_frames: null rgba_out");
+    if (map && map->cfg.device_id != r->device_id)
+        return set_err(PTL_ERR_ARG, "ptl_render_frames: renderer on device %d, map on device %d", r->device_id, map->cfg.device_id);
+    if (device_ms) *device_ms = 0.0;
+    if (n_frames == 0) return PTL_OK;
+    HIPCHK(hipSetDevice(r->device_id));
+    bool draw_map = false;
+    if (map) {
+        HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+        DevState st;
+        HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, map->stream));
+        HIPCHK(hipStreamSynchronize(map->stream));
+        draw_map = st.map_points > 0;
+    }
+    const ptl_render_cfg& cfg = r->cfg;
+    const hipStream_t s = r->stream;
+    const size_t px = (size_t)cfg.width * (size_t)cfg.height;
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventDefault)); HIPCHK(e1.create(hipEventDefault));
+    RenderArgs a = {};
+    a.width = cfg.width; a.height = cfg.height; a.point_px = cfg.point_px;
+    a.z_lo = cfg.z_lo; a.zscale = 256.0 / (cfg.z_hi - cfg.z_lo);
+    a.cams = r->d_cams; a.palette = r->d_palette; a.keys = r->d_keys; a.in_view = r->d_in_view;
+    double ms_total = 0.0;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += cfg.max_frames_per_call) {
+        const int nf = (int)std::min<int64_t>(cfg.max_frames_per_call, n_frames - f0);
+        HIPCHK(hipMemcpyAsync(r->d_cams, cams + f0, (size_t)nf * sizeof(RenderCam), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(e0, s));
+        HIPCHK(hipMemsetAsync(r->d_keys, 0xFF, (size_t)nf * px * 8, s));  // (k_render_clear: every key all ones)
+        HIPCHK(hipMemsetAsync(r->d_in_view, 0, (size_t)nf * 8, s));
+        if (draw_map) {
+            MapSrc src = {map->c};
+            const int n_chunks = (map->c.pool_cap + 63) / 64, want = (n_chunks + RENDER_THREADS / 64 - 1) / (RENDER_THREADS / 64);
+            const dim3 grid((unsigned)std::max(1, std::min(want, RENDER_MAX_BLOCKS)), (unsigned)nf);
+            if (r->early_reject) k_render_splat<MapSrc, true><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+            else k_render_splat<MapSrc, false><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+        }
+        if (r->ov_n > 0) {
+            OverlaySrc src = {r->d_ov_xyz, r->d_ov_rgba, (int)r->ov_n, r->ov_px};
+            const int want = (int)((r->ov_n + RENDER_THREADS - 1) / RENDER_THREADS);
+            const dim3 grid((unsigned)std::min(want, RENDER_MAX_BLOCKS), (unsigned)nf);
+            if (r->early_reject) k_render_splat<OverlaySrc, true><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+            else k_render_splat<OverlaySrc, false><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+        }
+        ResolveArgs ra = {};
+        ra.width = cfg.width; ra.height = cfg.height; ra.n_frames = nf; ra.background = cfg.background_rgba;
+        ra.edl_strength = cfg.edl_strength; ra.edl_radius = cfg.edl_radius_px;
+        ra.keys = r->d_keys; ra.rgba = r->d_rgba; ra.depth = depth_out ? r->d_depth : nullptr;
+        k_render_resolve<<<(unsigned)(((size_t)nf * px + RENDER_THREADS - 1) / RENDER_THREADS), RENDER_THREADS, 0, s>>>(ra);
+        HIPCHK(hipEventRecord(e1, s));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rgba_out + (size_t)f0 * px, r->d_rgba, (size_t)nf * px * 4, hipMemcpyDeviceToHost, s));
+        if (depth_out) HIPCHK(hipMemcpyAsync(depth_out + (size_t)f0 * px, r->d_depth, (size_t)nf * px * 4, hipMemcpyDeviceToHost, s));
+        if (keys_out) HIPCHK(hipMemcpyAsync(keys_out + (size_t)f0 * px, r->d_keys, (size_t)nf * px * 8, hipMemcpyDeviceToHost, s));
+        if (in_view_out) HIPCHK(hipMemcpyAsync(in_view_out + f0, r->d_in_view, (size_t)nf * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        ms_total += ms;
+    }
+    if (device_ms) *device_ms = ms_total;
     return PTL_OK;
 }
 

@@ -1,17 +1,21 @@
 """The compute half of the reference's map fly-by (src/ptudes/fly.py:75-111, src/ptudes/cli/flyby.py): scans that
 carry one pose per column are de-warped into the world frame and accumulated into a point map.  The reference hands
-both to ouster-sdk's `ScansAccumulator` and draws the result (the viewer is out of scope here); this module keeps the
+both to ouster-sdk's `ScansAccumulator` and draws the result in a window (out of scope here); this module keeps the
 arithmetic: column poses from a time-stamped trajectory (`utils.TrajectoryEvaluator`, `utils.pose_scans_from_nc_gt`),
 `client.dewarp` on the GPU (`ptl_lut_dewarp`), and the map as the voxel-hash map of the registration path
 (`ptl_icp_map_add`: a voxel keeps its first points, deterministic) instead of ScansAccumulator's random subsample.
 With a `core.Traj` the three steps run fused on the device (`ptl_icp_map_add_posed_range`), and `add_run` builds the map of a
-runner's resident sweeps without moving them (`ptl_*_map_build`); DESIGN.md 3.14."""
+runner's resident sweeps without moving them (`ptl_*_map_build`); DESIGN.md 3.14.
+The camera path of the reference (fly.py:14-233) is here too, against the package's own `Camera` instead of the viewer's, and `FlyBy` draws
+its frames on the device through `core.Renderer`; DESIGN.md 3.21."""
 from dataclasses import dataclass, field
+from enum import Enum
 from typing import Optional
 
 import numpy as np
 
 from . import core
+from .utils import estimate_apex_dolly, exp_pose6, log_pose, prune_trajectory
 
 
 @dataclass
@@ -93,6 +97,270 @@ class MapAccumulator:
     def score(self, radius=None, min_neighbours=5, sigma_floor=None, per_point=False):
         """sharpness of the accumulated map without ground truth: core.Icp.map_score of the map handle"""
         return self._icp.map_score(radius=radius, min_neighbours=min_neighbours, sigma_floor=sigma_floor, per_point=per_point)
+
+
+# ------------------------------------------------------------------------------------------------ the camera path (DESIGN.md 3.21)
+class FlyingState(Enum):
+    """Camera movement states (reference fly.py:19-24)"""
+    BUILDING = 0
+    TO_THE_BEGINNING = 1
+    COURSING = 2
+    TO_THE_APEX = 3
+
+
+def update_min_max(cmm: np.ndarray, new_point: np.ndarray):
+    cmm[:, 0] = np.minimum(cmm[:, 0], new_point)
+    cmm[:, 1] = np.maximum(cmm[:, 1], new_point)
+
+
+def _rot_z(deg):
+    c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+    return np.array([[c, -s, 0.0, 0.0], [s, c, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+
+
+def _rot_x(deg):
+    c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+    return np.array([[1.0, 0.0, 0.0, 0.0], [0.0, c, -s, 0.0], [0.0, s, c, 0.0], [0.0, 0.0, 0.0, 1.0]])
+
+
+_LOOK_DOWN = np.diag([1.0, -1.0, -1.0, 1.0])  # target frame (z up) -> camera frame (+x right, +y down, +z forward) of a camera that looks straight down
+
+
+@dataclass
+class Camera:
+    """The viewer camera the reference drives (ouster-sdk's viz.Camera through PointViz; third party), restated: it orbits the origin of the
+    `target` frame.  target: 4x4, what the reference passes to set_target (the inverse of the pose looked at); yaw, pitch in degrees
+    (pitch 0 looks straight down, -90 along the horizon); dolly: the view distance is 50 exp(dolly / 100); fov: vertical, degrees.
+    The defaults are those of the reference's make_point_viz."""
+    target: np.ndarray = field(default_factory=lambda: np.eye(4))
+    yaw: float = 140.0
+    pitch: float = 0.0
+    dolly: float = -100.0
+    fov: float = 90.0
+    near: float = 0.1
+    far: float = 1.0e4
+
+    def view_distance(self) -> float:
+        """inverts utils.estimate_apex_dolly: dolly = 100 ln(D / 50)"""
+        return 50.0 * float(np.exp(self.dolly / 100.0))
+
+    def view_matrix(self) -> np.ndarray:
+        """world -> camera, 4x4: dolly translation . pitch . yaw . target"""
+        dolly = np.eye(4)
+        dolly[2, 3] = self.view_distance()
+        return dolly @ _rot_x(self.pitch) @ _LOOK_DOWN @ _rot_z(self.yaw) @ np.asarray(self.target, dtype=np.float64)
+
+    def cam(self, width: int, height: int):
+        """the _lib.RenderCam of a width x height frame: fx = fy = (height / 2) / tan(fov / 2), principal point at the image centre"""
+        from . import _lib
+        c = _lib.RenderCam()
+        c.view[:] = list(self.view_matrix()[:3, :].reshape(12))
+        f = (height / 2.0) / np.tan(np.radians(self.fov) / 2.0)
+        c.fx, c.fy, c.cx, c.cy, c.near_m, c.far_m = f, f, width / 2.0, height / 2.0, self.near, self.far
+        return c
+
+
+class FState:
+    """Flyby states handler (reference fly.py:27-36); `update` progresses the state against a `Camera` and returns the next on transition"""
+
+    def __init__(self, name: str) -> None:
+        self.name = name
+
+    def update(self, dt: float, cam: Camera):
+        raise NotImplementedError
+
+
+class BuildingState(FState):
+    """The camera half of the reference's BuildingState (fly.py:95-106): the caller adds the scan to the map, this moves the camera along"""
+
+    def __init__(self, min_max: Optional[np.ndarray] = None, next_state: Optional[FlyingState] = None) -> None:
+        super().__init__("BUILDING")
+        self._min_max = np.zeros((3, 2)) if min_max is None else min_max
+        assert self._min_max.shape == (3, 2)
+        self._next_state = next_state
+
+    def update_camera(self, cam: Camera, first_column_pose: np.ndarray) -> None:
+        scan_pose = np.array(first_column_pose, dtype=np.float64)
+        scan_pose[:3, :3] = np.eye(3)
+        cam.target = np.linalg.inv(scan_pose)
+        update_min_max(self._min_max, scan_pose[:3, 3])
+        dolly = estimate_apex_dolly(self._min_max, cam.fov)
+        cam.dolly = cam.dolly + 0.05 * (dolly - cam.dolly)
+
+    def update(self, dt: float, cam: Camera):
+        return self._next_state
+
+
+class CameraTransitionState(FState):
+    """Transition camera to the target and/or pitch/dolly/yaw (reference fly.py:140-193)"""
+
+    def __init__(self, name: str = "", target: Optional[np.ndarray] = None, pitch: Optional[float] = -70, dolly: Optional[float] = -70,
+                 yaw: Optional[float] = 120, velocity: float = 1.0, next_state: Optional[FlyingState] = None) -> None:
+        super().__init__(name)
+        self._target = target
+        self._pitch = pitch
+        self._dolly = dolly
+        self._yaw = yaw
+        self._next_state = next_state
+        self._t = 0
+        self._v = velocity
+
+    def update(self, dt: float, cam: Camera):
+        curr_pitch, curr_dolly, curr_yaw = cam.pitch, cam.dolly, cam.yaw
+        dt = self._v * dt
+        if self._t + dt >= 1.0:
+            return self._next_state
+        if self._target is not None:
+            curr_target = np.asarray(cam.target, dtype=np.float64)
+            pose_d = log_pose(curr_target @ self._target)
+            new_target = np.linalg.inv(curr_target) @ exp_pose6(dt / (1 - self._t) * pose_d)
+            cam.target = np.linalg.inv(new_target)
+        if self._pitch is not None:
+            cam.pitch = curr_pitch + dt / (1 - self._t) * (self._pitch - curr_pitch)
+        if self._dolly is not None:
+            cam.dolly = curr_dolly + dt / (1 - self._t) * (self._dolly - curr_dolly)
+        if self._yaw is not None:
+            cam.yaw = curr_yaw + dt / (1 - self._t) * (self._yaw - curr_yaw)
+        self._t += dt
+        return None
+
+
+class CoursingState(FState):
+    """Follow the scans poses, i.e. set target along the traj eval poses (reference fly.py:196-233).  traj_eval: anything with `start_time`,
+    `end_time` and `pose_at(t)` (utils.TrajectoryEvaluator)"""
+
+    def __init__(self, traj_eval, start_time: Optional[float] = None, end_time: Optional[float] = None, velocity: float = 1.0,
+                 min_duration: float = 3.0, next_state: Optional[FlyingState] = None) -> None:
+        super().__init__("COURSING")
+        self._start_t = traj_eval.start_time if start_time is None else start_time
+        self._end_t = traj_eval.end_time if end_time is None else end_time
+        self._traj_eval = traj_eval
+        self._v = velocity
+        # slowing down velocity so we have at least min_duration coursing time
+        if self._v > 0 and self._end_t - self._start_t > 0 and (self._end_t - self._start_t) / self._v < min_duration:
+            self._v = (self._end_t - self._start_t) / min_duration
+        self._next_state = next_state
+        self._t = self._start_t
+
+    def update(self, dt: float, cam: Camera):
+        dt = self._v * dt
+        if self._t + dt > self._end_t:
+            return self._next_state
+        cam.target = np.linalg.inv(self._traj_eval.pose_at(self._t))
+        self._t += dt
+        return None
+
+
+BUILDING_Z_SPAN = 10.0  # metres either side of the sensor's height: the palette range of the frames drawn while the map is still growing
+TRACK_RGBA = (255, 255, 255, 255)
+
+
+class FlyBy:
+    """The reference's fly-by (cli/flyby.py:160-236) without a window: BUILDING (one frame per scan added, from the map so far), TO_THE_BEGINNING,
+    COURSING, TO_THE_APEX, then it stops (the reference loops for ever).  acc: the MapAccumulator the scans go into; renderer: a core.Renderer;
+    poses: [(ts, 4x4)] the trajectory the scans are posed on (as `flyby` shifts it); dt = rate / fps per frame (the reference ticks at 0.0333 s).
+    z_range: fixed palette range, or None = the sensor's height +- BUILDING_Z_SPAN while building and the map's own z extent afterwards.
+    `frames(scans)` yields (state name, (H, W, 4) uint8) frame by frame; the trajectory's positions are the overlay."""
+
+    def __init__(self, acc, renderer, poses, fps: float = 30, rate: float = 1.0, time_bounds: float = 1.5, z_range=None,
+                 max_frames: Optional[int] = None, track_px: int = 3, on_state=None):
+        self.acc, self.renderer, self.poses = acc, renderer, list(poses)
+        self.dt = float(rate) / float(fps)
+        self.time_bounds, self.z_range, self.max_frames, self.track_px = float(time_bounds), z_range, max_frames, int(track_px)
+        self.camera = Camera()
+        self.min_max = np.zeros((3, 2))
+        self.res_poses = []
+        self.on_state = on_state
+        self.state_name = "BUILDING"
+        self.n_frames = 0
+
+    def _create_state(self, flying_state):
+        cam = self.camera
+        if flying_state == FlyingState.TO_THE_BEGINNING:
+            return CameraTransitionState(name="TO_THE_BEGINNING", target=self.res_poses[0][1], velocity=0.15, next_state=FlyingState.COURSING)
+        if flying_state == FlyingState.COURSING:
+            from .utils import TrajectoryEvaluator
+            pruned = prune_trajectory(self.res_poses)
+            return CoursingState(TrajectoryEvaluator(pruned, time_bounds=1.0, device_id=self.renderer.device_id), velocity=5.0,
+                                 next_state=FlyingState.TO_THE_APEX)
+        if flying_state == FlyingState.TO_THE_APEX:
+            dolly = estimate_apex_dolly(self.min_max, cam.fov)
+            return CameraTransitionState(name="TO_THE_APEX", pitch=0, yaw=140, dolly=dolly, velocity=0.15,
+                                         next_state=FlyingState.TO_THE_BEGINNING)
+        raise ValueError(flying_state)
+
+    def _enter(self, name):
+        self.state_name = name
+        if self.on_state is not None:
+            self.on_state(name)
+
+    def _full(self):
+        return self.max_frames is not None and self.n_frames >= self.max_frames
+
+    def frames(self, scans, traj=None):
+        """scans: PosedScan-likes in order; traj: a core.Traj of `poses` for the fused map update (made here when None)"""
+        from .utils import TrajectoryEvaluator
+        r, W, H = self.renderer, self.renderer.width, self.renderer.height
+        own_traj = traj is None
+        if own_traj:
+            traj = core.Traj([t for t, _ in self.poses], [p for _, p in self.poses], self.time_bounds, self.time_bounds, device_id=r.device_id)
+        ev = TrajectoryEvaluator(self.poses, time_bounds=self.time_bounds, device_id=r.device_id)
+        building = BuildingState(min_max=self.min_max, next_state=FlyingState.TO_THE_BEGINNING)
+        self._enter(building.name)
+        try:
+            for scan in scans:
+                before = self.acc.skipped
+                self.acc.update(scan, traj=traj)
+                if self.acc.skipped != before or self._full():  # (max_frames ends the frames, not the map)
+                    continue
+                ts = np.asarray(scan.timestamp, dtype=np.float64) * 1e-9
+                ends = ev.poses_at([ts[0], ts[-1]])
+                self.res_poses.append((float(ts[-1]), ends[1]))
+                building.update_camera(self.camera, ends[0])
+                if self.z_range is None:
+                    h = float(ends[0][2, 3])
+                    r.set_z_range(h - BUILDING_Z_SPAN, h + BUILDING_Z_SPAN)
+                else:
+                    r.set_z_range(*self.z_range)
+                r.set_overlay(np.array([p[:3, 3] for _, p in self.res_poses]), TRACK_RGBA, self.track_px)
+                rgba = r.render(self.acc.icp, [self.camera.cam(W, H)])[0]
+                self.n_frames += 1
+                yield self.state_name, rgba[0]
+        finally:
+            if own_traj:
+                traj.close()
+        if not self.res_poses or self._full():
+            return
+        if self.z_range is None:
+            z = self.acc.map_points()[:, 2]
+            lo, hi = (float(z.min()), float(z.max())) if len(z) else (0.0, 1.0)
+            r.set_z_range(lo, hi if hi > lo else lo + 1.0)
+        state = self._create_state(building.update(self.dt, self.camera))
+        self._enter(state.name)
+        batch = int(r.cfg.max_frames_per_call)
+        cams = []
+        while not self._full():
+            nxt = state.update(self.dt, self.camera)
+            if nxt is not None:
+                # the frames of the state that ends are drawn before the next state is announced
+                yield from self._flush(cams)
+                if state.name == "TO_THE_APEX":
+                    break  # (the reference goes back to the beginning and loops for ever)
+                state = self._create_state(nxt)
+                self._enter(state.name)
+                continue
+            cams.append(self.camera.cam(W, H))
+            self.n_frames += 1
+            if len(cams) >= batch:
+                yield from self._flush(cams)
+        yield from self._flush(cams)
+
+    def _flush(self, cams):
+        if cams:
+            rgba = self.renderer.render(self.acc.icp, cams)[0]
+            del cams[:]
+            for f in rgba:
+                yield self.state_name, f
 
 
 def synthetic_range_scans(seq, first=0, last=None):

@@ -192,6 +192,14 @@ class TrajectoryEvaluator:
         self._bounds = (float(time_bounds), float(time_bounds)) if np.isscalar(time_bounds) else tuple(map(float, time_bounds))
         self._device_id = device_id
 
+    @property
+    def start_time(self) -> float:
+        return float(self._ts[0])
+
+    @property
+    def end_time(self) -> float:
+        return float(self._ts[-1])
+
     def poses_at(self, ts) -> np.ndarray:
         from . import core
         ts = np.atleast_1d(np.asarray(ts, dtype=np.float64))
@@ -306,6 +314,136 @@ def load_map_ply(path: str, scalars: bool = False):
     pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
     extras = (rec["neighbours"].astype(np.int32), rec["plane_var"].astype(np.float64), rec["entropy"].astype(np.float64))
     return (pts, extras) if scalars else pts
+
+
+def log_pose(pose: np.ndarray) -> np.ndarray:
+    """SE(3) logarithm of a 4x4 pose as (rotation vector (3), translation part (3)) - the order of ouster-sdk's pose_util.log_pose, which
+    the reference's camera path uses (fly.py:172, utils.py:143)"""
+    T = np.asarray(pose, dtype=np.float64)
+    w = Rotation.from_matrix(T[:3, :3]).as_rotvec()
+    th = float(np.linalg.norm(w))
+    W = vee(w)
+    if th < 1e-8:
+        Vinv = np.eye(3) - 0.5 * W + (W @ W) / 12.0
+    else:
+        Vinv = np.eye(3) - 0.5 * W + (1.0 / th ** 2 - (1.0 + np.cos(th)) / (2.0 * th * np.sin(th))) * (W @ W)
+    return np.concatenate([w, Vinv @ T[:3, 3]])
+
+
+def exp_pose6(xi: np.ndarray) -> np.ndarray:
+    """SE(3) exponential of (rotation vector (3), translation part (3)): the inverse of `log_pose`"""
+    xi = np.asarray(xi, dtype=np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    th = float(np.linalg.norm(w))
+    W = vee(w)
+    if th < 1e-8:
+        V = np.eye(3) + 0.5 * W + (W @ W) / 6.0
+    else:
+        V = np.eye(3) + (1.0 - np.cos(th)) / th ** 2 * W + (th - np.sin(th)) / th ** 3 * (W @ W)
+    T = np.eye(4)
+    T[:3, :3] = Rotation.from_rotvec(w).as_matrix()
+    T[:3, 3] = V @ v
+    return T
+
+
+def estimate_apex_dolly(min_max: np.ndarray, fov_deg: float) -> float:
+    """The dolly at which the box between min_max[:, 0] and min_max[:, 1] fits the view (reference utils.py:107-111):
+    D = 1.4142 d / sin(fov), dolly = max(-100, 100 ln(max(0.001, D) / 50))"""
+    mm = np.asarray(min_max, dtype=np.float64)
+    d = np.linalg.norm(mm[:, 1] - mm[:, 0])
+    D = 1.4142 * d / np.sin(fov_deg * np.pi / 180)
+    return float(max(-100, 100 * np.log(max(0.001, D) / 50.0)))
+
+
+def prune_trajectory_indices(traj_poses, min_dist_m=5, min_dist_angle=5, start_idx=None, end_idx=None) -> List[int]:
+    """indices of the knots `prune_trajectory` keeps (reference utils.py:122-153): the first, every one more than min_dist_m metres or
+    min_dist_angle degrees (SE(3) logarithm) from the last kept one, the last in any case; a single knot gets its successor"""
+    start_idx = 0 if start_idx is None else start_idx
+    end_idx = len(traj_poses) - 1 if end_idx is None else end_idx
+    assert start_idx <= end_idx, f"{start_idx = } should be lte {end_idx = }"
+    assert start_idx < len(traj_poses) and end_idx < len(traj_poses), \
+        f"{start_idx = } and {end_idx = } should be lt {len(traj_poses) = }"
+    kept = [start_idx]
+    last_pose_inv = np.linalg.inv(traj_poses[start_idx][1])
+    for idx in range(start_idx + 1, end_idx + 1):
+        p = traj_poses[idx][1]
+        pd = log_pose(last_pose_inv @ p)
+        pda, pdm = np.linalg.norm(pd[:3]), np.linalg.norm(pd[3:])
+        if pda > min_dist_angle * np.pi / 180 or pdm > min_dist_m or idx == end_idx:
+            kept.append(idx)
+            last_pose_inv = np.linalg.inv(p)
+    if len(kept) < 2 and end_idx + 1 < len(traj_poses):
+        kept.append(end_idx + 1)
+    return kept
+
+
+def make_kiss_traj_poses(poses) -> List[Tuple[float, np.ndarray]]:
+    """[(ts, pose)] with knot i at i + 0.5: the unit-spaced timestamps the reference's pruned camera trajectory gets from ouster-sdk's
+    pose_util.make_kiss_traj_poses (third party; the offset only shifts the coursing clock, CoursingState walks first to last knot)"""
+    return [(i + 0.5, np.asarray(p, dtype=np.float64)) for i, p in enumerate(poses)]
+
+
+def prune_trajectory(traj_poses, min_dist_m=5, min_dist_angle=5, start_idx=None, end_idx=None) -> List[Tuple[float, np.ndarray]]:
+    """Pruned poses without the knots close to each other, re-timed one per unit (reference utils.py:122-154)"""
+    kept = prune_trajectory_indices(traj_poses, min_dist_m, min_dist_angle, start_idx, end_idx)
+    return make_kiss_traj_poses([traj_poses[i][1] for i in kept])
+
+
+_PNG_SIG = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(tag: bytes, data: bytes) -> bytes:
+    import struct
+    import zlib
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def save_png(path: str, rgba) -> None:
+    """An (H, W, 4) uint8 frame as a PNG: 8-bit RGBA, no interlace, every scan line with filter 0 - standard library only"""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("save_png: need an (H, W, 4) uint8 frame")
+    h, w = a.shape[:2]
+    raw = np.zeros((h, 1 + 4 * w), dtype=np.uint8)
+    raw[:, 1:] = a.reshape(h, 4 * w)
+    with open(path, "wb") as f:
+        f.write(_PNG_SIG + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0))
+                + _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
+def load_png(path: str) -> np.ndarray:
+    """(H, W, 4) uint8 of a PNG written by `save_png` (8-bit RGBA, filter 0 on every line; anything else: ValueError)"""
+    import struct
+    import zlib
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_SIG:
+        raise ValueError(f"{path}: not a PNG file")
+    pos, hdr, idat = 8, None, b""
+    while pos + 8 <= len(data):
+        n, tag = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
+        body = data[pos + 8:pos + 8 + n]
+        if zlib.crc32(tag + body) & 0xFFFFFFFF != struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0]:
+            raise ValueError(f"{path}: chunk {tag!r} fails its CRC")
+        if tag == b"IHDR":
+            hdr = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat += body
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if hdr is None or hdr[2:] != (8, 6, 0, 0, 0):
+        raise ValueError(f"{path}: expected 8-bit RGBA without interlace, as save_png writes it")
+    w, h = hdr[0], hdr[1]
+    raw = np.frombuffer(zlib.decompress(idat), dtype=np.uint8)
+    if raw.size != h * (1 + 4 * w):
+        raise ValueError(f"{path}: {raw.size} bytes of image data, {h * (1 + 4 * w)} expected")
+    raw = raw.reshape(h, 1 + 4 * w)
+    if raw[:, 0].any():
+        raise ValueError(f"{path}: a scan line uses a filter; save_png writes filter 0 only")
+    return raw[:, 1:].reshape(h, w, 4).copy()
 
 
 def nc_gt_file_rows(t, poses) -> List[Tuple[float, np.ndarray]]:
