@@ -223,17 +223,29 @@ __device__ __forceinline__ unsigned brick_slot(unsigned long long key, unsigned 
 // (int)(x / vs) - the voxel index of VoxelHashMap / VoxelDownsample (C truncation) - without the fp64 division in the
 // common case: q = x * (1 / vs) differs from the correctly rounded quotient by a few ulp, so both truncate alike
 // unless an integer lies within 1e-9 (|q| + 1) of q; only then is the real division evaluated.
-__device__ __forceinline__ int voxel_index(double x, double vs, double inv_vs) {
-    const double q = x * inv_vs;
-    int k = (int)q;
-    if (fabs(q - rint(q)) <= 1e-9 * (fabs(q) + 1.0)) k = (int)(x / vs);
-    return k;
+// The three indices of a point together, and the divisions behind ONE branch that is uniform over the wavefront (any-lane vote over
+// the lanes that are active here): written as `if (near) k = (int)(x / vs)` the compiler turns the branch into a select - a division is
+// one cheap instruction to it until it is expanded - and every point pays three full fp64 divisions (v_div_scale x 2, the quarter-rate
+// v_rcp_f64, eight FMAs, v_div_fmas, v_div_fixup each) for a fallback that practically no lane takes.  The empty asm pins the
+// dividends inside the branch (nothing volatile is hoisted or speculated); inside it every lane divides and the lanes near an
+// integer take the quotient - the value per lane is what the select form gave, for every input.
+__device__ __forceinline__ bool voxel_index_near(double q) { return fabs(q - rint(q)) <= 1e-9 * (fabs(q) + 1.0); }
+__device__ __forceinline__ void voxel_index(V3 p, double vs, double inv_vs, int& kx, int& ky, int& kz) {
+    const double qx = p.x * inv_vs, qy = p.y * inv_vs, qz = p.z * inv_vs;
+    kx = (int)qx; ky = (int)qy; kz = (int)qz;
+    const bool nx = voxel_index_near(qx), ny = voxel_index_near(qy), nz = voxel_index_near(qz);
+    if (__any(nx || ny || nz)) {
+        asm volatile("" : "+v"(p.x), "+v"(p.y), "+v"(p.z));
+        if (nx) kx = (int)(p.x / vs);
+        if (ny) ky = (int)(p.y / vs);
+        if (nz) kz = (int)(p.z / vs);
+    }
 }
 
 // voxel index by C truncation toward zero, exactly (int)(coordinate / voxel_size)
 __device__ __forceinline__ bool vox_key(V3 p, double size, unsigned long long& key, int& kx, int& ky, int& kz) {
     const double inv = 1.0 / size;  // (loop-invariant for the callers: one division per thread, not three per point)
-    kx = voxel_index(p.x, size, inv); ky = voxel_index(p.y, size, inv); kz = voxel_index(p.z, size, inv);
+    voxel_index(p, size, inv, kx, ky, kz);
     const int ox = kx + KEY_OFF, oy = ky + KEY_OFF, oz = kz + KEY_OFF;
     const bool ok = ((unsigned)ox | (unsigned)oy | (unsigned)oz) < (1u << 21);
     key = ((unsigned long long)ox << 42) | ((unsigned long long)oy << 21) | (unsigned long long)oz;
@@ -1076,7 +1088,8 @@ template <int PC, class CT>
 __device__ __forceinline__ bool nn_search32(const CT& c, V3 s, int lane32, int gbase, V3& best, double& best_d2,
                                             int& ncand, unsigned long long& ck, int& cblk, bool use_cache, int& lastv) {
     const double inv_vs = 1.0 / c.vs;   // loop-invariant
-    const int kx = voxel_index(s.x, c.vs, inv_vs), ky = voxel_index(s.y, c.vs, inv_vs), kz = voxel_index(s.z, c.vs, inv_vs);
+    int kx, ky, kz;
+    voxel_index(s, c.vs, inv_vs, kx, ky, kz);
     const unsigned long long key = pack_key(kx, ky, kz);
     const bool hit = use_cache && key == ck;
     const int pb = hit ? cblk : nn_probe32(c, kx, ky, kz, lane32);
@@ -1847,7 +1860,8 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
     // (the lap timer runs in thread 0 of workgroup 0 of the sequences on the first teams)
     [[maybe_unused]] const bool srch_me = diag::phases && it > 0 && blockIdx.x < 8 && threadIdx.x == 0;
     [[maybe_unused]] DiagLap<diag::phases, true, true> srch(srch_me);
-    const int kx = voxel_index(s.x, c.vs, inv_vs), ky = voxel_index(s.y, c.vs, inv_vs), kz = voxel_index(s.z, c.vs, inv_vs);
+    int kx, ky, kz;
+    voxel_index(s, c.vs, inv_vs, kx, ky, kz);
     const unsigned long long key = pack_key(kx, ky, kz);
     int r[RE];
 #pragma unroll
@@ -2264,7 +2278,8 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                     miss = i;
                     if (it > 0) {
                         const unsigned long long old_key = cur.key;
-                        const int kx = voxel_index(s.x, c.vs, inv_vs), ky = voxel_index(s.y, c.vs, inv_vs), kz = voxel_index(s.z, c.vs, inv_vs);
+                        int kx, ky, kz;
+                        voxel_index(s, c.vs, inv_vs, kx, ky, kz);
                         if (old_key == pack_key(kx, ky, kz)) {
                             rebA = false;
                             double row[GN8_ANS_ROW];
@@ -2375,7 +2390,8 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                     [[maybe_unused]] double old_t[3] = {0, 0, 0}, old_sl = -1.0;
                     [[maybe_unused]] bool old_same_key = false;
                     if constexpr (diag::phases) if (wg == 0 && it > 0 && laneL == 0) {
-                        const int kx0 = voxel_index(s.x, c.vs, inv_vs), ky0 = voxel_index(s.y, c.vs, inv_vs), kz0 = voxel_index(s.z, c.vs, inv_vs);
+                        int kx0, ky0, kz0;
+                        voxel_index(s, c.vs, inv_vs, kx0, ky0, kz0);
                         old_same_key = c.pc_key[i] == pack_key(kx0, ky0, kz0);
                         old_t[0] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 3]; old_t[1] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 4]; old_t[2] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 5];
                         old_sl = c.pc_ans[GN8_ANS_ROW * (size_t)i + GN8_ANS_D];
