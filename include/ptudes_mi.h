@@ -747,6 +747,56 @@ int ptl_render_frames(ptl_render *r, ptl_icp *map, const ptl_render_cam *cams, i
  * pixel then costs an atomic */
 int ptl_render_debug_set_early_reject(ptl_render *r, int32_t on);
 
+/* ------------------------------------------------------------------------------------------------
+ * Distance of query points to the stored points of a map (no reference counterpart): the cloud-to-cloud nearest-neighbour
+ * distance with the voxel map as the search structure.  Distances are to the map AS STORED: a voxel keeps its first max_points_per_voxel points.
+ * Per query q: d2(q) = min over all stored points p of `ref` of (dx dx + dy dy) + dz dz, d = p - q, fp64 in that order without contraction;
+ * q is matched iff d2 <= max_dist max_dist (the product made once, as a double); its per-point output is d2 when matched and +inf when not.
+ * A query with a non-finite coordinate is counted in n_invalid and gets NaN; a query whose voxel index lies outside the key range is unmatched.
+ * n_within[k] counts the queries with d2 <= thresholds[k] thresholds[k].  A minimum does not depend on the order of its terms: d2, the match and
+ * every count are exact functions of the set of stored points and the query.  sum_dist (of sqrt(d2)), sum_dist2 (of d2) and max_dist2_seen run
+ * over the matched queries; the sums are reduced on the device by a fixed tree in query order (array queries: per staged chunk, the chunk
+ * sums added on the host in chunk order), so they depend on the order of the queries only up to summation order.
+ * Parameters: 0 < max_dist <= ref's voxel size (the 27-voxel search is complete then, cf. the map score's radius), 1 .. 8 thresholds, ascending
+ * (equal neighbours allowed), each in (0, max_dist].  The defaults (max_dist = voxel size, one threshold = max_dist) are a caller's choice echoed
+ * back, not tuned values. */
+#define PTL_MAP_CMP_MAX_THRESHOLDS 8
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_map_cmp_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double max_dist;
+    int32_t n_thresholds;
+    double thresholds[PTL_MAP_CMP_MAX_THRESHOLDS];
+} ptl_map_cmp_cfg;
+typedef struct {
+    int64_t n_query, n_invalid, n_matched;          /* unmatched = n_query - n_invalid - n_matched */
+    int64_t n_within[PTL_MAP_CMP_MAX_THRESHOLDS];   /* entries from n_thresholds on are 0 */
+    double sum_dist, sum_dist2, max_dist2_seen;     /* over the matched queries; 0 when there is none */
+    double max_dist;                                /* the parameters as used */
+    int32_t n_thresholds;
+    double thresholds[PTL_MAP_CMP_MAX_THRESHOLDS];
+    double device_ms;                               /* HIP-event time of the call's device work on ref's stream (0 without queries), cf. ptl_map_score_result */
+} ptl_map_cmp_result;
+/* the library's sizeof(ptl_map_cmp_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_map_cmp_sizeof_cfg(void);
+/* the defaults for a reference map of that voxel size; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch
+ * is refused with PTL_ERR_ARG and nothing is written */
+int ptl_map_cmp_default_cfg(ptl_map_cmp_cfg *cfg, double voxel_size);
+/* n queries xyz (n x 3 f64, host) against the map of `ref` (cfg nullable: the defaults).  The queries are staged and processed in chunks of a
+ * fixed size inside the call: no device buffer grows with n.  dist2_out (nullable): n doubles, the per-point outputs in query order.  Waits
+ * for the handle's map update first, only reads the map and keeps nothing in the handle.  Checked before any HIP call, refused with the numbers
+ * (PTL_ERR_ARG): null ref / result, xyz null with n > 0, n < 0, max_dist <= 0, not finite or above ref's voxel size, n_thresholds outside 1 .. 8,
+ * a threshold <= 0, above max_dist or below its predecessor.  PTL_ERR_STATE when the table leads to a block that does not hold the probed
+ * voxel.  An empty reference leaves every finite query unmatched; n = 0 gives the zero summary (with the parameters). */
+int ptl_icp_map_distance(ptl_icp *ref, const ptl_map_cmp_cfg *cfg, const double *xyz, int64_t n, ptl_map_cmp_result *result, double *dist2_out);
+/* The same with the stored points of `src` as the queries, walked on the device in pool order (block id, then slot): nothing but the summary
+ * crosses the bus.  xyz_out (3 per point) and dist2_out: both or neither; when given they receive every stored point of src with its output in
+ * that order and *n_written (nullable) their number; max_points below src's point count: PTL_ERR_CAPACITY naming the count, nothing written.
+ * ref and src must live on one device (else PTL_ERR_ARG with both ids); src == ref is allowed (every d2 is then 0).  Waits for both handles'
+ * map updates, only reads both maps. */
+int ptl_icp_map_compare(ptl_icp *ref, ptl_icp *src, const ptl_map_cmp_cfg *cfg, ptl_map_cmp_result *result, double *xyz_out, double *dist2_out,
+                        int64_t max_points, int64_t *n_written);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,18 @@ class RenderCam(C.Structure):
                 ("near_m", C.c_double), ("far_m", C.c_double)]
 
 
+class MapCmpCfg(_Cfg):
+    """ptl_map_cmp_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
+                ("thresholds", C.c_double * 8)]
+
+
+class MapCmpResult(C.Structure):
+    _fields_ = [("n_query", C.c_int64), ("n_invalid", C.c_int64), ("n_matched", C.c_int64), ("n_within", C.c_int64 * 8),
+                ("sum_dist", C.c_double), ("sum_dist2", C.c_double), ("max_dist2_seen", C.c_double), ("max_dist", C.c_double),
+                ("n_thresholds", C.c_int32), ("thresholds", C.c_double * 8), ("device_ms", C.c_double)]
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -243,6 +255,11 @@ PROTOTYPES = {
     "ptl_render_frames": (C.c_int, [_vp, _vp, C.POINTER(RenderCam), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                     C.POINTER(C.c_uint64), c_i64_p, c_d_p]),
     "ptl_render_debug_set_early_reject": (C.c_int, [_vp, C.c_int32]),
+    # distance of query points to a map's stored points (include/ptudes_mi.h)
+    "ptl_map_cmp_sizeof_cfg": (C.c_int64, []),
+    "ptl_map_cmp_default_cfg": (C.c_int, [C.POINTER(MapCmpCfg), C.c_double]),
+    "ptl_icp_map_distance": (C.c_int, [_vp, C.POINTER(MapCmpCfg), c_d_p, C.c_int64, C.POINTER(MapCmpResult), c_d_p]),
+    "ptl_icp_map_compare": (C.c_int, [_vp, _vp, C.POINTER(MapCmpCfg), C.POINTER(MapCmpResult), c_d_p, c_d_p, C.c_int64, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

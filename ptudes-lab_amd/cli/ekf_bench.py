@@ -246,11 +246,13 @@ def _bag_map(bags, info, start_scan, end_scan, knots, voxel_size=MAP_VOXEL_SIZE,
     return acc
 
 
-def _finish_map(path, map_icp, score):
+def _finish_map(path, map_icp, score, compare=None):
     """points (and, with `score` = keyword arguments of Icp.map_score, the per-point scalars) of a built map to `path` (nullable);
-    returns (voxels, points, MapScore | None)"""
+    compare (`compare_options`): the map against the reference cloud first, printed; returns (voxels, points, MapScore | None)"""
     from ..utils import save_map_ply
     voxels, _ = map_icp.map_size()
+    if compare is not None:
+        run_compare(map_icp, compare)
     ms, scalars = None, None
     if score is not None:
         ms, (pts, nb, pv, ent) = map_icp.map_score(per_point=True, **score)
@@ -266,12 +268,105 @@ def _finish_map(path, map_icp, score):
     return voxels, len(pts), ms
 
 
-def _save_run_map(path, seq, first, rows_t, rows_p, score=None):
+def _save_run_map(path, seq, first, rows_t, rows_p, score=None, compare=None):
     """... under the rows as the poses file holds them (utils.nc_gt_file_rows): what `flyby --nc-gt-poses` of that file works with"""
     from ..utils import nc_gt_file_rows
     map_icp, n_skipped = _run_map_handle(seq, first, nc_gt_file_rows(rows_t, rows_p), MAP_VOXEL_SIZE, 0)
-    voxels, points, ms = _finish_map(path, map_icp, score)
+    voxels, points, ms = _finish_map(path, map_icp, score, compare)
     return voxels, points, n_skipped, ms
+
+
+COMPARE_OPTIONS = [
+    click.option("--compare-map", required=False, type=click.Path(dir_okay=False),
+                 help="compare the map with this reference cloud (.ply as --save-map writes it, or .npy): nearest-neighbour distance in both "
+                      "directions on the GPU - accuracy (map to reference), completeness (reference to map), precision / recall / F per threshold"),
+    click.option("--compare-threshold", type=str, default=None,
+                 help="distance thresholds T1,T2,... of --compare-map, metres, ascending, at most 8 (default 0.05,0.1,0.2)"),
+    click.option("--compare-max-dist", type=float, default=None,
+                 help="largest distance at which a point of --compare-map counts as matched, metres (default and upper bound: the map's voxel size)"),
+    click.option("--compare-pose", required=False, type=click.Path(dir_okay=False),
+                 help="text file with 12 or 16 numbers, a row-major rigid transform applied to the points of --compare-map before the comparison "
+                      "(a ground-truth cloud lives in its own frame)"),
+    click.option("--save-map-error", required=False, type=click.Path(dir_okay=False),
+                 help="write the map's points with their distance to --compare-map's cloud (PLY, double `dist`, NaN = unmatched)"),
+]
+
+
+def compare_click_options(f):
+    for opt in reversed(COMPARE_OPTIONS):
+        f = opt(f)
+    return f
+
+
+def compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, voxel_size):
+    """the options of --compare-map checked before any device is touched: None without it, else a dict with the defaults filled in"""
+    import os
+    given = {"--compare-threshold": compare_threshold, "--compare-max-dist": compare_max_dist, "--compare-pose": compare_pose,
+             "--save-map-error": save_map_error}
+    if not compare_map:
+        for name, v in given.items():
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --compare-map")
+        return None
+    if not os.path.isfile(compare_map):
+        raise click.ClickException(f"--compare-map {compare_map}: no such file")
+    if not str(compare_map).endswith((".ply", ".npy")):
+        raise click.ClickException(f"--compare-map {compare_map}: expected a .ply or .npy cloud")
+    max_dist = voxel_size if compare_max_dist is None else compare_max_dist
+    if not 0.0 < max_dist <= voxel_size:
+        raise click.ClickException(f"--compare-max-dist {max_dist:g}: the 27-voxel neighbourhood search needs 0 < max dist <= the map's voxel size "
+                                   f"{voxel_size:g}")
+    try:
+        thr = [float(x) for x in (compare_threshold or "0.05,0.1,0.2").split(",")]
+    except ValueError:
+        raise click.ClickException(f"--compare-threshold {compare_threshold}: expected T1,T2,... (numbers)")
+    if not 1 <= len(thr) <= 8:
+        raise click.ClickException(f"--compare-threshold {compare_threshold}: {len(thr)} thresholds, 1 .. 8 are served")
+    for k, t in enumerate(thr):
+        if not 0.0 < t <= max_dist:
+            raise click.ClickException(f"--compare-threshold {compare_threshold}: {t:g} is outside (0, max dist = {max_dist:g}]")
+        if k and t < thr[k - 1]:
+            raise click.ClickException(f"--compare-threshold {compare_threshold}: {t:g} follows {thr[k - 1]:g}: ascending order")
+    pose = None
+    if compare_pose is not None:
+        try:
+            vals = [float(x) for x in open(compare_pose).read().replace(",", " ").split()]
+        except (OSError, ValueError) as e:
+            raise click.ClickException(f"--compare-pose {compare_pose}: {e}")
+        if len(vals) not in (12, 16) or not np.all(np.isfinite(vals)):
+            raise click.ClickException(f"--compare-pose {compare_pose}: {len(vals)} numbers; expected 12 or 16 finite ones, a row-major rigid transform")
+        if len(vals) == 16 and vals[12:] != [0.0, 0.0, 0.0, 1.0]:
+            raise click.ClickException(f"--compare-pose {compare_pose}: the last row is {vals[12:]}, a rigid transform's is 0 0 0 1")
+        pose = np.array(vals[:12], dtype=np.float64).reshape(3, 4)
+        if np.abs(pose[:, :3] @ pose[:, :3].T - np.eye(3)).max() > 1e-6:
+            raise click.ClickException(f"--compare-pose {compare_pose}: the 3 x 3 part is not a rotation (R R^T differs from 1 by more than 1e-6)")
+    return dict(path=compare_map, thresholds=thr, max_dist=max_dist, pose=pose, save_error=save_map_error)
+
+
+def load_reference(compare):
+    """the reference cloud of `compare_options`, moved by its pose: ((R0 x + R1 y) + R2 z) + t per row, in that order"""
+    from ..utils import load_map_ply
+    ref = np.ascontiguousarray(load_map_ply(compare["path"]), dtype=np.float64).reshape(-1, 3)
+    T = compare["pose"]
+    if T is not None:
+        x, y, z = ref[:, 0], ref[:, 1], ref[:, 2]
+        ref = np.stack([((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)], axis=1)
+    return ref
+
+
+def run_compare(map_icp, compare):
+    """--compare-map: the map of `map_icp` against the reference cloud, printed; --save-map-error's file.  Returns the fly.MapComparison"""
+    from .. import fly
+    from ..utils import save_map_ply
+    ref = load_reference(compare)
+    cmp_, (pts, d2) = fly.compare_handle(map_icp, ref, compare["thresholds"], compare["max_dist"], per_point=True, reference_name=compare["path"])
+    print("\n".join(cmp_.lines()))
+    if compare["save_error"]:
+        dist = np.sqrt(d2)
+        dist[~np.isfinite(d2)] = np.nan
+        save_map_ply(compare["save_error"], pts, {"dist": dist})
+        print(f"Map error saved to: {compare['save_error']}")
+    return cmp_
 
 
 def score_options(map_score, score_radius, voxel_size):
@@ -333,18 +428,22 @@ def score_options(map_score, score_radius, voxel_size):
                    "neighbourhoods) and print it; with --save-map the PLY carries the per-point values; works without --save-map too")
 @click.option("--score-radius", type=float, default=None, help="neighbourhood radius of --map-score, metres (default and upper bound: the "
                                                                "map's voxel size, 0.5)")
+@compare_click_options
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
                       kiss_max_range: float, synthetic: Optional[int], save_smoothed_poses: Optional[str] = None,
                       imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter",
-                      native_packets: bool = False, map_score: bool = False, score_radius: Optional[float] = None) -> None:
+                      native_packets: bool = False, map_score: bool = False, score_radius: Optional[float] = None,
+                      compare_map: Optional[str] = None, compare_threshold: Optional[str] = None, compare_max_dist: Optional[float] = None,
+                      compare_pose: Optional[str] = None, save_map_error: Optional[str] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
     from ..utils import TrajectoryEvaluator, active_beam_rows
     score = score_options(map_score, score_radius, MAP_VOXEL_SIZE)
-    want_map = bool(save_map) or map_score
+    compare = compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, MAP_VOXEL_SIZE)
+    want_map = bool(save_map) or map_score or compare is not None
     if want_map and map_from == "smoothed" and not save_smoothed_poses:
         raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
@@ -482,7 +581,7 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
         rows_t, rows_p = {"filter": (res_t, res_poses), "kiss": (res_t, kiss_poses),
                           "smoothed": (out.get("smoothed_t"), out.get("smoothed_poses"))}[map_from]
         if seq is not None:
-            voxels, points, n_skipped, ms = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p), score=score)
+            voxels, points, n_skipped, ms = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p), score=score, compare=compare)
             print(f"Map of scans {start_scan} - {seq.n_scans - 1} ({map_from} poses, {n_skipped} skipped): {voxels} voxels, {points} points")
         else:
             from ..utils import nc_gt_file_rows
@@ -491,7 +590,7 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             if beams:
                 print("NOTE: --beams thins the scans of the registration only; the map takes every beam of every sweep")
             acc = _bag_map(bags, info, start_scan, end_scan, nc_gt_file_rows(list(rows_t), list(rows_p)))
-            voxels, points, ms = _finish_map(save_map, acc.icp, score)
+            voxels, points, ms = _finish_map(save_map, acc.icp, score, compare)
             print(f"Map of {acc.scans} scans from {start_scan} ({map_from} poses, {acc.skipped} skipped): {voxels} voxels, {points} points")
         if ms is not None:
             print("\n".join(ms.lines()))

@@ -9,7 +9,8 @@ deterministic voxel map of the registration path (a voxel keeps its first points
 FILE (.pcap / .bag) goes through ouster-sdk when it is importable; a raw packet .bag (or a directory of bags) goes through the package's
 own packet decoder (packets.py) when it is not, or with --native-packets - every column is then posed at its decoded firing time;
 `--synthetic SEED` runs the same path on the synthetic sequence.  `--map-score` prints the sharpness of the map without ground truth
- and, with `--save-map`, adds the per-point values to the PLY.
+ and, with `--save-map`, adds the per-point values to the PLY.  `--compare-map REF` measures the map against a reference
+cloud on the GPU: accuracy, completeness, precision / recall / F per threshold.
 """
 from typing import Optional
 
@@ -17,6 +18,8 @@ import click
 import numpy as np
 
 from ..utils import read_newer_college_gt, save_map_ply
+
+from .ekf_bench import compare_click_options as _compare_click_options
 
 TIME_BOUNDS = 1.5  # seconds a column may lie outside the poses file (reference utils.py:368)
 
@@ -91,17 +94,22 @@ def frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_r
 @click.option("--z-range", type=str, default=None,
               help="heights LO,HI of the palette's ends for --save-frames (default: the map's own z extent once it is built; while it is "
                    "being built, the sensor's height +- 10 m)")
+@_compare_click_options
 def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional[str], nc_gt_poses: Optional[str], rate: float,
                  accum_map_ratio: Optional[float], start_scan: int, end_scan: Optional[int], voxel_size: float,
                  save_map: Optional[str], synthetic: Optional[int], native_packets: bool = False, map_score: bool = False,
                  score_radius: Optional[float] = None, save_frames: Optional[str] = None, frame_size: Optional[str] = None,
                  fps: Optional[float] = None, max_frames: Optional[int] = None, point_size: Optional[int] = None,
-                 edl: Optional[float] = None, z_range: Optional[str] = None) -> None:
+                 edl: Optional[float] = None, z_range: Optional[str] = None, compare_map: Optional[str] = None,
+                 compare_threshold: Optional[str] = None, compare_max_dist: Optional[float] = None, compare_pose: Optional[str] = None,
+                 save_map_error: Optional[str] = None) -> None:
     """Map of the lidar scans with poses (the flyby visualizer's map, headless).
 
     Data is provided via FILE in Ouster raw packets formats (PCAP or BAG with lidar/imu packets), or --synthetic SEED.
     """
     frames = frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_range)
+    from .ekf_bench import compare_options, run_compare
+    compare = compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, voxel_size)
     if kitti_poses:
         raise click.ClickException("--kitti-poses is not supported here: the column timing of one-pose-per-scan files is defined inside "
                                    "ouster-sdk's pose_scans_from_kitti, which this build cannot read; use --nc-gt-poses")
@@ -219,6 +227,8 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
     print(f"map of scans: {start_scan} - {end_scan}")
     print(f"map num points: {points}")
     print(f"map voxels: {voxels} (voxel size {voxel_size})")
+    if compare is not None:
+        run_compare(acc.icp, compare)
     scalars = None
     if score is not None:
         ms, (pts, nb, pv, ent) = acc.score(per_point=True, **score)

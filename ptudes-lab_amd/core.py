@@ -58,6 +58,74 @@ class MapScore:
                 f"  mean map entropy: {self.mean_entropy:.6f}"]
 
 
+@dataclass
+class MapDistance:
+    """Summary of `Icp.map_distance` / `Icp.map_compare` (include/ptudes_mi.h ptl_map_cmp_result): the queries' nearest-neighbour distances
+    to a reference map's stored points - counts (exact), the sums over the matched queries, the parameters as used and the HIP-event time"""
+    n_query: int
+    n_invalid: int
+    n_matched: int
+    n_within: tuple        # one count per threshold: queries with d2 <= threshold^2
+    sum_dist: float
+    sum_dist2: float
+    max_dist2_seen: float
+    max_dist: float
+    thresholds: tuple
+    device_ms: float
+
+    @property
+    def mean_dist(self):
+        """mean distance of the matched queries, metres (0 when there is none)"""
+        return self.sum_dist / self.n_matched if self.n_matched else 0.0
+
+    @property
+    def rms_dist(self):
+        return float(np.sqrt(self.sum_dist2 / self.n_matched)) if self.n_matched else 0.0
+
+    @property
+    def fractions(self):
+        """n_within / n_query per threshold (0 without queries): precision of a map against a reference, recall the other way round"""
+        return tuple(w / self.n_query if self.n_query else 0.0 for w in self.n_within)
+
+    @classmethod
+    def _from(cls, res):
+        k = int(res.n_thresholds)
+        return cls(int(res.n_query), int(res.n_invalid), int(res.n_matched), tuple(int(x) for x in res.n_within[:k]), float(res.sum_dist),
+                   float(res.sum_dist2), float(res.max_dist2_seen), float(res.max_dist), tuple(float(x) for x in res.thresholds[:k]),
+                   float(res.device_ms))
+
+
+def map_cmp_cfg(voxel_size, max_dist=None, thresholds=None):
+    """the _lib.MapCmpCfg of a reference map of that voxel size: max_dist defaults to the voxel size, thresholds to (max_dist,)"""
+    cfg = L.MapCmpCfg()
+    L.check(L.lib().ptl_map_cmp_default_cfg(C.byref(cfg), float(voxel_size)))
+    if max_dist is not None:
+        cfg.max_dist = float(max_dist)
+    thr = [cfg.max_dist] if thresholds is None else [float(t) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1)]
+    cfg.n_thresholds = len(thr)  # (a count outside 1 .. 8 is the library's to refuse, with the number)
+    for k, t in enumerate(thr[:8]):
+        cfg.thresholds[k] = t
+    return cfg
+
+
+def map_from_points(points, voxel_size=0.5, max_points_per_voxel=20, device_id=0, max_points_per_scan=1 << 20, **over):
+    """an `Icp` whose voxel map holds `points` (N, 3), added in chunks of at most its max_points_per_scan in array order (a voxel keeps its
+    first max_points_per_voxel points): a reference map for `Icp.map_distance` / `Icp.map_compare` out of a bare cloud"""
+    pts = L.as_f64(points).reshape(-1, 3)
+    over.setdefault("map_block_capacity", 1 << 21)  # (fly.MapAccumulator's)
+    over.setdefault("map_table_capacity", 1 << 23)
+    icp = Icp(1.0e9, 0.0, voxel_size=voxel_size, max_points_per_voxel=max_points_per_voxel, device_id=device_id,
+              max_points_per_scan=int(max_points_per_scan), **over)
+    try:
+        step = int(icp.cfg.max_points_per_scan)
+        for off in range(0, len(pts), step):
+            icp.map_add(pts[off:off + step])
+    except Exception:
+        icp.close()
+        raise
+    return icp
+
+
 def _diag(icp_handle):
     """{name: value} of the named slots a diagnostic build collects for one registration handle (csrc/diag.h; all 0 in the product build),
     cumulative since its cold start; the names are the library's own (include/ptudes_mi.h ptl_icp_diag)"""
@@ -176,6 +244,32 @@ class Icp:
                                           L.dptr(ent), p, C.byref(w)))
         k = w.value
         return MapScore(*(getattr(res, f) for f, _ in res._fields_)), (xyz[:k], n[:k], pv[:k], ent[:k])
+
+    def map_distance(self, points, max_dist=None, thresholds=None, per_point=False):
+        """nearest-neighbour distance of `points` (N, 3) to this map's stored points (include/ptudes_mi.h ptl_icp_map_distance, DESIGN.md
+        3.23): a `MapDistance`; with per_point also d2 (N,) in query order - the squared distance of a matched query, +inf for an unmatched
+        one, NaN for a non-finite one.  max_dist defaults to the voxel size (its upper bound), thresholds to (max_dist,)"""
+        cfg = map_cmp_cfg(self.cfg.voxel_size, max_dist, thresholds)
+        q = L.as_f64(points).reshape(-1, 3)
+        res = L.MapCmpResult()
+        d2 = np.empty(len(q)) if per_point else None
+        L.check(L.lib().ptl_icp_map_distance(self._h, C.byref(cfg), L.dptr(q) if len(q) else None, len(q), C.byref(res),
+                                             None if d2 is None else L.dptr(d2)))
+        return (MapDistance._from(res), d2) if per_point else MapDistance._from(res)
+
+    def map_compare(self, src_icp, max_dist=None, thresholds=None, per_point=False):
+        """the same with the stored points of `src_icp`'s map as the queries, walked on the device: nothing but the summary crosses the bus
+        (ptl_icp_map_compare).  With per_point also (xyz (N, 3), d2 (N,)) of src's stored points in its pool order"""
+        cfg = map_cmp_cfg(self.cfg.voxel_size, max_dist, thresholds)
+        res = L.MapCmpResult()
+        if not per_point:
+            L.check(L.lib().ptl_icp_map_compare(self._h, src_icp._h, C.byref(cfg), C.byref(res), None, None, 0, None))
+            return MapDistance._from(res)
+        _, p = src_icp.map_size()
+        xyz, d2 = np.empty((max(p, 1), 3)), np.empty(max(p, 1))
+        w = C.c_int64()
+        L.check(L.lib().ptl_icp_map_compare(self._h, src_icp._h, C.byref(cfg), C.byref(res), L.dptr(xyz), L.dptr(d2), p, C.byref(w)))
+        return MapDistance._from(res), (xyz[:w.value], d2[:w.value])
 
     def _cloud(self, fn):
         cap = int(self.cfg.max_points_per_scan)

@@ -10,6 +10,7 @@
 #include "packet_kernels.h"
 #include "score_kernels.h"
 #include "render_kernels.h"
+#include "compare_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -3065,6 +3066,180 @@ extern "C" int ptl_icp_map_score(ptl_icp* map, const ptl_map_score_cfg* cfg, ptl
         HIPCHK(hipMemcpy(n_out, d_nb, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(plane_var_out, d_pv, (size_t)n * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(entropy_out, d_ent, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (n_written) *n_written = n;
+    }
+    return PTL_OK;
+}
+
+// ================================================================================================ map distance
+// The definition is in include/ptudes_mi.h, the kernels in compare_kernels.h.  Everything is checked on the host before the first HIP call; the
+// work buffers (one staged chunk of queries or the chunk prefix of the source map, the per-query values, the summaries) live for the call.
+static void map_cmp_defaults(ptl_map_cmp_cfg* cfg, double voxel_size) {
+    PTL_CFG_INIT(cfg);
+    cfg->max_dist = voxel_size;
+    cfg->n_thresholds = 1;
+    cfg->thresholds[0] = voxel_size;
+}
+extern "C" int64_t ptl_map_cmp_sizeof_cfg(void) { return (int64_t)sizeof(ptl_map_cmp_cfg); }
+extern "C" int ptl_map_cmp_default_cfg(ptl_map_cmp_cfg* cfg, double voxel_size) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_map_cmp_cfg, cfg);
+    if (!(voxel_size > 0.0) || !(voxel_size < 1.0e150)) return set_err(PTL_ERR_ARG, "voxel_size must be positive and finite (got %g)", voxel_size);
+    map_cmp_defaults(cfg, voxel_size);
+    return PTL_OK;
+}
+static_assert(PTL_MAP_CMP_MAX_THRESHOLDS == CMP_MAX_THR, "the header's threshold count is the kernels'");
+// the configuration as used (cfg nullable: the defaults of ref's voxel size), checked; fills the kernel arguments' parameter half and the result's echo
+static int map_cmp_setup(const char* who, ptl_icp* ref, const ptl_map_cmp_cfg* cfg, ptl_map_cmp_result* result, CmpArgs* a) {
+    ptl_map_cmp_cfg use;
+    if (cfg) { ABI_CHECK(ptl_map_cmp_cfg, cfg); use = *cfg; } else map_cmp_defaults(&use, ref->cfg.voxel_size);
+    const double vs = ref->cfg.voxel_size;
+    if (!(use.max_dist > 0.0) || !(use.max_dist <= vs))
+        return set_err(PTL_ERR_ARG, "%s: max_dist = %g: the 27-voxel search needs 0 < max_dist <= the reference map's voxel size = %g", who, use.max_dist, vs);
+    if (use.n_thresholds < 1 || use.n_thresholds > CMP_MAX_THR)
+        return set_err(PTL_ERR_ARG, "%s: n_thresholds = %d: must be in [1, %d]", who, use.n_thresholds, CMP_MAX_THR);
+    for (int k = 0; k < use.n_thresholds; ++k) {
+        const double t = use.thresholds[k];
+        if (!(t > 0.0) || !(t <= use.max_dist))
+            return set_err(PTL_ERR_ARG, "%s: threshold %d = %g: must be in (0, max_dist = %g]", who, k, t, use.max_dist);
+        if (k > 0 && t < use.thresholds[k - 1])
+            return set_err(PTL_ERR_ARG, "%s: threshold %d = %g is below threshold %d = %g: ascending order", who, k, t, k - 1, use.thresholds[k - 1]);
+    }
+    memset(result, 0, sizeof *result);
+    memset(a, 0, sizeof *a);
+    result->max_dist = a->max_dist = use.max_dist;
+    a->max2 = use.max_dist * use.max_dist;
+    result->n_thresholds = a->n_thr = use.n_thresholds;
+    for (int k = 0; k < use.n_thresholds; ++k) { result->thresholds[k] = use.thresholds[k]; a->thr2[k] = use.thresholds[k] * use.thresholds[k]; }
+    return PTL_OK;
+}
+// one reduced summary (k_cmp_reduce) into the result; the sums in the order the summaries are handed in
+static void map_cmp_add(ptl_map_cmp_result* r, const double* sums) {
+    r->n_invalid += (int64_t)sums[0];
+    r->n_matched += (int64_t)sums[1];
+    r->sum_dist += sums[2];
+    r->sum_dist2 += sums[3];
+    if (sums[4] > r->max_dist2_seen) r->max_dist2_seen = sums[4];
+    for (int k = 0; k < r->n_thresholds; ++k) r->n_within[k] += (int64_t)sums[5 + k];
+}
+extern "C" int ptl_icp_map_distance(ptl_icp* ref, const ptl_map_cmp_cfg* cfg, const double* xyz, int64_t n, ptl_map_cmp_result* result, double* dist2_out) {
+    if (!ref || !result) return set_err(PTL_ERR_ARG, "ptl_icp_map_distance: null argument");
+    if (n < 0) return set_err(PTL_ERR_ARG, "ptl_icp_map_distance: n = %lld: must not be negative", (long long)n);
+    if (n > 0 && !xyz) return set_err(PTL_ERR_ARG, "ptl_icp_map_distance: %lld queries without xyz", (long long)n);
+    CmpArgs a;
+    { int rc = map_cmp_setup("ptl_icp_map_distance", ref, cfg, result, &a); if (rc) return rc; }
+    result->n_query = n;
+    if (n == 0) return PTL_OK;
+    HIPCHK(hipSetDevice(ref->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(ref->map_stream));  // (a map update may still be under way)
+    const int64_t n_chunks = (n + CMP_CHUNK - 1) / CMP_CHUNK;
+    const int cap = (int)(n < CMP_CHUNK ? n : CMP_CHUNK);
+    DevOwner tmp;
+    double *d_xyz = nullptr, *d_d2 = nullptr, *d_sum = nullptr;
+    int* d_bad = nullptr;
+    tmp.add(&d_xyz, (size_t)cap * 3); tmp.add(&d_d2, (size_t)cap); tmp.add(&d_sum, (size_t)n_chunks * CMP_SUMS); tmp.add(&d_bad, 1);
+    HIPCHK(tmp.err);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventDefault)); HIPCHK(e1.create(hipEventDefault));
+    hipStream_t s = ref->stream;
+    a.d2 = d_d2; a.bad = d_bad; a.n_alloc = cap;
+    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    for (int64_t ch = 0; ch < n_chunks; ++ch) {  // (one staging buffer: the stream's order keeps a chunk's kernels ahead of the next chunk's copy)
+        const int64_t off = ch * (int64_t)CMP_CHUNK;
+        const int m = (int)(n - off < CMP_CHUNK ? n - off : CMP_CHUNK);
+        HIPCHK(hipMemcpyAsync(d_xyz, xyz + 3 * off, (size_t)m * 24, hipMemcpyHostToDevice, s));
+        CmpArraySrc src = {d_xyz, m};
+        const int wg = (m + 2 * (CMP_THREADS / 64) - 1) / (2 * (CMP_THREADS / 64));
+        k_cmp_points<CmpArraySrc><<<wg < CMP_MAX_BLOCKS ? wg : CMP_MAX_BLOCKS, CMP_THREADS, 0, s>>>(src, ref->c, a);
+        k_cmp_reduce<<<1, 1024, 0, s>>>(d_d2, m, a, d_sum + ch * CMP_SUMS);
+        if (dist2_out) HIPCHK(hipMemcpyAsync(dist2_out + off, d_d2, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipGetLastError());
+    int bad = 0;
+    std::vector<double> sums((size_t)n_chunks * CMP_SUMS);
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sums.data(), d_sum, sums.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad) return set_err(PTL_ERR_STATE, "ptl_icp_map_distance: the reference map's table led %d probes to a block that does not hold the probed voxel", bad);
+    for (int64_t ch = 0; ch < n_chunks; ++ch) map_cmp_add(result, sums.data() + ch * CMP_SUMS);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    result->device_ms = ms;
+    return PTL_OK;
+}
+extern "C" int ptl_icp_map_compare(ptl_icp* ref, ptl_icp* src, const ptl_map_cmp_cfg* cfg, ptl_map_cmp_result* result, double* xyz_out, double* dist2_out,
+                                   int64_t max_points, int64_t* n_written) {
+    if (!ref || !src || !result) return set_err(PTL_ERR_ARG, "ptl_icp_map_compare: null argument");
+    if ((xyz_out != nullptr) != (dist2_out != nullptr)) return set_err(PTL_ERR_ARG, "ptl_icp_map_compare: xyz_out and dist2_out are given together or not at all");
+    const bool given = xyz_out != nullptr;
+    if (given && max_points < 0) return set_err(PTL_ERR_ARG, "ptl_icp_map_compare: max_points = %lld: must not be negative", (long long)max_points);
+    if (ref->cfg.device_id != src->cfg.device_id)
+        return set_err(PTL_ERR_ARG, "ptl_icp_map_compare: reference map on device %d, source map on device %d", ref->cfg.device_id, src->cfg.device_id);
+    CmpArgs a;
+    ptl_map_cmp_result r0;  // (the caller's is written once nothing can be refused for an argument any more)
+    { int rc = map_cmp_setup("ptl_icp_map_compare", ref, cfg, &r0, &a); if (rc) return rc; }
+    HIPCHK(hipSetDevice(ref->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(ref->map_stream));  // (a map update may still be under way, in either handle)
+    HIPCHK(hipStreamSynchronize(src->map_stream));
+    HIPCHK(hipStreamSynchronize(src->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, src->c.st, sizeof st, hipMemcpyDeviceToHost, ref->stream));
+    HIPCHK(hipStreamSynchronize(ref->stream));
+    const int64_t n = st.map_points;
+    if (n < 0 || n > (int64_t)0x7fffffff) return set_err(PTL_ERR_STATE, "ptl_icp_map_compare: the source map reports %lld points", (long long)n);
+    if (given && max_points < n)
+        return set_err(PTL_ERR_CAPACITY, "ptl_icp_map_compare: the source map holds %lld points, max_points = %lld", (long long)n, (long long)max_points);
+    *result = r0;
+    if (n_written) *n_written = 0;
+    result->n_query = n;
+    if (n == 0) return PTL_OK;
+    const Ctx& m = src->c;
+    const int n_chunks = (m.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr, *d_bad = nullptr;
+    double *d_d2 = nullptr, *d_xyz = nullptr, *d_sum = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1); tmp.add(&d_d2, (size_t)n);
+    if (given) tmp.add(&d_xyz, (size_t)n * 3);
+    tmp.add(&d_sum, CMP_SUMS); tmp.add(&d_bad, 1);
+    HIPCHK(tmp.err);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventDefault)); HIPCHK(e1.create(hipEventDefault));
+    hipStream_t s = ref->stream;
+    a.d2 = d_d2; a.xyz_out = d_xyz; a.bad = d_bad; a.n_alloc = (int)n;
+    CmpPoolSrc ps = {m, d_off, n_chunks};
+    HIPCHK(hipEventRecord(e0, s));  // (every per-point slot is written by k_cmp_points when the directory's total is the map state's - checked below)
+    HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    k_score_count<<<(m.pool_cap + 255) / 256, 256, 0, s>>>(m, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    const int wg = (n_chunks + CMP_THREADS / 64 - 1) / (CMP_THREADS / 64);
+    k_cmp_points<CmpPoolSrc><<<wg < CMP_MAX_BLOCKS ? wg : CMP_MAX_BLOCKS, CMP_THREADS, 0, s>>>(ps, ref->c, a);
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipGetLastError());
+    int total = 0, bad = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad) return set_err(PTL_ERR_STATE, "ptl_icp_map_compare: the reference map's table led %d probes to a block that does not hold the probed voxel", bad);
+    if (total != (int)n) return set_err(PTL_ERR_STATE, "ptl_icp_map_compare: the source map's block directory holds %d points, its map state %lld", total, (long long)n);
+    Event e2, e3;
+    HIPCHK(e2.create(hipEventDefault)); HIPCHK(e3.create(hipEventDefault));
+    double sums[CMP_SUMS];
+    HIPCHK(hipEventRecord(e2, s));  // (the reduction reads all n slots: only behind the check that all of them were written)
+    k_cmp_reduce<<<1, 1024, 0, s>>>(d_d2, (int)n, a, d_sum);
+    HIPCHK(hipEventRecord(e3, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, d_sum, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    map_cmp_add(result, sums);
+    float ms = 0, ms2 = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(&ms2, e2, e3));
+    result->device_ms = (double)ms + (double)ms2;
+    if (given) {
+        HIPCHK(hipMemcpy(xyz_out, d_xyz, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist2_out, d_d2, (size_t)n * 8, hipMemcpyDeviceToHost));
         if (n_written) *n_written = n;
     }
     return PTL_OK;

@@ -31,6 +31,70 @@ class PosedScan:
             self.pose = np.tile(np.eye(4), (self.range_mm.shape[1], 1, 1))
 
 
+DEFAULT_COMPARE_THRESHOLDS = (0.05, 0.1, 0.2)  # metres
+
+
+@dataclass
+class MapComparison:
+    """A map against a reference cloud, both directions of the nearest-neighbour distance: `accuracy` has the map's stored
+    points as queries against the reference, `completeness` the reference's against the map (two core.MapDistance).  Per threshold:
+    precision = accuracy's n_within / n_query, recall = completeness', F = 2 P R / (P + R) (0 when both are 0)."""
+    accuracy: "core.MapDistance"
+    completeness: "core.MapDistance"
+    reference_name: str = "reference"
+    reference_points: int = 0
+
+    @property
+    def thresholds(self):
+        return self.accuracy.thresholds
+
+    @property
+    def precision(self):
+        return self.accuracy.fractions
+
+    @property
+    def recall(self):
+        return self.completeness.fractions
+
+    @property
+    def f_score(self):
+        return tuple(2.0 * p * r / (p + r) if p + r > 0.0 else 0.0 for p, r in zip(self.precision, self.recall))
+
+    def lines(self):
+        """the block the commands print"""
+        out = [f"map comparison: reference {self.reference_name} ({self.reference_points} points), max dist {self.accuracy.max_dist:g} m"]
+        for name, d in (("accuracy (map -> reference)", self.accuracy), ("completeness (reference -> map)", self.completeness)):
+            out.append(f"  {name}: {d.n_query} queries, {d.n_matched} matched, mean {1000.0 * d.mean_dist:.3f} mm, rms {1000.0 * d.rms_dist:.3f} mm")
+        for t, p, r, f in zip(self.thresholds, self.precision, self.recall, self.f_score):
+            out.append(f"  at {t:g} m: precision {p:.6f}, recall {r:.6f}, F {f:.6f}")
+        return out
+
+
+def compare_maps(map_icp, ref_icp, thresholds=DEFAULT_COMPARE_THRESHOLDS, max_dist=None, per_point=False, reference_name="reference"):
+    """`MapComparison` of two map handles (core.Icp) on one device; per_point: also (xyz, d2) of the map's stored points against the reference"""
+    thresholds = DEFAULT_COMPARE_THRESHOLDS if thresholds is None else thresholds
+    acc = ref_icp.map_compare(map_icp, max_dist=max_dist, thresholds=thresholds, per_point=per_point)
+    com = map_icp.map_compare(ref_icp, max_dist=max_dist, thresholds=thresholds)
+    cmp_ = MapComparison(acc[0] if per_point else acc, com, reference_name, com.n_query)
+    return (cmp_, acc[1]) if per_point else cmp_
+
+
+def compare_handle(map_icp, reference, thresholds=DEFAULT_COMPARE_THRESHOLDS, max_dist=None, per_point=False, reference_name="reference"):
+    """`compare_maps` of a map handle against `reference`: a core.Icp, a MapAccumulator, or an (N, 3) array, for which a reference handle is
+    built for the call at the map's voxel size, points per voxel and capacities"""
+    if isinstance(reference, MapAccumulator):
+        reference = reference.icp
+    if isinstance(reference, core.Icp):
+        return compare_maps(map_icp, reference, thresholds, max_dist, per_point, reference_name)
+    c = map_icp.cfg
+    ref = core.map_from_points(reference, voxel_size=c.voxel_size, max_points_per_voxel=c.max_points_per_voxel, device_id=c.device_id,
+                               map_block_capacity=c.map_block_capacity, map_table_capacity=c.map_table_capacity)
+    try:
+        return compare_maps(map_icp, ref, thresholds, max_dist, per_point, reference_name)
+    finally:
+        ref.close()
+
+
 class MapAccumulator:
     """Accumulates posed scans into a world-frame voxel map on the GPU (ScansAccumulator's map, deterministic form)."""
 
@@ -97,6 +161,12 @@ class MapAccumulator:
     def score(self, radius=None, min_neighbours=5, sigma_floor=None, per_point=False):
         """sharpness of the accumulated map without ground truth: core.Icp.map_score of the map handle"""
         return self._icp.map_score(radius=radius, min_neighbours=min_neighbours, sigma_floor=sigma_floor, per_point=per_point)
+
+    def compare(self, reference, thresholds=DEFAULT_COMPARE_THRESHOLDS, max_dist=None, per_point=False, reference_name="reference"):
+        """the accumulated map against a reference cloud, both directions: a `MapComparison`.  reference: a core.Icp (or a
+        MapAccumulator) whose map is the reference, or an (N, 3) array - a reference handle is then built for the call at this map's voxel
+        size and points per voxel, so a cloud this map wrote reloads completely.  max_dist defaults to the voxel size"""
+        return compare_handle(self._icp, reference, thresholds, max_dist, per_point, reference_name)
 
 
 # ------------------------------------------------------------------------------------------------ the camera path (DESIGN.md 3.21)

@@ -245,6 +245,7 @@ _PLY_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {n}\n"
 _PLY_SCALARS = (("int", "neighbours"), ("double", "plane_var"), ("double", "entropy"))
 _PLY_XYZ = [("double", "x"), ("double", "y"), ("double", "z")]
 _PLY_SCORED_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("neighbours", "<i4"), ("plane_var", "<f8"), ("entropy", "<f8")])
+_PLY_DIST_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("dist", "<f8")])
 
 
 def save_map_ply(path: str, xyz, scalars=None) -> None:
@@ -252,8 +253,20 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
     as they are, so a map read back is bit-equal; a path ending in .npy uses np.save instead.
     scalars = (neighbours (N,) int, plane_var (N,), entropy (N,)) - the per-point values of a map score: three more
     properties behind x y z (`int neighbours`, `double plane_var`, `double entropy`); PLY only (a .npy map is the points and nothing else).
+    scalars = {"dist": (N,)} - the per-point distance to a reference cloud (NaN = unmatched): one more property, `double dist`.
     Without scalars the file is what it always was, byte for byte."""
     pts = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    if isinstance(scalars, dict):
+        if list(scalars) != ["dist"] or len(np.asarray(scalars["dist"]).reshape(-1)) != len(pts):
+            raise ValueError("scalars: a dict holds `dist`, one value per point")
+        if str(path).endswith(".npy"):
+            raise ValueError("per-point scalars are written to a PLY file only: a .npy map holds the points")
+        rec = np.empty(len(pts), dtype=_PLY_DIST_DTYPE)
+        rec["xyz"], rec["dist"] = pts, np.asarray(scalars["dist"], dtype=np.float64).reshape(-1)
+        with open(path, "wb") as f:
+            f.write(_PLY_HEADER.format(n=len(pts)).replace("end_header\n", "property double dist\nend_header\n").encode("ascii"))
+            f.write(rec.tobytes())
+        return
     if scalars is not None:
         nb, pv, ent = (np.asarray(a).reshape(-1) for a in scalars)
         if not len(nb) == len(pv) == len(ent) == len(pts):
@@ -277,7 +290,8 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
 
 def load_map_ply(path: str, scalars: bool = False):
     """(N, 3) float64 of a map written by `save_map_ply` (.npy: np.load), with or without per-point scalars.  Reads the PLY subset that
-    function writes.  scalars=True: (points, (neighbours int32, plane_var, entropy)), the second None for a file without them."""
+    function writes.  scalars=True: (points, (neighbours int32, plane_var, entropy)), the second None for a file without them and
+    {"dist": (N,)} for a file with the distance to a reference cloud."""
     if str(path).endswith(".npy"):
         pts = np.load(path).reshape(-1, 3)
         return (pts, None) if scalars else pts
@@ -300,6 +314,14 @@ def load_map_ply(path: str, scalars: bool = False):
         else:
             raise ValueError(f"{path}: no end_header")
         scored = props == _PLY_XYZ + list(_PLY_SCALARS)
+        with_dist = props == _PLY_XYZ + [("double", "dist")]
+        if with_dist and fmt == "binary_little_endian" and n is not None:
+            data = f.read(n * 32)
+            if len(data) != n * 32:
+                raise ValueError(f"{path}: {n} vertices announced, {len(data) // 32} present")
+            rec = np.frombuffer(data, dtype=_PLY_DIST_DTYPE)
+            pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
+            return (pts, {"dist": rec["dist"].astype(np.float64)}) if scalars else pts
         if fmt != "binary_little_endian" or n is None or not (props == _PLY_XYZ or scored):
             raise ValueError(f"{path}: expected binary_little_endian, element vertex N, property double x y z"
                              " (optionally int neighbours, double plane_var, double entropy)")
