@@ -84,6 +84,7 @@ def lib():
             "orc_ekf_process_imu": (None, [vp, c_d_p, c_d_p, C.c_double]),
             "orc_ekf_process_pose": (None, [vp, c_d_p, c_d_p]),
             "orc_ekf_get_nav": (None, [vp, c_d_p]), "orc_ekf_get_cov": (None, [vp, c_d_p]),
+            "orc_ekf_get_fx": (None, [vp, c_d_p]),
             "orc_ekf_pose_mat": (None, [vp, c_d_p]), "orc_ekf_ts": (C.c_double, [vp]),
             "orc_calc_ate": (C.c_int, [c_d_p, c_d_p, C.c_int64, c_d_p]),
             "orc_set_threads": (None, [C.c_int]), "orc_get_threads": (C.c_int, []),
@@ -329,6 +330,13 @@ class EKF:
     def cov(self):
         out = np.empty((18, 18))
         lib().orc_ekf_get_cov(self._h, out.ctypes.data_as(c_d_p))
+        return out
+
+    @property
+    def fx(self):
+        """Fx of the last predict (identity before the first)"""
+        out = np.empty((18, 18))
+        lib().orc_ekf_get_fx(self._h, out.ctypes.data_as(c_d_p))
         return out
 
     def pose_mat(self):

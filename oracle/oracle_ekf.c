@@ -264,6 +264,7 @@ void orc_ekf_get_nav(const orc_ekf *e, double nav[19]) {
     memcpy(nav + 16, e->grav, 24);
 }
 void orc_ekf_get_cov(const orc_ekf *e, double cov[324]) { memcpy(cov, e->P, sizeof e->P); }
+void orc_ekf_get_fx(const orc_ekf *e, double fx[324]) { memcpy(fx, e->Fx, sizeof e->Fx); }
 void orc_ekf_pose_mat(const orc_ekf *e, double T[16]) {
     double R[9];
     quat_to_mat(e->q, R);
