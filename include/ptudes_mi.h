@@ -797,6 +797,78 @@ int ptl_icp_map_distance(ptl_icp *ref, const ptl_map_cmp_cfg *cfg, const double 
 int ptl_icp_map_compare(ptl_icp *ref, ptl_icp *src, const ptl_map_cmp_cfg *cfg, ptl_map_cmp_result *result, double *xyz_out, double *dist2_out,
                         int64_t max_points, int64_t *n_written);
 
+/* ------------------------------------------------------------------------------------------------
+ * Free space carved: the moving-object points of a world map (no reference counterpart).  A second pass over the sweeps that
+ * built a map, posed by the same trajectory: for every STORED map point it counts the rays that went through the point and the rays that ended
+ * at it.  All outputs are integers; sums of integers have no order, so every count is an exact function of the map's stored points and the set
+ * of rays - the lane mapping, the launch geometry and the order of the sweeps do not change it.  All arithmetic fp64 in the written order,
+ * without contraction.
+ * Parameters: radius > 0; margin >= 0; 0 < step <= the map's voxel size vs; min_range >= 0; max_range > min_range, max_range / step <= 65536.
+ * The defaults (radius = vs / 10, margin = vs, step = vs / 2, min_range = 0, max_range = 120 vs) are a caller's choice that the result echoes
+ * back, not tuned values.
+ * Ray: a pixel with a return.  Its end w is the world point the posed-scan pass gives it (ptl_icp_map_add_posed_*), its origin o the
+ * translation of its own column's pose; d = w - o, len2 = (dx dx + dy dy) + dz dz, len = sqrt(len2).  The ray is used iff
+ * min_range <= len <= max_range, otherwise it is counted in n_rays_out_of_range; a pixel without a return is counted in n_no_return.  A sweep
+ * with any column outside the trajectory's bounds is skipped as a whole and counted (n_scans_skipped), as ptl_icp_map_add_posed_* skips it.
+ * March: the samples are k = 0, 1, ... while t_k = ((double)k + 0.5) step < len: a_k = t_k / len, s_k[c] = o[c] + a_k d[c]; the last sample is
+ * w itself, not o + 1 d.  A sample's voxel is the map's own truncating index (int)(coordinate / vs) per axis; a sample outside the key range
+ * (2^20 voxels either side) is passed over; consecutive samples with one key visit the voxel once.  Every coordinate of s_k is monotone in k and
+ * so is the index: a ray cannot return to a voxel it has left.
+ * Vote: for every point p stored in a visited voxel, e = p - o: c = e x d with six separately rounded products (cx = ey dz - ez dy, ...); p is
+ * near the ray iff (cx cx + cy cy) + cz cz <= (radius radius) len2 (the left factor made once per call, the product once per ray);
+ * t_p = ((ex dx + ey dy) + ez dz) / len.  A near point with t_p < min_range gets nothing; with t_p <= len - margin through += 1; otherwise with
+ * t_p <= len + margin support += 1; beyond that nothing.
+ * ONLY the visited voxels are looked at: a point within `radius` of a ray whose centre line misses the point's voxel is NOT counted.  This is
+ * part of the definition; the rays of a sweep are dense against `radius`.  Which points count as moving is the caller's policy on the two
+ * counts (the Python layer's CarveVotes.dynamic), not the library's. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_carve_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double radius, margin, step, min_range, max_range;
+} ptl_carve_cfg;
+typedef struct {
+    int64_t n_points;                                  /* stored points of the map (the length of the per-point arrays) */
+    int64_t n_scans, n_scans_skipped;                  /* sweeps carved / skipped as outside the trajectory's bounds */
+    int64_t n_rays, n_rays_out_of_range, n_no_return;  /* pixels of the carved sweeps: used rays, returns outside [min_range, max_range], no return */
+    int64_t n_voxel_visits;                            /* visited voxels that the map holds, over all rays */
+    int64_t n_points_through, n_points_supported;      /* points with a non-zero count */
+    int64_t sum_through, sum_support;
+    double radius, margin, step, min_range, max_range; /* the parameters as used */
+    double device_ms;                                  /* HIP-event time of the handle's device work so far: prefixes, sweeps, the read's reduction */
+} ptl_carve_result;
+typedef struct ptl_carve ptl_carve; /* the votes for one map: its own stream, column table, sweep staging and vote arrays */
+/* the library's sizeof(ptl_carve_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_carve_sizeof_cfg(void);
+/* the defaults for a map of that voxel size; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is
+ * refused with PTL_ERR_ARG and nothing is written */
+int ptl_carve_default_cfg(ptl_carve_cfg *cfg, double voxel_size);
+/* cfg nullable: the defaults of the map's voxel size.  Waits for the map's update, snapshots its point count and the per-block prefixes of the
+ * pool order (block id, then slot: the order of ptl_icp_map_score's and ptl_icp_map_compare's per-point outputs) and clears the votes.  The map
+ * handle must outlive the carve handle and is only ever read.  Checked before any HIP call, refused with the numbers (PTL_ERR_ARG): null map /
+ * out, a cfg of another size or version, each parameter bound above. */
+int ptl_carve_create(ptl_icp *map, const ptl_carve_cfg *cfg, ptl_carve **out);
+int ptl_carve_destroy(ptl_carve *c);
+/* one posed sweep, with the arguments of ptl_icp_map_add_posed_range / _xyz: *n_valid = the sweep's used rays (nullable), *skipped = 1 when a
+ * column lay outside the bounds and nothing was counted but the sweep (nullable).  Trajectory, LUT and map on one device (else PTL_ERR_ARG with
+ * the ids); W = the map handle's scan_cols and H W <= its max_points_per_scan (else PTL_ERR_CAPACITY with the numbers) - all before any HIP call.
+ * Every add and read compares the map's point count with the snapshot: a map updated since ptl_carve_create gives PTL_ERR_STATE.
+ * PTL_ERR_STATE as well when the map's table leads a probe to a block that does not hold the probed voxel. */
+int ptl_carve_add_posed_range(ptl_carve *c, ptl_traj *t, ptl_lut *lut, const uint32_t *range_mm, const double *col_ts, int64_t *n_valid,
+                              int32_t *skipped);
+int ptl_carve_add_posed_xyz(ptl_carve *c, ptl_traj *t, const float *xyz, int32_t H, int32_t W, const double *col_ts, int64_t *n_valid,
+                            int32_t *skipped);
+/* the RESIDENT sweeps [first, last] of a runner, no sweep crosses the bus; arguments, column times and state errors as ptl_seq_map_build /
+ * ptl_batch_map_build.  *n_valid = used rays, *n_skipped = sweeps skipped (both nullable) */
+int ptl_carve_add_seq(ptl_carve *c, ptl_seq *s, ptl_traj *t, const double *t0t1, int64_t first, int64_t last, int64_t *n_valid,
+                      int64_t *n_skipped);
+int ptl_carve_add_batch(ptl_carve *c, ptl_batch *b, int32_t seq, ptl_traj *t, const double *t0t1, int64_t first, int64_t last,
+                        int64_t *n_valid, int64_t *n_skipped);
+/* the summary so far, and (all three arrays given, or none) every stored point (3 doubles) with its two counts in pool order; *n_written
+ * (nullable) their number.  max_points below the map's point count: PTL_ERR_CAPACITY naming the count, nothing written.  The votes stay: sweeps
+ * may be added and read again. */
+int ptl_carve_read(ptl_carve *c, ptl_carve_result *result, double *xyz_out, uint32_t *through_out, uint32_t *support_out, int64_t max_points,
+                   int64_t *n_written);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,19 @@ class MapCmpResult(C.Structure):
                 ("n_thresholds", C.c_int32), ("thresholds", C.c_double * 8), ("device_ms", C.c_double)]
 
 
+class CarveCfg(_Cfg):
+    """ptl_carve_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("radius", C.c_double), ("margin", C.c_double), ("step", C.c_double),
+                ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class CarveResult(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_scans", C.c_int64), ("n_scans_skipped", C.c_int64), ("n_rays", C.c_int64),
+                ("n_rays_out_of_range", C.c_int64), ("n_no_return", C.c_int64), ("n_voxel_visits", C.c_int64), ("n_points_through", C.c_int64),
+                ("n_points_supported", C.c_int64), ("sum_through", C.c_int64), ("sum_support", C.c_int64), ("radius", C.c_double),
+                ("margin", C.c_double), ("step", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("device_ms", C.c_double)]
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -260,6 +273,16 @@ PROTOTYPES = {
     "ptl_map_cmp_default_cfg": (C.c_int, [C.POINTER(MapCmpCfg), C.c_double]),
     "ptl_icp_map_distance": (C.c_int, [_vp, C.POINTER(MapCmpCfg), c_d_p, C.c_int64, C.POINTER(MapCmpResult), c_d_p]),
     "ptl_icp_map_compare": (C.c_int, [_vp, _vp, C.POINTER(MapCmpCfg), C.POINTER(MapCmpResult), c_d_p, c_d_p, C.c_int64, c_i64_p]),
+    # free space carved: through / support votes of a map's stored points (include/ptudes_mi.h)
+    "ptl_carve_sizeof_cfg": (C.c_int64, []),
+    "ptl_carve_default_cfg": (C.c_int, [C.POINTER(CarveCfg), C.c_double]),
+    "ptl_carve_create": (C.c_int, [_vp, C.POINTER(CarveCfg), _vpp]),
+    "ptl_carve_destroy": (C.c_int, [_vp]),
+    "ptl_carve_add_posed_range": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32), c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_carve_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_carve_add_seq": (C.c_int, [_vp, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    "ptl_carve_add_batch": (C.c_int, [_vp, _vp, C.c_int32, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    "ptl_carve_read": (C.c_int, [_vp, C.POINTER(CarveResult), c_d_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

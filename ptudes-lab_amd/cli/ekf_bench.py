@@ -204,8 +204,9 @@ MAP_VOXEL_SIZE = 0.5
 MAP_TIME_BOUNDS = 1.5  # as the fly-by's pose_scans_from_nc_gt (reference utils.py:368)
 
 
-def _run_map_handle(seq, first, knots, voxel_size, device_id):
-    """(map handle, n_skipped): the map of `run_map`, still on the device"""
+def _run_map_handle(seq, first, knots, voxel_size, device_id, carve=None):
+    """(map handle, n_skipped): the map of `run_map`, still on the device; with carve (`carve_options`) a third entry, the core.CarveVotes of
+    a second pass over the same resident sweeps"""
     from .. import core
     from ..sequence import sweep_times
     traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
@@ -216,9 +217,15 @@ def _run_map_handle(seq, first, knots, voxel_size, device_id):
     map_icp = core.Icp(1.0e9, 0.0, voxel_size=voxel_size, scan_cols=seq.W, max_points_per_scan=seq.H * seq.W, device_id=device_id,
                        map_block_capacity=1 << 21, map_table_capacity=1 << 23)
     _, n_skipped = runner.build_map(map_icp, traj, sweep_times(seq), first=first)
+    votes = None
+    if carve is not None:
+        carver = core.Carver(map_icp, **carve["cfg"])
+        carver.add_run(runner, traj, sweep_times(seq), first=first)
+        votes = carver.votes()
+        carver.close()
     for h in (runner, traj):
         h.close()
-    return map_icp, n_skipped
+    return (map_icp, n_skipped) if carve is None else (map_icp, n_skipped, votes)
 
 
 def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
@@ -232,24 +239,45 @@ def run_map(seq, first, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
     return pts, voxels, n_skipped
 
 
-def _bag_map(bags, info, start_scan, end_scan, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0):
+def _bag_map(bags, info, start_scan, end_scan, knots, voxel_size=MAP_VOXEL_SIZE, device_id=0, carve=None):
     """... of a raw packet bag: a second pass over the bag through the package's packet feed, every decoded sweep into the map by the fused
     per-call path with its decoded column times (every column posed at its own firing time).  The LUT is the registration's
-    (lidar_to_sensor and the extrinsic, sequence.run_events).  Returns the fly.MapAccumulator."""
+    (lidar_to_sensor and the extrinsic, sequence.run_events).  Returns the fly.MapAccumulator; with carve (`carve_options`) also the
+    core.CarveVotes of a third pass over the bag."""
     from .. import core, fly
     lut = fly.sensor_lut(info, use_extrinsics=True, device_id=device_id)
     traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
     acc = fly.MapAccumulator(lut, voxel_size=voxel_size, device_id=device_id)
     fly.add_packet_bag(acc, bags, info, traj, start_scan, end_scan, device_id=device_id)
+    votes = None
+    if carve is not None:
+        carver = fly.MapCarver(acc, **carve["cfg"])
+        fly.carve_packet_bag(carver, bags, info, traj, start_scan, end_scan, device_id=device_id)
+        votes = carver.votes()
+        carver.close()
     traj.close()
     lut.close()  # (the sweeps are in: the map no longer needs it)
-    return acc
+    return acc if carve is None else (acc, votes)
 
 
-def _finish_map(path, map_icp, score, compare=None):
+def _finish_map(path, map_icp, score, compare=None, carved=None):
     """points (and, with `score` = keyword arguments of Icp.map_score, the per-point scalars) of a built map to `path` (nullable);
-    compare (`compare_options`): the map against the reference cloud first, printed; returns (voxels, points, MapScore | None)"""
+    compare (`compare_options`): the map against the reference cloud first, printed; carved = (core.CarveVotes, `carve_options`): the
+    map's figures as accumulated are printed, the votes' block, and everything that follows works on the cleaned map;
+    returns (voxels, points, MapScore | None)"""
     from ..utils import save_map_ply
+    if carved is not None:
+        if compare is not None or score is not None:
+            print("before carving:")
+        if compare is not None:
+            run_compare(map_icp, dict(compare, save_error=None))
+        if score is not None:
+            print("\n".join(map_icp.map_score(**score).lines()))
+        clean = carve_report(map_icp, *carved)
+        map_icp.close()
+        map_icp = clean
+        if compare is not None or score is not None:
+            print("after carving:")
     voxels, _ = map_icp.map_size()
     if compare is not None:
         run_compare(map_icp, compare)
@@ -268,11 +296,11 @@ def _finish_map(path, map_icp, score, compare=None):
     return voxels, len(pts), ms
 
 
-def _save_run_map(path, seq, first, rows_t, rows_p, score=None, compare=None):
+def _save_run_map(path, seq, first, rows_t, rows_p, score=None, compare=None, carve=None):
     """... under the rows as the poses file holds them (utils.nc_gt_file_rows): what `flyby --nc-gt-poses` of that file works with"""
     from ..utils import nc_gt_file_rows
-    map_icp, n_skipped = _run_map_handle(seq, first, nc_gt_file_rows(rows_t, rows_p), MAP_VOXEL_SIZE, 0)
-    voxels, points, ms = _finish_map(path, map_icp, score, compare)
+    map_icp, n_skipped, *votes = _run_map_handle(seq, first, nc_gt_file_rows(rows_t, rows_p), MAP_VOXEL_SIZE, 0, carve)
+    voxels, points, ms = _finish_map(path, map_icp, score, compare, (votes[0], carve) if carve is not None else None)
     return voxels, points, n_skipped, ms
 
 
@@ -369,6 +397,71 @@ def run_compare(map_icp, compare):
     return cmp_
 
 
+CARVE_OPTIONS = [
+    click.option("--carve", is_flag=True,
+                 help="after the map is built, pass over the same sweeps again and count for every stored point the rays that went through it "
+                      "and the rays that ended at it (GPU); the points the policy flags as a moving object's leave the map before it is "
+                      "saved, scored or compared; needs --save-map, --map-score or --compare-map"),
+    click.option("--save-carved", required=False, type=click.Path(dir_okay=False),
+                 help="write EVERY stored point with its votes (PLY: uint through, uint support, uchar dynamic)"),
+    click.option("--carve-radius", type=float, default=None, help="a point within this distance of a ray is met by it, metres (default: voxel size / 10)"),
+    click.option("--carve-margin", type=float, default=None,
+                 help="a point closer than this to a ray's end along the ray supports it instead, metres (default: the voxel size)"),
+    click.option("--carve-max-range", type=float, default=None, help="longest ray used, metres (default: 120 voxel sizes)"),
+    click.option("--carve-min-through", type=int, default=None, help="policy: rays through a point before it can count as moving (default 2)"),
+    click.option("--carve-min-fraction", type=float, default=None,
+                 help="policy: share of through among the rays that met the point, through / (through + support) (default 0.5)"),
+]
+
+
+def carve_click_options(f):
+    for opt in reversed(CARVE_OPTIONS):
+        f = opt(f)
+    return f
+
+
+def carve_options(carve, save_carved, carve_radius, carve_margin, carve_max_range, carve_min_through, carve_min_fraction, voxel_size, have_map):
+    """the options of --carve checked before any device is touched: None without it, else a dict with the policy's defaults filled in"""
+    given = {"--save-carved": save_carved, "--carve-radius": carve_radius, "--carve-margin": carve_margin, "--carve-max-range": carve_max_range,
+             "--carve-min-through": carve_min_through, "--carve-min-fraction": carve_min_fraction}
+    if not carve:
+        for name, v in given.items():
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --carve")
+        return None
+    if not have_map:
+        raise click.ClickException("--carve needs a map: --save-map, --map-score or --compare-map")
+    if carve_radius is not None and not carve_radius > 0.0:
+        raise click.ClickException(f"--carve-radius {carve_radius:g}: must be positive")
+    if carve_margin is not None and not carve_margin >= 0.0:
+        raise click.ClickException(f"--carve-margin {carve_margin:g}: must not be negative")
+    if carve_max_range is not None and not 0.0 < carve_max_range <= 32768.0 * voxel_size:
+        raise click.ClickException(f"--carve-max-range {carve_max_range:g}: must be in (0, {32768.0 * voxel_size:g}] (65536 steps of half a voxel)")
+    if carve_min_through is not None and carve_min_through < 0:
+        raise click.ClickException(f"--carve-min-through {carve_min_through}: must not be negative")
+    if carve_min_fraction is not None and not 0.0 <= carve_min_fraction <= 1.0:
+        raise click.ClickException(f"--carve-min-fraction {carve_min_fraction:g}: must be in [0, 1]")
+    if save_carved and not str(save_carved).endswith(".ply"):
+        raise click.ClickException(f"--save-carved {save_carved}: the votes are written to a .ply file")
+    return dict(cfg=dict(radius=carve_radius, margin=carve_margin, max_range=carve_max_range), save=save_carved,
+                min_through=2 if carve_min_through is None else carve_min_through,
+                min_fraction=0.5 if carve_min_fraction is None else carve_min_fraction)
+
+
+def carve_report(map_icp, votes, carve):
+    """--carve: prints the votes' block, writes --save-carved's file and returns the cleaned map's handle (a new core.Icp; `map_icp` stays)"""
+    from .. import fly
+    from ..utils import save_map_ply
+    dyn = votes.dynamic(carve["min_through"], carve["min_fraction"])
+    print("\n".join(votes.lines(carve["min_through"], carve["min_fraction"])))
+    if carve["save"]:
+        save_map_ply(carve["save"], votes.xyz, {"through": votes.through, "support": votes.support, "dynamic": dyn.astype(np.uint8)})
+        print(f"Carved map saved to: {carve['save']}")
+    clean = fly.carved_handle(map_icp, dyn, votes.xyz)
+    print(f"map after carving: {clean.map_size()[0]} voxels, {clean.map_size()[1]} points")
+    return clean
+
+
 def score_options(map_score, score_radius, voxel_size):
     """the keyword arguments of Icp.map_score for --map-score / --score-radius, or None; refusals before any device is touched"""
     if score_radius is not None and not map_score:
@@ -429,6 +522,7 @@ def score_options(map_score, score_radius, voxel_size):
 @click.option("--score-radius", type=float, default=None, help="neighbourhood radius of --map-score, metres (default and upper bound: the "
                                                                "map's voxel size, 0.5)")
 @compare_click_options
+@carve_click_options
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
@@ -436,7 +530,10 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                       imu_deskew: bool = False, save_map: Optional[str] = None, map_from: str = "filter",
                       native_packets: bool = False, map_score: bool = False, score_radius: Optional[float] = None,
                       compare_map: Optional[str] = None, compare_threshold: Optional[str] = None, compare_max_dist: Optional[float] = None,
-                      compare_pose: Optional[str] = None, save_map_error: Optional[str] = None) -> None:
+                      compare_pose: Optional[str] = None, save_map_error: Optional[str] = None, carve: bool = False,
+                      save_carved: Optional[str] = None, carve_radius: Optional[float] = None, carve_margin: Optional[float] = None,
+                      carve_max_range: Optional[float] = None, carve_min_through: Optional[int] = None,
+                      carve_min_fraction: Optional[float] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
@@ -444,6 +541,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
     score = score_options(map_score, score_radius, MAP_VOXEL_SIZE)
     compare = compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, MAP_VOXEL_SIZE)
     want_map = bool(save_map) or map_score or compare is not None
+    carving = carve_options(carve, save_carved, carve_radius, carve_margin, carve_max_range, carve_min_through, carve_min_fraction, MAP_VOXEL_SIZE,
+                            want_map)
     if want_map and map_from == "smoothed" and not save_smoothed_poses:
         raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
@@ -581,7 +680,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
         rows_t, rows_p = {"filter": (res_t, res_poses), "kiss": (res_t, kiss_poses),
                           "smoothed": (out.get("smoothed_t"), out.get("smoothed_poses"))}[map_from]
         if seq is not None:
-            voxels, points, n_skipped, ms = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p), score=score, compare=compare)
+            voxels, points, n_skipped, ms = _save_run_map(save_map, seq, start_scan, list(rows_t), list(rows_p), score=score, compare=compare,
+                                                           carve=carving)
             print(f"Map of scans {start_scan} - {seq.n_scans - 1} ({map_from} poses, {n_skipped} skipped): {voxels} voxels, {points} points")
         else:
             from ..utils import nc_gt_file_rows
@@ -589,8 +689,11 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                 raise click.ClickException("the map needs a trajectory of at least two poses")
             if beams:
                 print("NOTE: --beams thins the scans of the registration only; the map takes every beam of every sweep")
-            acc = _bag_map(bags, info, start_scan, end_scan, nc_gt_file_rows(list(rows_t), list(rows_p)))
-            voxels, points, ms = _finish_map(save_map, acc.icp, score, compare)
+            acc = _bag_map(bags, info, start_scan, end_scan, nc_gt_file_rows(list(rows_t), list(rows_p)), carve=carving)
+            votes = None
+            if carving is not None:
+                acc, votes = acc
+            voxels, points, ms = _finish_map(save_map, acc.icp, score, compare, (votes, carving) if carving is not None else None)
             print(f"Map of {acc.scans} scans from {start_scan} ({map_from} poses, {acc.skipped} skipped): {voxels} voxels, {points} points")
         if ms is not None:
             print("\n".join(ms.lines()))

@@ -10,7 +10,10 @@ FILE (.pcap / .bag) goes through ouster-sdk when it is importable; a raw packet 
 own packet decoder (packets.py) when it is not, or with --native-packets - every column is then posed at its decoded firing time;
 `--synthetic SEED` runs the same path on the synthetic sequence.  `--map-score` prints the sharpness of the map without ground truth
  and, with `--save-map`, adds the per-point values to the PLY.  `--compare-map REF` measures the map against a reference
-cloud on the GPU: accuracy, completeness, precision / recall / F per threshold.
+cloud on the GPU: accuracy, completeness, precision / recall / F per threshold.  `--carve` passes over the same sweeps a
+second time and takes the points that later rays went through - a moving object's trail - out of the map before it is saved, scored or
+compared (both maps' figures are printed); `--save-carved` writes every stored point with its votes.  The frames draw the
+map as accumulated.
 """
 from typing import Optional
 
@@ -19,6 +22,7 @@ import numpy as np
 
 from ..utils import read_newer_college_gt, save_map_ply
 
+from .ekf_bench import carve_click_options as _carve_click_options
 from .ekf_bench import compare_click_options as _compare_click_options
 
 TIME_BOUNDS = 1.5  # seconds a column may lie outside the poses file (reference utils.py:368)
@@ -95,6 +99,7 @@ def frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_r
               help="heights LO,HI of the palette's ends for --save-frames (default: the map's own z extent once it is built; while it is "
                    "being built, the sensor's height +- 10 m)")
 @_compare_click_options
+@_carve_click_options
 def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional[str], nc_gt_poses: Optional[str], rate: float,
                  accum_map_ratio: Optional[float], start_scan: int, end_scan: Optional[int], voxel_size: float,
                  save_map: Optional[str], synthetic: Optional[int], native_packets: bool = False, map_score: bool = False,
@@ -102,7 +107,9 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
                  fps: Optional[float] = None, max_frames: Optional[int] = None, point_size: Optional[int] = None,
                  edl: Optional[float] = None, z_range: Optional[str] = None, compare_map: Optional[str] = None,
                  compare_threshold: Optional[str] = None, compare_max_dist: Optional[float] = None, compare_pose: Optional[str] = None,
-                 save_map_error: Optional[str] = None) -> None:
+                 save_map_error: Optional[str] = None, carve: bool = False, save_carved: Optional[str] = None,
+                 carve_radius: Optional[float] = None, carve_margin: Optional[float] = None, carve_max_range: Optional[float] = None,
+                 carve_min_through: Optional[int] = None, carve_min_fraction: Optional[float] = None) -> None:
     """Map of the lidar scans with poses (the flyby visualizer's map, headless).
 
     Data is provided via FILE in Ouster raw packets formats (PCAP or BAG with lidar/imu packets), or --synthetic SEED.
@@ -110,6 +117,9 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
     frames = frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_range)
     from .ekf_bench import compare_options, run_compare
     compare = compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, voxel_size)
+    from .ekf_bench import carve_options, carve_report
+    carving = carve_options(carve, save_carved, carve_radius, carve_margin, carve_max_range, carve_min_through, carve_min_fraction, voxel_size,
+                            bool(save_map) or map_score or compare is not None)
     if kitti_poses:
         raise click.ClickException("--kitti-poses is not supported here: the column timing of one-pose-per-scan files is defined inside "
                                    "ouster-sdk's pose_scans_from_kitti, which this build cannot read; use --nc-gt-poses")
@@ -227,6 +237,29 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
     print(f"map of scans: {start_scan} - {end_scan}")
     print(f"map num points: {points}")
     print(f"map voxels: {voxels} (voxel size {voxel_size})")
+    if carving is not None:
+        # the second pass over the same sweeps; the frames above drew the map as accumulated
+        carver = fly.MapCarver(acc, **carving["cfg"])
+        if native:
+            fly.carve_packet_bag(carver, bags, info, traj, start_scan, end_scan)
+        else:
+            for scan in (scans if isinstance(scans, list) else real_scans()):
+                carver.update(scan, traj)
+        votes = carver.votes()
+        carver.close()
+        if compare is not None or score is not None:
+            print("before carving:")
+        if compare is not None:
+            run_compare(acc.icp, dict(compare, save_error=None))
+        if score is not None:
+            print("\n".join(acc.score(**score).lines()))
+        clean = fly.MapAccumulator.__new__(fly.MapAccumulator)
+        clean.lut, clean.scans, clean.returns, clean.skipped = acc.lut, acc.scans, acc.returns, acc.skipped
+        clean._icp = carve_report(acc.icp, votes, carving)
+        acc.close()
+        acc = clean
+        if compare is not None or score is not None:
+            print("after carving:")
     if compare is not None:
         run_compare(acc.icp, compare)
     scalars = None

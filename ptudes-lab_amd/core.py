@@ -437,6 +437,132 @@ class Traj:
     __del__ = close
 
 
+def carve_dynamic(through, support, min_through=2, min_fraction=0.5):
+    """HOST POLICY on the two counts of `Carver.votes()`, not part of the library's definition: a stored point counts as a moving object's
+    when at least min_through rays went through it and they are at least min_fraction of the rays that met it,
+    (through >= min_through) & (through >= min_fraction * (through + support)).  Returns a bool mask"""
+    t, s = np.asarray(through, dtype=np.int64), np.asarray(support, dtype=np.int64)
+    return (t >= int(min_through)) & (t >= float(min_fraction) * (t + s))
+
+
+@dataclass
+class CarveVotes:
+    """What `Carver.votes()` returns (include/ptudes_mi.h ptl_carve_result): every stored point of the map in pool order with
+    the rays that went through it and the rays that ended at it, and the summary - counts (all exact), the parameters as used, the HIP-event
+    time of the handle's device work so far"""
+    xyz: np.ndarray        # (N, 3)
+    through: np.ndarray    # (N,) uint32
+    support: np.ndarray    # (N,) uint32
+    n_points: int
+    n_scans: int
+    n_scans_skipped: int
+    n_rays: int
+    n_rays_out_of_range: int
+    n_no_return: int
+    n_voxel_visits: int
+    n_points_through: int
+    n_points_supported: int
+    sum_through: int
+    sum_support: int
+    radius: float
+    margin: float
+    step: float
+    min_range: float
+    max_range: float
+    device_ms: float
+
+    def dynamic(self, min_through=2, min_fraction=0.5):
+        """`carve_dynamic` of these votes: host policy, not the library's"""
+        return carve_dynamic(self.through, self.support, min_through, min_fraction)
+
+    def lines(self, min_through=2, min_fraction=0.5):
+        """the block the commands print"""
+        n_dyn = int(self.dynamic(min_through, min_fraction).sum())
+        return [f"carve: radius {self.radius:g} m, margin {self.margin:g} m, step {self.step:g} m, range [{self.min_range:g}, {self.max_range:g}] m",
+                f"  sweeps: {self.n_scans} (skipped {self.n_scans_skipped}), rays {self.n_rays} (out of range {self.n_rays_out_of_range}, "
+                f"no return {self.n_no_return}), voxel visits {self.n_voxel_visits}",
+                f"  points: {self.n_points} (passed through {self.n_points_through}, supported {self.n_points_supported}), "
+                f"votes through {self.sum_through}, support {self.sum_support}",
+                f"  dynamic (through >= {int(min_through)}, fraction >= {float(min_fraction):g}): {n_dyn} points"]
+
+
+def carve_cfg(voxel_size, radius=None, margin=None, step=None, min_range=None, max_range=None):
+    """the _lib.CarveCfg of a map of that voxel size: the library's defaults with the given fields on top"""
+    cfg = L.CarveCfg()
+    L.check(L.lib().ptl_carve_default_cfg(C.byref(cfg), float(voxel_size)))
+    for k, v in (("radius", radius), ("margin", margin), ("step", step), ("min_range", min_range), ("max_range", max_range)):
+        if v is not None:
+            setattr(cfg, k, float(v))
+    return cfg
+
+
+class Carver:
+    """Free space carved (include/ptudes_mi.h ptl_carve_*): a second pass over the sweeps that built `map_icp`'s map, posed by
+    the same trajectory, counts for every stored point the rays that went through it and the rays that ended at it.  The map is only read and
+    must not be updated (nor closed) while the carver lives: a map updated since gives a RuntimeError at the next add or read"""
+
+    def __init__(self, map_icp, radius=None, margin=None, step=None, min_range=None, max_range=None):
+        self.map_icp = map_icp
+        self.cfg = carve_cfg(map_icp.cfg.voxel_size, radius, margin, step, min_range, max_range)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_carve_create(map_icp._h, C.byref(self.cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_carve_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_posed(self, traj, col_ts, range_mm=None, lut=None, xyz=None, H=None):
+        """one posed sweep, with the arguments of `Icp.map_add_posed`.  Returns (n_rays, skipped): the sweep's used rays; a sweep with a
+        column outside the trajectory's bounds is skipped as a whole"""
+        t = L.as_f64(col_ts).reshape(-1)
+        nv, sk = C.c_int64(), C.c_int32()
+        if (range_mm is None) == (xyz is None):
+            raise ValueError("give range_mm (with lut) or xyz")
+        if range_mm is not None:
+            if lut is None:
+                raise ValueError("a range image needs its lut")
+            r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+            if r.size != lut.H * lut.W or len(t) != lut.W:
+                raise ValueError("need an H x W range image and one time per column")
+            L.check(L.lib().ptl_carve_add_posed_range(self._h, traj._h, lut._h, r.ctypes.data_as(C.POINTER(C.c_uint32)), L.dptr(t),
+                                                      C.byref(nv), C.byref(sk)))
+        else:
+            x = np.ascontiguousarray(xyz, dtype=np.float32)
+            W = len(t)
+            H = int(H) if H is not None else x.size // (3 * max(W, 1))
+            if x.size != H * W * 3:
+                raise ValueError("need H x W x 3 points and one time per column")
+            L.check(L.lib().ptl_carve_add_posed_xyz(self._h, traj._h, x.ctypes.data_as(C.POINTER(C.c_float)), H, W, L.dptr(t),
+                                                    C.byref(nv), C.byref(sk)))
+        return nv.value, bool(sk.value)
+
+    def add_run(self, runner, traj, t0t1, s=None, first=0, last=None):
+        """the RESIDENT sweeps [first, last] of a SeqRunner (s=None) or of sequence s of a BatchRunner, as `build_map` takes them: no sweep
+        crosses the bus.  Returns (n_rays, n_skipped)"""
+        t = _sweep_times(t0t1, runner.n_scans)
+        last = runner.n_scans - 1 if last is None else int(last)
+        nv, ns = C.c_int64(), C.c_int64()
+        if s is None:
+            L.check(L.lib().ptl_carve_add_seq(self._h, runner._h, traj._h, L.dptr(t), int(first), last, C.byref(nv), C.byref(ns)))
+        else:
+            L.check(L.lib().ptl_carve_add_batch(self._h, runner._h, int(s), traj._h, L.dptr(t), int(first), last, C.byref(nv), C.byref(ns)))
+        return nv.value, ns.value
+
+    def votes(self):
+        """a `CarveVotes` of the sweeps added so far; more may be added and read again"""
+        _, p = self.map_icp.map_size()
+        xyz, thr, sup = np.empty((max(p, 1), 3)), np.zeros(max(p, 1), dtype=np.uint32), np.zeros(max(p, 1), dtype=np.uint32)
+        res, w = L.CarveResult(), C.c_int64()
+        u32p = C.POINTER(C.c_uint32)
+        L.check(L.lib().ptl_carve_read(self._h, C.byref(res), L.dptr(xyz), thr.ctypes.data_as(u32p), sup.ctypes.data_as(u32p), p, C.byref(w)))
+        k = w.value
+        vals = [getattr(res, f) for f, _ in res._fields_]
+        return CarveVotes(xyz[:k].copy(), thr[:k].copy(), sup[:k].copy(), *(int(v) for v in vals[:11]), *(float(v) for v in vals[11:]))
+
+
 def rgba_word(rgba):
     """(..., 4) uint8 R, G, B, A -> the uint32 words the renderer's keys carry (R the lowest byte)"""
     a = np.ascontiguousarray(rgba, dtype=np.uint8)

@@ -11,6 +11,7 @@
 #include "score_kernels.h"
 #include "render_kernels.h"
 #include "compare_kernels.h"
+#include "carve_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -3242,6 +3243,280 @@ extern "C" int ptl_icp_map_compare(ptl_icp* ref, ptl_icp* src, const ptl_map_cmp
         HIPCHK(hipMemcpy(dist2_out, d_d2, (size_t)n * 8, hipMemcpyDeviceToHost));
         if (n_written) *n_written = n;
     }
+    return PTL_OK;
+}
+
+// ================================================================================================ free space carved
+// The definition is in include/ptudes_mi.h, the kernels in carve_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// carve handle owns what its passes need - stream, column table, sweep staging, prefixes, vote arrays, counters - and only reads the map handle.
+struct ptl_carve {
+    int device_id = 0;  // (first member, as in ptl_traj)
+    ptl_icp* map = nullptr;
+    ptl_carve_cfg cfg;
+    int64_t n_points = 0;  // the map's point count at create: every add and read compares
+    int n_alloc = 1;
+    double device_ms = 0;
+    Stream stream;
+    Event e0, e1;
+    double* coltab = nullptr;   // [12][W]
+    double* d_ts = nullptr;     // [W]
+    void* d_raw = nullptr;      // one sweep of the caller's: n_max pixels of f32 xyz or u32 ranges
+    FlyWs* d_fly = nullptr;     // k_fly_coltab's flag
+    int* d_blk_off = nullptr;   // [pool_cap]
+    unsigned *d_through = nullptr, *d_support = nullptr;  // [n_alloc], pool order
+    double* d_xyz = nullptr;    // [n_alloc][3], made by the first read that asks for it
+    unsigned long long* d_counts = nullptr;  // [CARVE_COUNTERS] + 4 of the read's reduction
+    int* d_bad = nullptr;
+    unsigned long long counts[CARVE_COUNTERS] = {};  // the host's copy after the last add
+    DevOwner mem;
+};
+static void carve_defaults(ptl_carve_cfg* cfg, double vs) {
+    PTL_CFG_INIT(cfg);
+    cfg->radius = vs / 10.0; cfg->margin = vs; cfg->step = vs / 2.0; cfg->min_range = 0.0; cfg->max_range = 120.0 * vs;
+}
+extern "C" int64_t ptl_carve_sizeof_cfg(void) { return (int64_t)sizeof(ptl_carve_cfg); }
+extern "C" int ptl_carve_default_cfg(ptl_carve_cfg* cfg, double voxel_size) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_carve_cfg, cfg);
+    if (!(voxel_size > 0.0) || !(voxel_size < 1.0e150)) return set_err(PTL_ERR_ARG, "voxel_size must be positive and finite (got %g)", voxel_size);
+    carve_defaults(cfg, voxel_size);
+    return PTL_OK;
+}
+// the event pair around a piece of the handle's device work, added to its device_ms (the stream has been waited for)
+static int carve_clock(ptl_carve* h) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    h->device_ms += ms;
+    return PTL_OK;
+}
+// the map as it is now: its update waited for, its point count against the snapshot
+static int carve_map_unchanged(ptl_carve* h, const char* who) {
+    ptl_icp* m = h->map;
+    HIPCHK(hipSetDevice(h->device_id));
+    HIPCHK(hipStreamSynchronize(m->map_stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, m->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((int64_t)st.map_points != h->n_points)
+        return set_err(PTL_ERR_STATE, "%s: the map holds %lld points, it held %lld at ptl_carve_create: a map updated since then needs a new carve handle", who,
+                       (long long)st.map_points, (long long)h->n_points);
+    return PTL_OK;
+}
+extern "C" int ptl_carve_create(ptl_icp* map, const ptl_carve_cfg* cfg, ptl_carve** out) {
+    if (!map || !out) return set_err(PTL_ERR_ARG, "ptl_carve_create: null argument");
+    ptl_carve_cfg use;
+    if (cfg) { ABI_CHECK(ptl_carve_cfg, cfg); use = *cfg; } else carve_defaults(&use, map->cfg.voxel_size);
+    const double vs = map->cfg.voxel_size;
+    if (!(use.radius > 0.0) || !(use.radius < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_carve_create: radius = %g: must be positive and finite", use.radius);
+    if (!(use.margin >= 0.0) || !(use.margin < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_carve_create: margin = %g: must be >= 0 and finite", use.margin);
+    if (!(use.step > 0.0) || !(use.step <= vs))
+        return set_err(PTL_ERR_ARG, "ptl_carve_create: step = %g: the march needs 0 < step <= the map's voxel size = %g", use.step, vs);
+    if (!(use.min_range >= 0.0)) return set_err(PTL_ERR_ARG, "ptl_carve_create: min_range = %g: must be >= 0", use.min_range);
+    if (!(use.max_range > use.min_range)) return set_err(PTL_ERR_ARG, "ptl_carve_create: max_range = %g: must be above min_range = %g", use.max_range, use.min_range);
+    if (!(use.max_range / use.step <= (double)CARVE_MAX_SAMPLES))
+        return set_err(PTL_ERR_ARG, "ptl_carve_create: max_range / step = %g / %g = %g samples per ray: the limit is %d", use.max_range, use.step,
+                       use.max_range / use.step, CARVE_MAX_SAMPLES);
+    HIPCHK(hipSetDevice(map->cfg.device_id));
+    std::unique_ptr<ptl_carve> h(new ptl_carve());
+    h->device_id = map->cfg.device_id; h->map = map; h->cfg = use;
+    HIPCHK(h->stream.create());
+    HIPCHK(h->e0.create(hipEventDefault)); HIPCHK(h->e1.create(hipEventDefault));
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    HIPCHK(hipStreamSynchronize(map->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t n = st.map_points;
+    if (n < 0 || n > (int64_t)0x7fffffff) return set_err(PTL_ERR_STATE, "ptl_carve_create: the map reports %lld points", (long long)n);
+    h->n_points = n; h->n_alloc = n > 0 ? (int)n : 1;
+    const Ctx& c = map->c;
+    const int n_chunks = (c.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    const size_t px = (size_t)map->n_max;
+    h->mem.add(&h->coltab, (size_t)12 * c.W); h->mem.add(&h->d_ts, (size_t)c.W);
+    { unsigned char* raw = nullptr; h->mem.add(&raw, px * 12); h->d_raw = raw; }
+    h->mem.add(&h->d_fly, 1); h->mem.add(&h->d_blk_off, (size_t)c.pool_cap);
+    h->mem.add(&h->d_through, (size_t)h->n_alloc); h->mem.add(&h->d_support, (size_t)h->n_alloc);
+    h->mem.add(&h->d_counts, (size_t)CARVE_COUNTERS + 4); h->mem.add(&h->d_bad, 1);
+    HIPCHK(h->mem.err);
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1);
+    HIPCHK(tmp.err);
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->e0, s));
+    HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), s));
+    HIPCHK(hipMemsetAsync(h->d_through, 0, (size_t)h->n_alloc * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_support, 0, (size_t)h->n_alloc * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_counts, 0, ((size_t)CARVE_COUNTERS + 4) * 8, s));
+    HIPCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), s));
+    k_score_count<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    k_carve_blkoff<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_off, h->d_blk_off);
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total != (int)n) return set_err(PTL_ERR_STATE, "ptl_carve_create: the block directory holds %d points, the map state %lld", total, (long long)n);
+    { int rc = carve_clock(h.get()); if (rc) return rc; }
+    *out = h.release();
+    return PTL_OK;
+}
+extern "C" int ptl_carve_destroy(ptl_carve* c) { return c ? handle_destroy(c, c->device_id) : PTL_OK; }
+// what every add checks before any HIP call
+static int carve_check(ptl_carve* h, const ptl_traj* t, const ptl_lut* lut, int64_t H, int64_t W, const char* who) {
+    const ptl_icp* m = h->map;
+    if (t->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: trajectory on device %d, map on device %d", who, t->device_id, h->device_id);
+    if (lut && lut->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: LUT on device %d, map on device %d", who, lut->device_id, h->device_id);
+    if (H < 1 || W < 1) return set_err(PTL_ERR_ARG, "%s: empty scan (%lld x %lld)", who, (long long)H, (long long)W);
+    if (W != m->c.W) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld columns, the map handle's scan_cols is %d", who, (long long)W, m->c.W);
+    if (H * W > m->n_max) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the map handle's max_points_per_scan is %lld", who, (long long)(H * W), (long long)m->n_max);
+    return PTL_OK;
+}
+// one sweep enqueued on the carve handle's stream; raw (device): the sweep; d_col_ts (device, W) or the sweep's (t0, t1)
+static int carve_enqueue(ptl_carve* h, const ptl_traj* t, const void* raw, bool is_range, const ptl_lut* lut, int H, int W, const double* d_col_ts,
+                         double t0, double t1) {
+    const Ctx& c = h->map->c;
+    hipStream_t s = h->stream;
+    const int n = H * W;
+    CarveArgs a = {};
+    a.r2 = h->cfg.radius * h->cfg.radius; a.margin = h->cfg.margin; a.step = h->cfg.step; a.min_range = h->cfg.min_range; a.max_range = h->cfg.max_range;
+    a.blk_off = h->d_blk_off; a.through = h->d_through; a.support = h->d_support; a.n_alloc = h->n_alloc; a.counts = h->d_counts; a.bad = h->d_bad;
+    const int per_wg = (CARVE_THREADS / 64) * (64 / CARVE_LANES);
+    const int wg = (n + per_wg - 1) / per_wg, grid = wg < CARVE_MAX_BLOCKS ? wg : CARVE_MAX_BLOCKS;
+    k_fly_coltab<<<1, 256, 0, s>>>(t->d_kt, t->d_kp, t->n, t->before, t->after, d_col_ts, t0, t1, W, h->coltab, h->d_fly);
+    if (is_range) k_carve_rays<true><<<grid, CARVE_THREADS, 0, s>>>(raw, lut->dir, lut->off, n, W, h->coltab, h->d_fly, c, a);
+    else k_carve_rays<false><<<grid, CARVE_THREADS, 0, s>>>(raw, nullptr, nullptr, n, W, h->coltab, h->d_fly, c, a);
+    HIPCHK(hipGetLastError());
+    return PTL_OK;
+}
+// closes an add: the counters and the table's verdict come back, the host's copy of the counters moves on; the deltas are the call's
+static int carve_finish(ptl_carve* h, int64_t* n_valid, int64_t* n_skipped, const char* who) {
+    unsigned long long now[CARVE_COUNTERS];
+    int bad = 0;
+    HIPCHK(hipEventRecord(h->e1, h->stream));
+    HIPCHK(hipMemcpyAsync(now, h->d_counts, sizeof now, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    { int rc = carve_clock(h); if (rc) return rc; }
+    if (n_valid) *n_valid = (int64_t)(now[CARVE_N_RAYS] - h->counts[CARVE_N_RAYS]);
+    if (n_skipped) *n_skipped = (int64_t)(now[CARVE_N_SKIPPED] - h->counts[CARVE_N_SKIPPED]);
+    memcpy(h->counts, now, sizeof now);
+    if (bad) return set_err(PTL_ERR_STATE, "%s: the map's table led %d probes to a block that does not hold the probed voxel", who, bad);
+    return PTL_OK;
+}
+static int carve_add_percall(ptl_carve* h, ptl_traj* t, ptl_lut* lut, const void* raw_host, size_t raw_bytes, bool is_range, int64_t H, int64_t W,
+                             const double* col_ts, int64_t* n_valid, int32_t* skipped, const char* who) {
+    int rc = carve_check(h, t, lut, H, W, who);
+    if (rc) return rc;
+    rc = carve_map_unchanged(h, who);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(h->e0, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_raw, raw_host, raw_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ts, col_ts, (size_t)W * 8, hipMemcpyHostToDevice, h->stream));
+    rc = carve_enqueue(h, t, h->d_raw, is_range, lut, (int)H, (int)W, h->d_ts, 0.0, 0.0);
+    if (rc) return rc;
+    int64_t sk = 0;
+    rc = carve_finish(h, n_valid, &sk, who);
+    if (skipped) *skipped = sk ? 1 : 0;
+    return rc;
+}
+extern "C" int ptl_carve_add_posed_range(ptl_carve* c, ptl_traj* t, ptl_lut* lut, const uint32_t* range_mm, const double* col_ts, int64_t* n_valid,
+                                         int32_t* skipped) {
+    if (!c || !t || !lut || !range_mm || !col_ts) return set_err(PTL_ERR_ARG, "ptl_carve_add_posed_range: null argument");
+    return carve_add_percall(c, t, lut, range_mm, (size_t)lut->H * lut->W * 4, true, lut->H, lut->W, col_ts, n_valid, skipped, "ptl_carve_add_posed_range");
+}
+extern "C" int ptl_carve_add_posed_xyz(ptl_carve* c, ptl_traj* t, const float* xyz, int32_t H, int32_t W, const double* col_ts, int64_t* n_valid,
+                                       int32_t* skipped) {
+    if (!c || !t || !xyz || !col_ts) return set_err(PTL_ERR_ARG, "ptl_carve_add_posed_xyz: null argument");
+    return carve_add_percall(c, t, nullptr, xyz, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * 12, false, H, W, col_ts, n_valid, skipped, "ptl_carve_add_posed_xyz");
+}
+// resident form, as fly_build: sweeps [first, last] of a lane, `slot` bytes apart.  The caller has checked the runner's side and waited for its
+// streams; the lane is only read.
+static int carve_build(ptl_carve* h, ptl_traj* t, const SeqLane& l, size_t slot, const unsigned char* is_range_k, bool all_range, const ptl_lut* lut,
+                       int64_t pps, const double* t0t1, int64_t first, int64_t last, int64_t* n_valid, int64_t* n_skipped, const char* who) {
+    const int64_t W = h->map->c.W;
+    if (pps % W) return set_err(PTL_ERR_CAPACITY, "%s: %lld points per sweep are no multiple of the map handle's scan_cols = %lld", who, (long long)pps, (long long)W);
+    if (l.icp->c.W != W) return set_err(PTL_ERR_CAPACITY, "%s: the runner's scan_cols is %d, the map handle's %lld", who, l.icp->c.W, (long long)W);
+    int rc = carve_check(h, t, lut, pps / W, W, who);
+    if (rc) return rc;
+    rc = carve_map_unchanged(h, who);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(h->e0, h->stream));
+    for (int64_t k = first; k <= last; ++k) {
+        const bool rg = all_range || (is_range_k && is_range_k[(size_t)k]);
+        rc = carve_enqueue(h, t, (const char*)l.d_scans + (size_t)k * slot, rg, lut, (int)(pps / W), (int)W, nullptr, t0t1[2 * k], t0t1[2 * k + 1]);
+        if (rc) return rc;
+    }
+    return carve_finish(h, n_valid, n_skipped, who);
+}
+extern "C" int ptl_carve_add_seq(ptl_carve* c, ptl_seq* s, ptl_traj* t, const double* t0t1, int64_t first, int64_t last, int64_t* n_valid,
+                                 int64_t* n_skipped) {
+    if (!c || !s || !t || !t0t1) return set_err(PTL_ERR_ARG, "ptl_carve_add_seq: null argument");
+    if (first < 0 || last < first || last >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_carve_add_seq: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)s->cfg.n_scans);
+    if (s->cfg.icp.device_id != c->device_id) return set_err(PTL_ERR_ARG, "ptl_carve_add_seq: runner on device %d, map on device %d", s->cfg.icp.device_id, c->device_id);
+    bool any_range = false;
+    for (int64_t k = first; k <= last; ++k) any_range = any_range || s->is_range[(size_t)k];
+    if (any_range && !s->lut) return set_err(PTL_ERR_STATE, "ptl_carve_add_seq: the sweeps are range images but no LUT was set (ptl_seq_set_lut)");
+    HIPCHK(hipSetDevice(c->device_id));
+    HIPCHK(hipStreamSynchronize(s->stream));  // the runner's own work first; its sweeps are then only read
+    HIPCHK(hipStreamSynchronize(s->ekf_stream));
+    return carve_build(c, t, s->lane, (size_t)s->cfg.points_per_scan * 12, s->is_range.data(), false, any_range ? s->lut : nullptr, s->cfg.points_per_scan,
+                       t0t1, first, last, n_valid, n_skipped, "ptl_carve_add_seq");
+}
+extern "C" int ptl_carve_add_batch(ptl_carve* c, ptl_batch* b, int32_t seq, ptl_traj* t, const double* t0t1, int64_t first, int64_t last,
+                                   int64_t* n_valid, int64_t* n_skipped) {
+    if (!c || !b || !t || !t0t1) return set_err(PTL_ERR_ARG, "ptl_carve_add_batch: null argument");
+    if (seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "ptl_carve_add_batch: sequence %d of %d", seq, b->S);
+    if (first < 0 || last < first || last >= b->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_carve_add_batch: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)b->cfg.n_scans);
+    if (b->cfg.icp.device_id != c->device_id) return set_err(PTL_ERR_ARG, "ptl_carve_add_batch: batch on device %d, map on device %d", b->cfg.icp.device_id, c->device_id);
+    if (b->ring < b->cfg.n_scans) return set_err(PTL_ERR_STATE, "ptl_carve_add_batch: the batch keeps a ring of %lld sweep slots (resident_scans): earlier sweeps are gone", (long long)b->ring);
+    if (b->cfg.range_input && !b->lut) return set_err(PTL_ERR_STATE, "ptl_carve_add_batch: a range-input batch needs its LUT (ptl_batch_set_lut)");
+    HIPCHK(hipSetDevice(c->device_id));
+    HIPCHK(hipStreamSynchronize(b->stream));  // the batch's own work first; its sweeps are then only read
+    HIPCHK(hipStreamSynchronize(b->side));
+    const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
+    return carve_build(c, t, b->lane[seq], slot, nullptr, b->is_range != 0, b->is_range ? b->lut : nullptr, b->cfg.points_per_scan, t0t1, first, last,
+                       n_valid, n_skipped, "ptl_carve_add_batch");
+}
+extern "C" int ptl_carve_read(ptl_carve* h, ptl_carve_result* result, double* xyz_out, uint32_t* through_out, uint32_t* support_out, int64_t max_points,
+                              int64_t* n_written) {
+    if (!h || !result) return set_err(PTL_ERR_ARG, "ptl_carve_read: null argument");
+    const int given = (xyz_out != nullptr) + (through_out != nullptr) + (support_out != nullptr);
+    if (given != 0 && given != 3) return set_err(PTL_ERR_ARG, "ptl_carve_read: the three per-point arrays (xyz, through, support) are given together or not at all (%d given)", given);
+    if (given && max_points < 0) return set_err(PTL_ERR_ARG, "ptl_carve_read: max_points = %lld: must not be negative", (long long)max_points);
+    const int64_t n = h->n_points;
+    if (given && max_points < n) return set_err(PTL_ERR_CAPACITY, "ptl_carve_read: the map holds %lld points, max_points = %lld", (long long)n, (long long)max_points);
+    { int rc = carve_map_unchanged(h, "ptl_carve_read"); if (rc) return rc; }
+    if (n_written) *n_written = 0;
+    hipStream_t s = h->stream;
+    if (given && n > 0 && !h->d_xyz) HIPCHK(h->mem.alloc(&h->d_xyz, (size_t)n * 3));
+    unsigned long long sums[4] = {0, 0, 0, 0};
+    HIPCHK(hipEventRecord(h->e0, s));
+    k_carve_reduce<<<1, 1024, 0, s>>>(h->d_through, h->d_support, (int)n, h->d_counts + CARVE_COUNTERS);
+    if (given && n > 0) k_carve_export<<<(h->map->c.pool_cap + 255) / 256, 256, 0, s>>>(h->map->c, h->d_blk_off, h->n_alloc, h->d_xyz);
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, h->d_counts + CARVE_COUNTERS, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    { int rc = carve_clock(h); if (rc) return rc; }
+    memset(result, 0, sizeof *result);
+    result->n_points = n;
+    result->n_scans = (int64_t)h->counts[CARVE_N_SCANS]; result->n_scans_skipped = (int64_t)h->counts[CARVE_N_SKIPPED];
+    result->n_rays = (int64_t)h->counts[CARVE_N_RAYS]; result->n_rays_out_of_range = (int64_t)h->counts[CARVE_N_OOR];
+    result->n_no_return = (int64_t)h->counts[CARVE_N_NORET]; result->n_voxel_visits = (int64_t)h->counts[CARVE_N_VISITS];
+    result->n_points_through = (int64_t)sums[0]; result->n_points_supported = (int64_t)sums[1];
+    result->sum_through = (int64_t)sums[2]; result->sum_support = (int64_t)sums[3];
+    result->radius = h->cfg.radius; result->margin = h->cfg.margin; result->step = h->cfg.step;
+    result->min_range = h->cfg.min_range; result->max_range = h->cfg.max_range;
+    result->device_ms = h->device_ms;
+    if (given && n > 0) {
+        HIPCHK(hipMemcpy(xyz_out, h->d_xyz, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(through_out, h->d_through, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(support_out, h->d_support, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    if (given && n_written) *n_written = n;
     return PTL_OK;
 }
 

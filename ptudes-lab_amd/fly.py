@@ -95,6 +95,18 @@ def compare_handle(map_icp, reference, thresholds=DEFAULT_COMPARE_THRESHOLDS, ma
         ref.close()
 
 
+def carved_handle(map_icp, mask, xyz):
+    """a new map handle (core.Icp) that holds the points of `xyz` (N, 3) that `mask` (N,) does not flag, with `map_icp`'s voxel size, points
+    per voxel, scan geometry and capacities (core.map_from_points)"""
+    mask, pts = np.asarray(mask, dtype=bool).reshape(-1), np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    if len(mask) != len(pts):
+        raise ValueError("one flag per point")
+    c = map_icp.cfg
+    return core.map_from_points(pts[~mask], voxel_size=c.voxel_size, max_points_per_voxel=c.max_points_per_voxel, device_id=c.device_id,
+                                max_points_per_scan=max(int(c.max_points_per_scan), 1 << 16), scan_cols=c.scan_cols,
+                                map_block_capacity=c.map_block_capacity, map_table_capacity=c.map_table_capacity)
+
+
 class MapAccumulator:
     """Accumulates posed scans into a world-frame voxel map on the GPU (ScansAccumulator's map, deterministic form)."""
 
@@ -167,6 +179,48 @@ class MapAccumulator:
         MapAccumulator) whose map is the reference, or an (N, 3) array - a reference handle is then built for the call at this map's voxel
         size and points per voxel, so a cloud this map wrote reloads completely.  max_dist defaults to the voxel size"""
         return compare_handle(self._icp, reference, thresholds, max_dist, per_point, reference_name)
+
+    def carved(self, mask, xyz):
+        """a NEW accumulator whose map holds the points of `xyz` (N, 3) that `mask` (N,) does not flag - `xyz` the stored points as a carve
+        lists them (core.CarveVotes.xyz, pool order), `mask` e.g. CarveVotes.dynamic().  Built by core.map_from_points with this map's voxel
+        size, points per voxel and capacities: the kept points are a subset of the stored ones, so the new map holds all of them.  This
+        accumulator stays as it is"""
+        out = MapAccumulator.__new__(MapAccumulator)
+        out.lut, out.scans, out.returns, out.skipped = self.lut, self.scans, self.returns, self.skipped
+        out._icp = carved_handle(self._icp, mask, xyz)
+        return out
+
+
+class MapCarver:
+    """The second pass over the sweeps that built `acc`'s map: a core.Carver on the accumulator's map handle, fed the way the
+    accumulator was.  cfg: radius, margin, step, min_range, max_range (defaults: the library's for the map's voxel size).  The map must not be
+    updated while the carver lives"""
+
+    def __init__(self, acc, **cfg):
+        self.acc = acc
+        self.carver = core.Carver(acc.icp, **cfg)
+
+    def update(self, scan, traj):
+        """one PosedScan or packets.PacketScan, posed by `traj` (a core.Traj) at its column timestamps, as MapAccumulator.update(scan, traj)
+        adds it.  Returns the sweep's used rays (0 for a sweep skipped as outside the bounds)"""
+        range_mm = scan.range_mm if hasattr(scan, "range_mm") else scan.range
+        n_rays, _ = self.carver.add_posed(traj, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9, range_mm=range_mm, lut=self.acc.lut)
+        return n_rays
+
+    def add_run(self, runner, traj, t0t1, s=None, first=0, last=None):
+        """the RESIDENT sweeps [first, last] of a core.SeqRunner (s=None) or of sequence s of a core.BatchRunner, as MapAccumulator.add_run"""
+        return self.carver.add_run(runner, traj, t0t1, s=s, first=first, last=last)
+
+    def votes(self):
+        return self.carver.votes()
+
+    def carved(self, min_through=2, min_fraction=0.5):
+        """(the accumulator without the points the host policy flags, the votes): MapAccumulator.carved of CarveVotes.dynamic"""
+        v = self.votes()
+        return self.acc.carved(v.dynamic(min_through, min_fraction), v.xyz), v
+
+    def close(self):
+        self.carver.close()
 
 
 # ------------------------------------------------------------------------------------------------ the camera path (DESIGN.md 3.21)
@@ -468,6 +522,20 @@ def add_packet_bag(acc, bags, info, traj, start_scan=0, end_scan=None, device_id
         for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
             if not hasattr(d, "lacc"):
                 acc.update(d, traj=traj)
+    finally:
+        feed.close()
+
+
+def carve_packet_bag(carver, bags, info, traj, start_scan=0, end_scan=None, device_id=0):
+    """the counterpart of `add_packet_bag` for a `MapCarver`: the same sweeps of the same bag(s), decoded again by the package's packet feed
+    and posed by `traj` at their decoded column times"""
+    from . import packets as pk
+    from .bag import OusterPacketBagSource
+    feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info, device_id=device_id)
+    try:
+        for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+            if not hasattr(d, "lacc"):
+                carver.update(d, traj)
     finally:
         feed.close()
 

@@ -246,6 +246,8 @@ _PLY_SCALARS = (("int", "neighbours"), ("double", "plane_var"), ("double", "entr
 _PLY_XYZ = [("double", "x"), ("double", "y"), ("double", "z")]
 _PLY_SCORED_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("neighbours", "<i4"), ("plane_var", "<f8"), ("entropy", "<f8")])
 _PLY_DIST_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("dist", "<f8")])
+_PLY_CARVE = (("uint", "through"), ("uint", "support"), ("uchar", "dynamic"))
+_PLY_CARVE_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("through", "<u4"), ("support", "<u4"), ("dynamic", "u1")])
 
 
 def save_map_ply(path: str, xyz, scalars=None) -> None:
@@ -254,8 +256,24 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
     scalars = (neighbours (N,) int, plane_var (N,), entropy (N,)) - the per-point values of a map score: three more
     properties behind x y z (`int neighbours`, `double plane_var`, `double entropy`); PLY only (a .npy map is the points and nothing else).
     scalars = {"dist": (N,)} - the per-point distance to a reference cloud (NaN = unmatched): one more property, `double dist`.
+    scalars = {"through": (N,), "support": (N,), "dynamic": (N,)} - the votes of a carve and the host policy's flag: `uint
+    through`, `uint support`, `uchar dynamic`.
     Without scalars the file is what it always was, byte for byte."""
     pts = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+    if isinstance(scalars, dict) and list(scalars) == ["through", "support", "dynamic"]:
+        # the votes of a carve (DESIGN.md 3.24): `uint through`, `uint support`, `uchar dynamic` (the host policy's flag) behind x y z
+        cols = [np.asarray(scalars[k]).reshape(-1) for k in scalars]
+        if any(len(c) != len(pts) for c in cols):
+            raise ValueError("scalars: one through / support / dynamic value per point")
+        if str(path).endswith(".npy"):
+            raise ValueError("per-point scalars are written to a PLY file only: a .npy map holds the points")
+        rec = np.empty(len(pts), dtype=_PLY_CARVE_DTYPE)
+        rec["xyz"], rec["through"], rec["support"], rec["dynamic"] = pts, cols[0], cols[1], cols[2]
+        extra = "".join(f"property {t} {name}\n" for t, name in _PLY_CARVE)
+        with open(path, "wb") as f:
+            f.write(_PLY_HEADER.format(n=len(pts)).replace("end_header\n", extra + "end_header\n").encode("ascii"))
+            f.write(rec.tobytes())
+        return
     if isinstance(scalars, dict):
         if list(scalars) != ["dist"] or len(np.asarray(scalars["dist"]).reshape(-1)) != len(pts):
             raise ValueError("scalars: a dict holds `dist`, one value per point")
@@ -291,7 +309,7 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
 def load_map_ply(path: str, scalars: bool = False):
     """(N, 3) float64 of a map written by `save_map_ply` (.npy: np.load), with or without per-point scalars.  Reads the PLY subset that
     function writes.  scalars=True: (points, (neighbours int32, plane_var, entropy)), the second None for a file without them and
-    {"dist": (N,)} for a file with the distance to a reference cloud."""
+    {"dist": (N,)} for a file with the distance to a reference cloud, {"through", "support", "dynamic"} for a file with a carve's votes."""
     if str(path).endswith(".npy"):
         pts = np.load(path).reshape(-1, 3)
         return (pts, None) if scalars else pts
@@ -315,6 +333,14 @@ def load_map_ply(path: str, scalars: bool = False):
             raise ValueError(f"{path}: no end_header")
         scored = props == _PLY_XYZ + list(_PLY_SCALARS)
         with_dist = props == _PLY_XYZ + [("double", "dist")]
+        if props == _PLY_XYZ + list(_PLY_CARVE) and fmt == "binary_little_endian" and n is not None:
+            size = _PLY_CARVE_DTYPE.itemsize
+            data = f.read(n * size)
+            if len(data) != n * size:
+                raise ValueError(f"{path}: {n} vertices announced, {len(data) // size} present")
+            rec = np.frombuffer(data, dtype=_PLY_CARVE_DTYPE)
+            pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
+            return (pts, {k: rec[k].copy() for _, k in _PLY_CARVE}) if scalars else pts
         if with_dist and fmt == "binary_little_endian" and n is not None:
             data = f.read(n * 32)
             if len(data) != n * 32:
