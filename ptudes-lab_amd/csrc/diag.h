@@ -67,6 +67,12 @@ constexpr int flavours = (phases ? 1 : 0) | (it0 ? 2 : 0) | (stages ? 4 : 0) | (
     X(phase_a_eval, 1) X(phase_a_compact, 1) X(phase_a_chunks, 1) X(search_pass_ticks, 1) X(search_passes, 1)                              \
     /* PHASES, gn8_search, thread 0 of the first teams' workgroups, iterations > 0, every step waited out */                               \
     X(search_row_key, 1) X(search_rebuild, 1) X(search_first_round, 1) X(search_survivors, 1) X(search_answer_row, 1) X(searches_timed, 1) \
+    /* ... the same laps, same thread, in a scan's FIRST iteration (every point searches and rebuilds its row; same order as the set   */    \
+    /* above: gn8_search adds one offset), and over all workgroups the first iteration's searches and survivor rounds */                  \
+    X(search_it0_row_key, 1) X(search_it0_rebuild, 1) X(search_it0_first_round, 1) X(search_it0_survivors, 1) X(search_it0_answer_row, 1)  \
+    X(searches_timed_it0, 1) X(searches_it0, 1) X(survivor_rounds_it0, 1)                                                                  \
+    /* PHASES, gn8_search, all workgroups: searches whose place in the queue (front: row valid | back: rebuild) disagrees with pc_key[] */ \
+    X(queue_kind_mismatch, 1)                                                                                                              \
     /* PHASES, serial tail of an iteration, workgroup 0 */                                                                                 \
     X(tail_sums, 1) X(tail_solve, 1) X(tail_exp_flags, 1) X(tails, 1)                                                                      \
     /* PHASES, workgroup 0, iterations > 0: why the answer row did not settle a point, and the searches by iteration index */              \

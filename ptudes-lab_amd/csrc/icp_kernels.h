@@ -168,7 +168,8 @@ struct Ctx {
     double* traj;        // [T][16] kiss poses
     ScanStats* sstats;   // [T]
     const double* ext_guess;  // device 4x4 or null
-    unsigned long long* pc_key;  // [n_max]      multi-pass probe cache: voxel key of source point i at its last probe
+    unsigned long long* pc_key;  // [n_max]      multi-pass probe cache: voxel key of source point i at its last probe (the 32-lane loop; the 8-lane
+                                 //              search takes the key from its answer row and keeps this one in a PHASES build only: diag.h queue_kind_mismatch)
     int* pc_pb;                  // [n_max][32]  and the 27 probe results (block id | count << 24, -1 = absent)
     double* pc_ans;              // [n_max][GN8_ANS_ROW]  8-lane kernel: exact answer cache (s0 | the K nearest candidates | distance bound of the others | order ids, counts)
     unsigned long long* gn_rows_ll;  // [2][G][64]      per-workgroup sums as (32 data bits | 32 flag bits) words
@@ -1718,8 +1719,9 @@ __global__ __launch_bounds__(GN_MAX_THREADS) void k_gn_loop(Ctx c, int mode) {
 //     go straight into the lane's sums;
 //   * the others are compacted in point order (deterministic) and get the full 27-voxel search with 8 lanes per point
 //     (gn8_search): 128-byte probe row per point in memory (lane l holds entries 4 l .. 4 l + 3; entry 27 = the voxel of
-//     the last winner, entry 28 = the candidate count of the 27 voxels), box distances from the point alone, first round
-//     = own + last winner's + the two nearest other voxels with every load in flight together (lane l <-> stored points
+//     the last winner, entry 28 = the candidate count of the 27 voxels; a point that changed voxel is queued at the back
+//     and rebuilds its row without reading it), box distances from the point alone, first round = own + last winner's (or,
+//     without one outside the own voxel, the third-nearest) + the two nearest other voxels with every load in flight together (lane l <-> stored points
 //     l, l + 8, l + 16), the rest exactly pruned as in nn_scan32, group reductions by DPP;
 //   * the SAME correspondence, distance, gate and weight for every point as the 32-lane kernel; the linear system is
 //     accumulated as 16 moments sum w z_a z_b over z = (1, s, r, s x r) per lane instead of 27 products picked per lane:
@@ -1847,18 +1849,21 @@ __device__ __forceinline__ void scan_voxelsL(const CT& c, const int (&pb)[NV], c
         }
     }
 }
-// The full 27-voxel search of source point i at s by a group of LP lanes (all of them call it): probe row (re-probed when
-// the point changed voxel), box distances, first round = own voxel + last winner's voxel (+ the two nearest other boxes
+// The full 27-voxel search of source point i at s by a group of LP lanes (all of them call it): probe row (rebuild, uniform
+// over the group: the point changed voxel since its last search, or this is a scan's first iteration - phase A of gn8_body
+// has decided it from the key in the answer row and queued the point by kind; such a group sends its 27 table probes at
+// once, the others read their row), box distances, first round = own voxel + last winner's voxel (+ the two nearest other boxes
 // when LP == 8), the remaining voxels exactly pruned and scanned two at a time, the new answer row.  Returns in every
 // lane the neighbour, its squared distance, found, and the candidate count of the 27 voxels.
 // xc: the workgroup's executed-work counters in LDS ([1] probe rows rebuilt, [2] stored points read; DevState::exec_cnt)
 __device__ __forceinline__ unsigned pb_count(int pb) { return pb < 0 ? 0u : (unsigned)pb >> 24; }
 template <int PC, int LP>
-__device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, double inv_vs, int laneL, int gb, V3& t, double& m, bool& found, int& ctot,
-                                           unsigned* xc) {
+__device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, bool rebuild, V3 s, double inv_vs, int laneL, int gb, V3& t, double& m, bool& found,
+                                           int& ctot, unsigned* xc) {
     constexpr int RE = 32 / LP;  // row entries per lane
-    // (the lap timer runs in thread 0 of workgroup 0 of the sequences on the first teams)
-    [[maybe_unused]] const bool srch_me = diag::phases && it > 0 && blockIdx.x < 8 && threadIdx.x == 0;
+    // (the lap timer runs in thread 0 of workgroup 0 of the sequences on the first teams; a scan's first iteration has slots of its own)
+    [[maybe_unused]] const bool srch_me = diag::phases && blockIdx.x < 8 && threadIdx.x == 0;
+    [[maybe_unused]] const int lap0 = it > 0 ? 0 : D_search_it0_row_key - D_search_row_key;
     [[maybe_unused]] DiagLap<diag::phases, true, true> srch(srch_me);
     int kx, ky, kz;
     voxel_index(s, c.vs, inv_vs, kx, ky, kz);
@@ -1866,14 +1871,16 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
     int r[RE];
 #pragma unroll
     for (int k = 0; k < RE; ++k) r[k] = -1;
-    if (it > 0) {  // (uniform; a scan's first iteration rebuilds every row: nothing to read, nothing to wait for)
-        const int4* rp = (const int4*)(c.pc_pb + 32 * (size_t)i + RE * laneL);  // (requested together with the key that validates it)
+    if constexpr (diag::phases) {  // (cross-check of the queue's kinds: pc_key[i] is kept up to date in this build only)
+        if (laneL == 0 && rebuild != !(it > 0 && c.pc_key[i] == key)) diag_add<true>(c, D_queue_kind_mismatch);
+    }
+    if (!rebuild) {  // (a row that is rebuilt is overwritten entry by entry: nothing to read, nothing to wait for)
+        const int4* rp = (const int4*)(c.pc_pb + 32 * (size_t)i + RE * laneL);
 #pragma unroll
         for (int k = 0; k < RE / 4; ++k) { const int4 v = rp[k]; r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w; }
     }
-    const bool same_voxel = it > 0 && c.pc_key[i] == key;
-    if constexpr (diag::phases) { srch.lap(c, D_search_row_key); }  // row + key
-    if (!same_voxel) {  // uniform over the group: probe this lane's neighbour voxels, rebuild the row
+    if constexpr (diag::phases) { srch.lap(c, lap0 + D_search_row_key); }  // row
+    if (rebuild) {  // uniform over the group: probe this lane's neighbour voxels, rebuild the row
         int cs = 0;
         {   // this lane's RE probes with their first table reads in flight together; a collision walks on by itself
             unsigned long long kq[RE];
@@ -1918,9 +1925,12 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         int4* wp = (int4*)(c.pc_pb + 32 * (size_t)i + RE * laneL);
 #pragma unroll
         for (int k = 0; k < RE / 4; ++k) wp[k] = make_int4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
-        if (laneL == 0) { c.pc_key[i] = key; atomicAdd(xc + 1, 1u); }
+        if (laneL == 0) {
+            if constexpr (diag::phases) c.pc_key[i] = key;  // (nothing of the 8-lane kernel reads it: the reference of the cross-check above)
+            atomicAdd(xc + 1, 1u);
+        }
     }
-    if constexpr (diag::phases) { srch.lap(c, D_search_rebuild); }  // rebuild (some group of the wavefront changed voxel)
+    if constexpr (diag::phases) { srch.lap(c, lap0 + D_search_rebuild); }  // rebuild (some group of the wavefront changed voxel)
     const int lv_raw = __shfl(r[27 % RE], gb + 27 / RE);
     ctot = __shfl(r[28 % RE], gb + 28 / RE);
     const int lv = (lv_raw != 13) ? lv_raw : -1;
@@ -1956,23 +1966,29 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
     }
     if (LP == 8 && GN8_SPEC > 0) {
         // first round: the own voxel, the last winner's and the two nearest other boxes, all loads in flight together (a
-        // voxel scanned although its box turns out to lie beyond the best distance is harmless: it is one of the 27)
+        // voxel scanned although its box turns out to lie beyond the best distance is harmless: it is one of the 27).
+        // Without a last winner outside the own voxel (lv < 0: every rebuilt row, and every row whose winner lay in the own
+        // voxel) the second slot takes the NEXT nearest box instead of nothing: one more round of the same selection, no
+        // load, register or voxel more than the round carries anyway, and a box less that may need a survivor round.
         constexpr int NS = GN8_SPEC > 0 ? GN8_SPEC : 1;  // nearest other boxes taken along
         int pbN[2 + NS], vxN[2 + NS];
         pbN[0] = pbc; pbN[1] = pbl; vxN[0] = 13; vxN[1] = lv;
         unsigned npts = pb_count(pbc) + pb_count(pbl);
 #pragma unroll
-        for (int u = 0; u < NS; ++u) {
+        for (int u = 0; u < NS + 1; ++u) {
             double gl = 1.7976931348623157e308;
             int ql = 0;
 #pragma unroll
             for (int q = 0; q < RE; ++q) if (gap2[q] < gl) { gl = gap2[q]; ql = q; }
             const double gmin = group_minL<LP>(gl);
-            const unsigned v = group_minL<LP>((gl == gmin && gmin < 1.0e300) ? (unsigned)(RE * laneL + ql) : 0xFFu);
-            vxN[2 + u] = (v == 0xFFu) ? -1 : (int)v;
-            pbN[2 + u] = (v == 0xFFu) ? -1 : __shfl(sel_entry<RE>(r, (int)(v % RE)), gb + (int)((v / RE) & (LP - 1)));
-            npts += pb_count(pbN[2 + u]);
-            if (v != 0xFFu && (int)(v / RE) == laneL) {
+            unsigned v = group_minL<LP>((gl == gmin && gmin < 1.0e300) ? (unsigned)(RE * laneL + ql) : 0xFFu);
+            if (u == NS && lv >= 0) v = 0xFFu;  // (the slot is the last winner's: the box stays a candidate of the survivor rounds)
+            const int vxu = (v == 0xFFu) ? -1 : (int)v;
+            const int pbu = (v == 0xFFu) ? -1 : __shfl(sel_entry<RE>(r, (int)(v % RE)), gb + (int)((v / RE) & (LP - 1)));
+            if (u < NS) { vxN[2 + u] = vxu; pbN[2 + u] = pbu; }
+            else if (lv < 0) { vxN[1] = vxu; pbN[1] = pbu; }
+            npts += pb_count(pbu);
+            if (v != 0xFFu && (int)(v / RE) == laneL) {  // struck from the candidates: a voxel is scanned once
 #pragma unroll
                 for (int q = 0; q < RE; ++q) if (q == (int)(v % RE)) gap2[q] = 1.7976931348623157e308;
             }
@@ -1984,7 +2000,7 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         if (laneL == 0) atomicAdd(xc + 2, pb_count(pbc) + pb_count(pbl));
         scan_voxelsL<PC, LP, 2>(c, pb2, vx2, s, laneL, bd, sd, border, bp, b2d, b2o, b2p);
     }
-    if constexpr (diag::phases) { srch.lap(c, D_search_first_round); }  // box distances + first round
+    if constexpr (diag::phases) { srch.lap(c, lap0 + D_search_first_round); }  // box distances + first round
     // the other voxels: dropped when their box lies farther than the best distance so far (exact, see nn_scan32)
     unsigned mine = 0u;
     double gdrop = 1.7976931348623157e308;  // smallest squared box distance among the voxels this lane dropped
@@ -2009,12 +2025,12 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
             npts += pb_count(pbS[j]);
         }
         if (vxS[0] == 0xFF) break;
-        if constexpr (diag::phases) { if (laneL == 0) diag_add<true>(c, D_survivor_rounds); }
+        if constexpr (diag::phases) { if (laneL == 0) { diag_add<true>(c, D_survivor_rounds); if (it == 0) diag_add<true>(c, D_survivor_rounds_it0); } }
         if (laneL == 0) atomicAdd(xc + 2, npts);
         scan_voxelsL<PC, LP, GN8_SURV>(c, pbS, vxS, s, laneL, bd, sd, border, bp, b2d, b2o, b2p);
     }
-    if constexpr (diag::phases) { if (laneL == 0) { diag_add<true>(c, D_searches); if (!same_voxel) diag_add<true>(c, D_rows_rebuilt); } }
-    if constexpr (diag::phases) { srch.lap(c, D_search_survivors); }  // survivors
+    if constexpr (diag::phases) { if (laneL == 0) { diag_add<true>(c, D_searches); if (it == 0) diag_add<true>(c, D_searches_it0); if (rebuild) diag_add<true>(c, D_rows_rebuilt); } }
+    if constexpr (diag::phases) { srch.lap(c, lap0 + D_search_survivors); }  // survivors
     // ---- the group's GN8_KCAND nearest candidates in (distance, visiting order) order.  Every lane holds its own two nearest
     // (bd / b2d) and the smallest distance that lost to both (sd): K rounds of "every lane offers the nearest it has not
     // given yet, the group's minimum takes it"; what is left - the lanes' next offers, sd, the boxes of the dropped voxels -
@@ -2068,10 +2084,10 @@ __device__ __forceinline__ void gn8_search(const Ctx& c, int i, int it, V3 s, do
         arow[GN8_ANS_D] = sl2;
         meta |= (unsigned long long)(unsigned)ctot << 50 | (unsigned long long)(unsigned)nvalid << 60;
         arow[GN8_ANS_D + 1] = __longlong_as_double((long long)meta);
-        arow[GN8_ANS_D + 2] = __longlong_as_double((long long)key);  // (= pc_key[i]: the voxel this search looked around)
+        arow[GN8_ANS_D + 2] = __longlong_as_double((long long)key);  // (the voxel this search looked around: phase A's test of the row)
     }
-    if constexpr (diag::phases) { srch.lap(c, D_search_answer_row); }  // reductions + answer row
-    if constexpr (diag::phases) { if (srch_me) diag_add<true>(c, D_searches_timed); }
+    if constexpr (diag::phases) { srch.lap(c, lap0 + D_search_answer_row); }  // reductions + answer row
+    if constexpr (diag::phases) { if (srch_me) diag_add<true>(c, lap0 + D_searches_timed); }
 }
 
 // packed upper triangle of JTJ (21) + JTr (6) from the 16 moments
@@ -2388,15 +2404,13 @@ __device__ __forceinline__ void gn8_body(const Ctx& c_in, int mode, const int G_
                     int ctot;
                     // (diagnostic) why did the answer row not settle this point?  (wg 0, iterations > 0): voxel changed | same neighbour again | another one
                     [[maybe_unused]] double old_t[3] = {0, 0, 0}, old_sl = -1.0;
-                    [[maybe_unused]] bool old_same_key = false;
+                    const bool rebuild = !(k < nfront);  // the kind phase A queued the point by (uniform over the group: kback0 is a multiple of 8)
+                    [[maybe_unused]] const bool old_same_key = !rebuild;
                     if constexpr (diag::phases) if (wg == 0 && it > 0 && laneL == 0) {
-                        int kx0, ky0, kz0;
-                        voxel_index(s, c.vs, inv_vs, kx0, ky0, kz0);
-                        old_same_key = c.pc_key[i] == pack_key(kx0, ky0, kz0);
                         old_t[0] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 3]; old_t[1] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 4]; old_t[2] = c.pc_ans[GN8_ANS_ROW * (size_t)i + 5];
                         old_sl = c.pc_ans[GN8_ANS_ROW * (size_t)i + GN8_ANS_D];
                     }
-                    gn8_search<PC, LPB>(c, i, it, s, inv_vs, laneL, gb, t, m, found, ctot, xcnt);
+                    gn8_search<PC, LPB>(c, i, it, rebuild, s, inv_vs, laneL, gb, t, m, found, ctot, xcnt);
                     if constexpr (diag::phases) if (wg == 0 && it > 0 && laneL == 0)
                         diag_add<true>(c, !old_same_key ? D_miss_voxel_changed : (old_sl < 0.0) ? D_miss_no_answer
                                           : (found && t.x == old_t[0] && t.y == old_t[1] && t.z == old_t[2]) ? D_miss_same_neighbour : D_miss_other_neighbour);

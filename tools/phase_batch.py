@@ -46,6 +46,12 @@ try:
     if D["searches_timed"] > 0:
         print("one search (thread 0 of the first teams' workgroup 0, iterations > 0, every step waited out), ticks: row + key %.0f | rebuild %.0f | boxes + first round %.0f | survivors %.0f | reductions + answer row %.0f   (%d searches)"
               % tuple([D["search_" + k] / D["searches_timed"] for k in ("row_key", "rebuild", "first_round", "survivors", "answer_row")] + [int(D["searches_timed"])]))
+    if D.get("searches_timed_it0", 0) > 0:
+        print("one search of a scan's FIRST iteration (same thread; every point searches and rebuilds its row), ticks: row %.0f | rebuild %.0f | boxes + first round %.0f | survivors %.0f | reductions + answer row %.0f   (%d searches);  survivor rounds per search: first iteration %.2f, later iterations %.2f"
+              % tuple([D["search_it0_" + k] / D["searches_timed_it0"] for k in ("row_key", "rebuild", "first_round", "survivors", "answer_row")] + [int(D["searches_timed_it0"])]
+                      + [D["survivor_rounds_it0"] / max(D["searches_it0"], 1), (D["survivor_rounds"] - D["survivor_rounds_it0"]) / max(D["searches"] - D["searches_it0"], 1)]))
+    if "queue_kind_mismatch" in D:
+        print("searches whose place in the queue disagrees with pc_key[]: %d of %d" % (int(D["queue_kind_mismatch"]), int(D["searches"])))
     if D["bound_candidate"] + D["bound_box"] > 0:
         bound, ratio = D["bound_candidate"] + D["bound_box"], np.array([D["bound_ratio_%d" % i] for i in range(5)])
         print("bound of the others after a search: third-nearest candidate %.1f %%, box of a dropped voxel %.1f %%;  bound / winner's distance in [1,1.2) [1.2,1.5) [1.5,2) [2,3) [3,..): %s %%"
