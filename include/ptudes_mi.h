@@ -471,7 +471,8 @@ int ptl_batch_debug_set_map_points_per_thread(ptl_batch *b, int32_t points, int3
  * and pass of K1 + map update / K2-K4 in the free-running kernel, [5] threads per workgroup of the 8-lane kernels,
  * [6] lanes per point of the full search, [7] nearest other boxes in its first round, [8] voxels per survivor round,
  * [9] chunks phase A requests ahead, [10] 1000 x the pruning margin, [11] / [12] bytes per map-table / voxel-table
- * entry, [13] the diagnostic flavours compiled in, a bit each: 1 PHASES, 2 IT0, 4 STAGES, 8 MAP_DIAG (0 = the product build), [14] reserved (0; rounds 5's movement-budget experiment is gone from the sources). */
+ * entry, [13] the diagnostic flavours compiled in, a bit each: 1 PHASES, 2 IT0, 4 STAGES, 8 MAP_DIAG (0 = the product build), [14] reserved (0; rounds 5's movement-budget experiment is gone from the sources),
+ * [15] candidates that ptl_icp_pose_hits stages and processes at a time. */
 int ptl_build_info(int32_t out[16]);
 /* identity of what THIS library was built from: sha256 over the kernel sources, the Makefile and the experiment flags (12 hex digits,
  * csrc/Makefile CODE_ID).  bench.py records it in its line and tools/pmc_summary.py in every counter summary: a counter pass speaks
@@ -868,6 +869,55 @@ int ptl_carve_add_batch(ptl_carve *c, ptl_batch *b, int32_t seq, ptl_traj *t, co
  * may be added and read again. */
 int ptl_carve_read(ptl_carve *c, ptl_carve_result *result, double *xyz_out, uint32_t *through_out, uint32_t *support_out, int64_t max_points,
                    int64_t *n_written);
+
+/* ------------------------------------------------------------------------------------------------
+ * A sweep's fit to a map at each of K candidate poses (no reference counterpart): the search half of finding the sensor in a
+ * saved map - ptl_icp_align is the refinement half.  K poses x n points are evaluated resident; K x n_thresholds integers come back.
+ * Per candidate k (row-major 4 x 4 fp64; the top three rows are used as given, nothing is re-orthonormalised) and query point q_i (sensor frame):
+ * wx = ((r00 qx + r01 qy) + r02 qz) + tx, wy and wz likewise, fp64 in that order without contraction; d2(w) is ptl_icp_map_distance's - the
+ * minimum over all stored points of (dx dx + dy dy) + dz dz with the same neighbourhood and key-range rule; hits[k][j] = the number of i with
+ * d2 <= thresholds[j] thresholds[j] (the products made once, as doubles).  A query point with a non-finite coordinate is never a hit and is
+ * counted once in n_invalid_points; a candidate with a non-finite entry in its top three rows takes no probe, gets hits = -1 at every threshold
+ * and is counted in n_invalid_poses; a transformed point that is not finite or lies outside the key range is not a hit.  Counts of integers have
+ * no order: every output is an exact function of the set of stored points, the query set and the pose.
+ * best_hits[j] / best_pose[j]: the largest hits[.][j] over the valid candidates and the SMALLEST candidate index that attains it; without a valid
+ * candidate (n_poses = 0 included) best_pose[j] = -1 and best_hits[j] = 0, as for j >= n_thresholds.
+ * Parameters: 0 < max_dist <= the map's voxel size, 1 .. 4 thresholds, ascending (equal neighbours allowed), each in (0, max_dist].  The defaults
+ * (max_dist = voxel size, one threshold = max_dist) are a caller's choice echoed back, not tuned values. */
+#define PTL_POSE_SEARCH_MAX_THRESHOLDS 4
+#define PTL_POSE_SEARCH_MAX_POINTS (1 << 20)
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_pose_search_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double max_dist;
+    int32_t n_thresholds;
+    double thresholds[PTL_POSE_SEARCH_MAX_THRESHOLDS];
+} ptl_pose_search_cfg;
+typedef struct {
+    int64_t n_points, n_invalid_points;                   /* query points, and those with a non-finite coordinate */
+    int64_t n_poses, n_invalid_poses;                     /* candidates, and those with a non-finite entry in the top three rows */
+    int64_t best_pose[PTL_POSE_SEARCH_MAX_THRESHOLDS];    /* per threshold: the smallest index with the most hits, -1 = no valid candidate */
+    int64_t best_hits[PTL_POSE_SEARCH_MAX_THRESHOLDS];
+    double max_dist;                                      /* the parameters as used */
+    int32_t n_thresholds;
+    double thresholds[PTL_POSE_SEARCH_MAX_THRESHOLDS];
+    double device_ms;                                     /* HIP-event time of the call's device work on the map's stream, staging copies included */
+} ptl_pose_search_result;
+/* the library's sizeof(ptl_pose_search_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_pose_search_sizeof_cfg(void);
+/* the defaults for a map of that voxel size; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is
+ * refused with PTL_ERR_ARG and nothing is written */
+int ptl_pose_search_default_cfg(ptl_pose_search_cfg *cfg, double voxel_size);
+/* n query points xyz (n x 3 f64, host, sensor frame) at n_poses candidates poses16 (n_poses x 16 f64, host) against the map of `map` (cfg
+ * nullable: the defaults).  hits_out (nullable): n_poses x n_thresholds counts, candidate-major.  The query points are resident for the call;
+ * the candidates are staged and processed in chunks of a fixed size (ptl_build_info [15]): no device buffer grows with n_poses.  Waits for the
+ * handle's map update first, only reads the map and keeps nothing in the handle.  Checked before any HIP call, refused with the numbers
+ * (PTL_ERR_ARG): null map / result, xyz null with n > 0, n < 0, poses16 null with n_poses > 0, n_poses < 0, max_dist <= 0, not finite or above the
+ * map's voxel size, n_thresholds outside 1 .. 4, a threshold <= 0, above max_dist or below its predecessor; n > 2^20: PTL_ERR_CAPACITY.
+ * PTL_ERR_STATE when the table leads to a block that does not hold the probed voxel.  An empty map gives zeros for every valid candidate;
+ * n = 0 as well. */
+int ptl_icp_pose_hits(ptl_icp *map, const ptl_pose_search_cfg *cfg, const double *xyz, int64_t n, const double *poses16, int64_t n_poses,
+                      ptl_pose_search_result *result, int32_t *hits_out);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,18 @@ class CarveResult(C.Structure):
                 ("margin", C.c_double), ("step", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("device_ms", C.c_double)]
 
 
+class PoseSearchCfg(_Cfg):
+    """ptl_pose_search_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
+                ("thresholds", C.c_double * 4)]
+
+
+class PoseSearchResult(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_invalid_points", C.c_int64), ("n_poses", C.c_int64), ("n_invalid_poses", C.c_int64),
+                ("best_pose", C.c_int64 * 4), ("best_hits", C.c_int64 * 4), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
+                ("thresholds", C.c_double * 4), ("device_ms", C.c_double)]
+
+
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 # every exported symbol of include/ptudes_mi.h with its prototype
@@ -283,6 +295,11 @@ PROTOTYPES = {
     "ptl_carve_add_seq": (C.c_int, [_vp, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
     "ptl_carve_add_batch": (C.c_int, [_vp, _vp, C.c_int32, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
     "ptl_carve_read": (C.c_int, [_vp, C.POINTER(CarveResult), c_d_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64, c_i64_p]),
+    # a sweep's fit to a map at K candidate poses (include/ptudes_mi.h)
+    "ptl_pose_search_sizeof_cfg": (C.c_int64, []),
+    "ptl_pose_search_default_cfg": (C.c_int, [C.POINTER(PoseSearchCfg), C.c_double]),
+    "ptl_icp_pose_hits": (C.c_int, [_vp, C.POINTER(PoseSearchCfg), c_d_p, C.c_int64, c_d_p, C.c_int64, C.POINTER(PoseSearchResult),
+                                    C.POINTER(C.c_int32)]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -191,12 +191,23 @@ def ptudes_ekf_nc(file: str, meta: Optional[str] = None, gt_file: Optional[str] 
         print(f"WARNING: plot param '{plot}' doesn't supported")
 
 
-def _synthetic_source(seed: int, n_scans: int):
+def parse_synthetic_size(text):
+    """(H, W) of --synthetic-size HxW, checked before any device is touched; None gives the 128x1024 default"""
+    import re
+    if text is None:
+        return 128, 1024
+    m = re.fullmatch(r"(\d+)x(\d+)", text)
+    if not m or not (1 <= int(m.group(1)) <= 1024 and 16 <= int(m.group(2)) <= 8192):
+        raise click.ClickException(f"--synthetic-size {text}: expected HxW with H in 1 .. 1024 and W in 16 .. 8192, like 128x1024")
+    return int(m.group(1)), int(m.group(2))
+
+
+def _synthetic_source(seed: int, n_scans: int, H: int = 128, W: int = 1024):
     from .. import synth
     from ..sequence import synthetic_events
-    seq = synth.make_sequence(seed=seed, n_scans=n_scans)
+    seq = synth.make_sequence(seed=seed, n_scans=n_scans, H=H, W=W)
     meta = SimpleNamespace(format=SimpleNamespace(columns_per_frame=seq.W, pixels_per_column=seq.H),
-                           prod_line="SYNTH-OS-0-128", mode=f"{seq.W}x10")
+                           prod_line=f"SYNTH-OS-0-{seq.H}", mode=f"{seq.W}x10")
     return seq, meta, synthetic_events(seq)
 
 
@@ -499,6 +510,7 @@ def score_options(map_score, score_radius, voxel_size):
               help="write the resulting poses to this file, Newer College ground-truth format")
 @click.option("--synthetic", type=int, default=None,
               help="Run on the synthetic 128x1024 sequence with this seed instead of FILE (no ouster-sdk needed)")
+@click.option("--synthetic-size", type=str, default=None, help="beams x columns HxW of the --synthetic sweeps (default 128x1024)")
 @click.option("--native-packets", is_flag=True,
               help="read FILE (.bag, or a directory of bags) with the package's own packet decoder also when ouster-sdk is installed "
                    "(without ouster-sdk this is what happens anyway)")
@@ -533,8 +545,11 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                       compare_pose: Optional[str] = None, save_map_error: Optional[str] = None, carve: bool = False,
                       save_carved: Optional[str] = None, carve_radius: Optional[float] = None, carve_margin: Optional[float] = None,
                       carve_max_range: Optional[float] = None, carve_min_through: Optional[int] = None,
-                      carve_min_fraction: Optional[float] = None) -> None:
+                      carve_min_fraction: Optional[float] = None, synthetic_size: Optional[str] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
+    if synthetic_size is not None and synthetic is None:
+        raise click.ClickException("--synthetic-size belongs to --synthetic")
+    synth_hw = parse_synthetic_size(synthetic_size)
     from ..ins.data import StreamStatsTracker
     from ..sequence import run_events
     from ..utils import TrajectoryEvaluator, active_beam_rows
@@ -601,7 +616,7 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
         start_scan_feed = 0  # withScanIdx already applied the range
     else:
         n_scans = (end_scan + 1) if end_scan is not None else 100
-        seq, info, events = _synthetic_source(synthetic, n_scans)
+        seq, info, events = _synthetic_source(synthetic, n_scans, *synth_hw)
         start_scan_feed = start_scan
     if synthetic is not None:
         file = f"synthetic:{synthetic}"

@@ -1,0 +1,158 @@
+"""`localize`: the poses of a recording's sweeps in the frame of a map saved earlier (no reference counterpart).
+
+`--map MAP.ply` and `--keyframes POSES.csv` come from one mapping run (`ekf-bench ouster --save-map MAP.ply --save-nc-gt-poses POSES.csv`):
+the map's points and poses the run went through.  Every keyframe, turned through `--yaws` headings, is a candidate start pose; the first sweep
+is searched for among all of them on the GPU (`Icp.pose_hits`), the best `--top` are refined by the registration's own Gauss-Newton loop
+(`Icp.align`) and scored again.  The following sweeps are tracked from the previous fixes and searched for again when fewer than
+`--min-fraction` of their points lie within a voxel size of the map.  The map is never added to.
+SOURCE is a raw packet .bag (or a directory of bags) read by the package's own packet decoder, with `-m META`; `--synthetic SEED` runs on the
+synthetic sequence instead.  The sweeps' poses are written with `--save-nc-gt-poses` / `--save-kitti-poses`."""
+from typing import Optional
+
+import click
+import numpy as np
+
+from .ekf_bench import MAP_VOXEL_SIZE, parse_synthetic_size
+
+DEFAULTS = dict(yaws=16, top=4, min_fraction=0.5, query_voxel=1.0)  # a caller's policy, untuned (fly.MapLocalizer)
+
+
+def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan):
+    """the options checked before any device is touched: a dict with the defaults filled in"""
+    import os
+    if not map_path:
+        raise click.ClickException("--map MAP.ply is needed: the map to localise in")
+    if not os.path.isfile(map_path):
+        raise click.ClickException(f"--map {map_path}: no such file")
+    if not str(map_path).endswith((".ply", ".npy")):
+        raise click.ClickException(f"--map {map_path}: expected a .ply or .npy cloud")
+    if not keyframes:
+        raise click.ClickException("--keyframes POSES.csv is needed: the poses of the mapping run (its --save-nc-gt-poses)")
+    if not os.path.isfile(keyframes):
+        raise click.ClickException(f"--keyframes {keyframes}: no such file")
+    out = dict(DEFAULTS, map=map_path, keyframes=keyframes, spacing=keyframe_spacing, start_scan=start_scan, end_scan=end_scan)
+    for name, opt, v in (("yaws", "--yaws", yaws), ("top", "--top", top), ("min_fraction", "--min-fraction", min_fraction),
+                         ("query_voxel", "--query-voxel", query_voxel)):
+        if v is not None:
+            out[name] = v
+    if out["yaws"] < 1:
+        raise click.ClickException(f"--yaws {out['yaws']}: at least one heading per keyframe")
+    if keyframe_spacing is not None and not keyframe_spacing >= 0.0:
+        raise click.ClickException(f"--keyframe-spacing {keyframe_spacing:g}: must not be negative")
+    if out["top"] < 1:
+        raise click.ClickException(f"--top {out['top']}: at least one candidate is refined")
+    if not 0.0 <= out["min_fraction"] <= 1.0:
+        raise click.ClickException(f"--min-fraction {out['min_fraction']:g}: a fraction in [0, 1]")
+    if not out["query_voxel"] > 0.0:
+        raise click.ClickException(f"--query-voxel {out['query_voxel']:g}: must be positive")
+    if start_scan < 0:
+        raise click.ClickException(f"--start-scan {start_scan}: must not be negative")
+    if end_scan is not None and end_scan < start_scan:
+        raise click.ClickException(f"--end-scan {end_scan} lies before --start-scan {start_scan}")
+    return out
+
+
+@click.command(name="localize")
+@click.argument("source", required=False, type=click.Path())
+@click.option("-m", "--meta", required=False, type=click.Path(exists=True, dir_okay=False, readable=True),
+              help="sensor metadata .json of SOURCE (needed when it is not found next to it)")
+@click.option("--synthetic", type=int, default=None, help="localise the sweeps of the synthetic sequence with this seed instead of SOURCE")
+@click.option("--synthetic-size", type=str, default=None, help="beams x columns HxW of the --synthetic sweeps (default 128x1024)")
+@click.option("--map", "map_path", required=False, type=click.Path(dir_okay=False),
+              help="the map to localise in: the points a mapping run wrote with --save-map (.ply, or .npy)")
+@click.option("--keyframes", required=False, type=click.Path(dir_okay=False),
+              help="poses of the mapping run in the map's frame, Newer College format (its --save-nc-gt-poses)")
+@click.option("--yaws", type=int, default=None, help=f"headings tried per keyframe (default {DEFAULTS['yaws']}, untuned)")
+@click.option("--keyframe-spacing", type=float, default=None, help="keep a keyframe every this many metres of travel (default: every keyframe)")
+@click.option("--top", type=int, default=None, help=f"candidates refined by the registration (default {DEFAULTS['top']}, untuned)")
+@click.option("--min-fraction", type=float, default=None,
+              help=f"hit fraction below which a tracked sweep is searched for again (default {DEFAULTS['min_fraction']}, untuned)")
+@click.option("--query-voxel", type=float, default=None,
+              help=f"side of the voxels that thin a sweep to one point each, metres (default {DEFAULTS['query_voxel']}, untuned)")
+@click.option("--start-scan", type=int, default=0, help="first sweep to localise (0-based)")
+@click.option("--end-scan", type=int, help="last sweep to localise (inclusive)")
+@click.option("--save-nc-gt-poses", required=False, type=click.Path(exists=False, dir_okay=False),
+              help="write the sweeps' poses in the map's frame, Newer College format")
+@click.option("--save-kitti-poses", required=False, type=click.Path(exists=False, dir_okay=False),
+              help="write the sweeps' poses in the map's frame, KITTI format")
+def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optional[int], synthetic_size: Optional[str],
+                    map_path: Optional[str], keyframes: Optional[str], yaws: Optional[int], keyframe_spacing: Optional[float],
+                    top: Optional[int], min_fraction: Optional[float], query_voxel: Optional[float], start_scan: int,
+                    end_scan: Optional[int], save_nc_gt_poses: Optional[str], save_kitti_poses: Optional[str]) -> None:
+    """Poses of the sweeps of SOURCE in the frame of a saved map."""
+    opts = localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan)
+    if synthetic_size is not None and synthetic is None:
+        raise click.ClickException("--synthetic-size belongs to --synthetic")
+    H, W = parse_synthetic_size(synthetic_size)
+    if synthetic is None:
+        from pathlib import Path
+        if not source:
+            raise click.ClickException("give SOURCE or --synthetic SEED")
+        path = Path(source)
+        if not ((path.is_file() and path.suffix == ".bag") or path.is_dir()):
+            raise click.ClickException(f"'{source}': SOURCE is a raw packet .bag or a directory of .bag files, read by the package's own decoder; "
+                                       "--synthetic SEED runs the same path on a synthetic sequence")
+        if not meta and path.is_file() and path.with_suffix(".json").is_file():
+            meta = str(path.with_suffix(".json"))
+        if not meta:
+            raise click.ClickException("File not found, please specify a metadata file with `-m`")
+    from ..utils import load_map_ply, read_newer_college_gt, save_poses_kitti_format, save_poses_nc_gt_format
+    kf = read_newer_college_gt(opts["keyframes"])
+    if not kf:
+        raise click.ClickException(f"--keyframes {opts['keyframes']}: no pose in the file")
+    map_pts = np.ascontiguousarray(load_map_ply(opts["map"]), dtype=np.float64).reshape(-1, 3)
+    from .. import fly
+
+    if synthetic is not None:
+        from .. import synth
+        n_scans = (end_scan + 1) if end_scan is not None else 100
+        seq = synth.make_sequence(seed=synthetic, n_scans=n_scans, H=H, W=W)
+        points_per_sweep = H * W
+
+        def sweeps():
+            for k in range(start_scan, n_scans):
+                yield float(seq.t_base + (k + 1) * seq.scan_dt), seq.scan(k)
+    else:
+        from .. import packets as pk
+        from ..bag import OusterPacketBagSource
+        info = pk.read_metadata_json(meta)
+        lut = fly.sensor_lut(info, use_extrinsics=True)  # (the registration's: lidar_to_sensor and the extrinsic)
+        bags = sorted(path.glob("*.bag")) if path.is_dir() else path
+        points_per_sweep = lut.H * lut.W
+
+        def sweeps():
+            feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info)
+            try:
+                for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+                    if not hasattr(d, "lacc"):
+                        yield d.ts, lut(d.range)  # (a pixel without a return is (0, 0, 0): MapLocalizer.query drops it)
+            finally:
+                feed.close()
+
+    loc = fly.MapLocalizer(map_pts, [p for _, p in kf], n_yaw=opts["yaws"], spacing=opts["spacing"], top=opts["top"],
+                           min_fraction=opts["min_fraction"], query_voxel=opts["query_voxel"], voxel_size=MAP_VOXEL_SIZE,
+                           max_points_per_scan=max(points_per_sweep, 1 << 16))
+    print(f"map: {opts['map']} ({len(map_pts)} points, voxel size {MAP_VOXEL_SIZE})")
+    print(f"keyframes: {opts['keyframes']} ({len(kf)} poses, {len(loc.kept)} kept) x {opts['yaws']} yaws = {len(loc.candidates)} candidates")
+    res_t, res_poses, fractions = [], [], []
+    try:
+        for ts, xyz in sweeps():
+            fix = loc.track(xyz)
+            res_t.append(ts)
+            res_poses.append(fix.pose)
+            fractions.append(fix.fraction)
+        relocalizations, search_ms, rescore_ms, query_ms = loc.relocalizations, loc.search_ms, loc.rescore_ms, loc.query_ms
+    finally:
+        loc.close()
+    header = f"localize: map {opts['map']}, keyframes {opts['keyframes']}\n(sweeps num: {len(res_poses)})"
+    if save_kitti_poses:
+        save_poses_kitti_format(save_kitti_poses, res_poses, header=header)
+        print(f"Kitti poses saved to: {save_kitti_poses}")
+    if save_nc_gt_poses:
+        save_poses_nc_gt_format(save_nc_gt_poses, t=res_t, poses=res_poses, header=header)
+        print(f"NC GT poses saved to: {save_nc_gt_poses}")
+    print(f"sweeps localised: {len(res_poses)}")
+    print(f"re-localisations: {relocalizations}")
+    print(f"mean hit fraction: {float(np.mean(fractions)) if fractions else 0.0:.6f}")
+    print(f"search device time: {search_ms + rescore_ms:.3f} ms (candidate searches {search_ms:.3f} ms, rescoring {rescore_ms:.3f} ms)")
+    print(f"sweep thinning: {query_ms:.3f} ms of wall time (a scratch one-point-per-voxel map per sweep)")

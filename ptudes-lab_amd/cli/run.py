@@ -3,6 +3,7 @@ import click
 
 from .ekf_bench import ptudes_ekf_bench
 from .flyby import ptudes_flyby
+from .localize import ptudes_localize
 from .stat import ptudes_stat
 
 
@@ -14,6 +15,7 @@ def ptudes_cli() -> None:
 ptudes_cli.add_command(ptudes_ekf_bench)
 ptudes_cli.add_command(ptudes_stat)
 ptudes_cli.add_command(ptudes_flyby)
+ptudes_cli.add_command(ptudes_localize)
 
 
 def main():

@@ -108,6 +108,47 @@ def map_cmp_cfg(voxel_size, max_dist=None, thresholds=None):
     return cfg
 
 
+@dataclass
+class PoseHits:
+    """Summary of `Icp.pose_hits` (include/ptudes_mi.h ptl_pose_search_result): per threshold the largest hit count over the valid candidates
+    and the smallest candidate index that attains it (-1 without a valid candidate), the counts of non-finite inputs, the parameters as used
+    and the HIP-event time"""
+    n_points: int
+    n_invalid_points: int
+    n_poses: int
+    n_invalid_poses: int
+    best_pose: tuple       # one index per threshold
+    best_hits: tuple
+    max_dist: float
+    thresholds: tuple
+    device_ms: float
+
+    @property
+    def fractions(self):
+        """best_hits / n_points per threshold (0 without points)"""
+        return tuple(h / self.n_points if self.n_points else 0.0 for h in self.best_hits)
+
+    @classmethod
+    def _from(cls, res):
+        k = int(res.n_thresholds)
+        return cls(int(res.n_points), int(res.n_invalid_points), int(res.n_poses), int(res.n_invalid_poses),
+                   tuple(int(x) for x in res.best_pose[:k]), tuple(int(x) for x in res.best_hits[:k]), float(res.max_dist),
+                   tuple(float(x) for x in res.thresholds[:k]), float(res.device_ms))
+
+
+def pose_search_cfg(voxel_size, max_dist=None, thresholds=None):
+    """the _lib.PoseSearchCfg of a map of that voxel size: max_dist defaults to the voxel size, thresholds to (max_dist,)"""
+    cfg = L.PoseSearchCfg()
+    L.check(L.lib().ptl_pose_search_default_cfg(C.byref(cfg), float(voxel_size)))
+    if max_dist is not None:
+        cfg.max_dist = float(max_dist)
+    thr = [cfg.max_dist] if thresholds is None else [float(t) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1)]
+    cfg.n_thresholds = len(thr)  # (a count outside 1 .. 4 is the library's to refuse, with the number)
+    for k, t in enumerate(thr[:4]):
+        cfg.thresholds[k] = t
+    return cfg
+
+
 def map_from_points(points, voxel_size=0.5, max_points_per_voxel=20, device_id=0, max_points_per_scan=1 << 20, **over):
     """an `Icp` whose voxel map holds `points` (N, 3), added in chunks of at most its max_points_per_scan in array order (a voxel keeps its
     first max_points_per_voxel points): a reference map for `Icp.map_distance` / `Icp.map_compare` out of a bare cloud"""
@@ -270,6 +311,19 @@ class Icp:
         w = C.c_int64()
         L.check(L.lib().ptl_icp_map_compare(self._h, src_icp._h, C.byref(cfg), C.byref(res), L.dptr(xyz), L.dptr(d2), p, C.byref(w)))
         return MapDistance._from(res), (xyz[:w.value], d2[:w.value])
+
+    def pose_hits(self, points, poses, max_dist=None, thresholds=None, per_pose=True):
+        """how many of `points` (N, 3), sensor frame, lie within each threshold of this map's stored points when posed by each of `poses`
+        (K, 4, 4) (include/ptudes_mi.h ptl_icp_pose_hits): a `PoseHits`; with per_pose also the (K, T) int32 counts, -1 in the
+        row of a candidate with a non-finite entry.  max_dist defaults to the voxel size (its upper bound), thresholds to (max_dist,)"""
+        cfg = pose_search_cfg(self.cfg.voxel_size, max_dist, thresholds)
+        q = L.as_f64(points).reshape(-1, 3)
+        p = L.as_f64(poses).reshape(-1, 16)
+        res = L.PoseSearchResult()
+        hits = np.empty((len(p), max(0, min(int(cfg.n_thresholds), 4))), dtype=np.int32) if per_pose else None
+        L.check(L.lib().ptl_icp_pose_hits(self._h, C.byref(cfg), L.dptr(q) if len(q) else None, len(q), L.dptr(p) if len(p) else None, len(p),
+                                          C.byref(res), None if hits is None else hits.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (PoseHits._from(res), hits) if per_pose else PoseHits._from(res)
 
     def _cloud(self, fn):
         cap = int(self.cfg.max_points_per_scan)
@@ -1262,7 +1316,7 @@ class BatchRunner(_Runner):
 
 
 BUILD_INFO = ("kcand", "ans_row_doubles", "lds_points", "seq_u", "seq_u2", "gn8_threads", "lanes_per_point", "spec", "surv",
-              "prefetch", "keep_x1000", "tab_entry_bytes", "vds_entry_bytes", "diagnostics", "fast")
+              "prefetch", "keep_x1000", "tab_entry_bytes", "vds_entry_bytes", "diagnostics", "fast", "pose_chunk")
 
 
 def build_info():

@@ -12,6 +12,7 @@
 #include "render_kernels.h"
 #include "compare_kernels.h"
 #include "carve_kernels.h"
+#include "pose_kernels.h"
 #include "hip_own.h"
 
 #include <hip/hip_runtime.h>
@@ -2439,6 +2440,7 @@ extern "C" int ptl_batch_sched_counters(ptl_batch* b, int32_t s, uint64_t out[4]
 //   [0] GN8_KCAND  [1] doubles per answer row  [2] GN8_LDS_PTS  [3] SEQ_U  [4] SEQ_U2  [5] GN8_MAX_THREADS  [6] GN8_LPB  [7] GN8_SPEC
 //   [8] GN8_SURV  [9] GN8_PREFETCH  [10] 1000 x GN8_KEEP  [11] bytes per map table entry  [12] bytes per VDS entry
 //   [13] diagnostic flavours compiled in (diag.h): 1 PHASES | 2 IT0 | 4 STAGES | 8 MAP_DIAG, 0 = the product build
+//   [15] POSE_CHUNK (pose_kernels.h)
 #ifndef PTL_CODE_ID
 #define PTL_CODE_ID "unknown"
 #endif
@@ -2448,7 +2450,7 @@ extern "C" int ptl_build_info(int32_t out[16]) {
     for (int i = 0; i < 16; ++i) out[i] = 0;
     out[0] = GN8_KCAND; out[1] = GN8_ANS_ROW; out[2] = GN8_LDS_PTS; out[3] = SEQ_U; out[4] = SEQ_U2; out[5] = GN8_MAX_THREADS;
     out[6] = GN8_LPB; out[7] = GN8_SPEC; out[8] = GN8_SURV; out[9] = GN8_PREFETCH; out[10] = (int32_t)(1000.0 * GN8_KEEP + 0.5);
-    out[11] = (int32_t)sizeof(TabEnt); out[12] = (int32_t)sizeof(VdsEnt); out[13] = diag::flavours; out[14] = 0;
+    out[11] = (int32_t)sizeof(TabEnt); out[12] = (int32_t)sizeof(VdsEnt); out[13] = diag::flavours; out[14] = 0; out[15] = POSE_CHUNK;
     return PTL_OK;
 }
 extern "C" int ptl_batch_run(ptl_batch* b, int64_t n) {
@@ -3243,6 +3245,109 @@ extern "C" int ptl_icp_map_compare(ptl_icp* ref, ptl_icp* src, const ptl_map_cmp
         HIPCHK(hipMemcpy(dist2_out, d_d2, (size_t)n * 8, hipMemcpyDeviceToHost));
         if (n_written) *n_written = n;
     }
+    return PTL_OK;
+}
+
+// ================================================================================================ pose search
+// The definition is in include/ptudes_mi.h, the kernels in pose_kernels.h.  Everything is checked on the host before the first HIP call; the
+// work buffers (the query points, one staged chunk of candidates and its counts, the running best) live for the call.
+static void pose_search_defaults(ptl_pose_search_cfg* cfg, double voxel_size) {
+    PTL_CFG_INIT(cfg);
+    cfg->max_dist = voxel_size;
+    cfg->n_thresholds = 1;
+    cfg->thresholds[0] = voxel_size;
+}
+extern "C" int64_t ptl_pose_search_sizeof_cfg(void) { return (int64_t)sizeof(ptl_pose_search_cfg); }
+extern "C" int ptl_pose_search_default_cfg(ptl_pose_search_cfg* cfg, double voxel_size) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_pose_search_cfg, cfg);
+    if (!(voxel_size > 0.0) || !(voxel_size < 1.0e150)) return set_err(PTL_ERR_ARG, "voxel_size must be positive and finite (got %g)", voxel_size);
+    pose_search_defaults(cfg, voxel_size);
+    return PTL_OK;
+}
+static_assert(PTL_POSE_SEARCH_MAX_THRESHOLDS == POSE_MAX_THR && POSE_MAX_THR <= CMP_MAX_THR, "the header's threshold count is the kernels'");
+static_assert(PTL_POSE_SEARCH_MAX_POINTS == POSE_MAX_POINTS, "the header's point limit is the kernels'");
+extern "C" int ptl_icp_pose_hits(ptl_icp* map, const ptl_pose_search_cfg* cfg, const double* xyz, int64_t n, const double* poses16, int64_t n_poses,
+                                 ptl_pose_search_result* result, int32_t* hits_out) {
+    const char* who = "ptl_icp_pose_hits";
+    if (!map || !result) return set_err(PTL_ERR_ARG, "%s: null argument", who);
+    if (n < 0) return set_err(PTL_ERR_ARG, "%s: n = %lld: must not be negative", who, (long long)n);
+    if (n > 0 && !xyz) return set_err(PTL_ERR_ARG, "%s: %lld query points without xyz", who, (long long)n);
+    if (n_poses < 0) return set_err(PTL_ERR_ARG, "%s: n_poses = %lld: must not be negative", who, (long long)n_poses);
+    if (n_poses > 0 && !poses16) return set_err(PTL_ERR_ARG, "%s: %lld candidates without poses16", who, (long long)n_poses);
+    ptl_pose_search_cfg use;
+    if (cfg) { ABI_CHECK(ptl_pose_search_cfg, cfg); use = *cfg; } else pose_search_defaults(&use, map->cfg.voxel_size);
+    const double vs = map->cfg.voxel_size;
+    if (!(use.max_dist > 0.0) || !(use.max_dist <= vs))
+        return set_err(PTL_ERR_ARG, "%s: max_dist = %g: the 27-voxel search needs 0 < max_dist <= the map's voxel size = %g", who, use.max_dist, vs);
+    if (use.n_thresholds < 1 || use.n_thresholds > POSE_MAX_THR)
+        return set_err(PTL_ERR_ARG, "%s: n_thresholds = %d: must be in [1, %d]", who, use.n_thresholds, POSE_MAX_THR);
+    for (int k = 0; k < use.n_thresholds; ++k) {
+        const double t = use.thresholds[k];
+        if (!(t > 0.0) || !(t <= use.max_dist))
+            return set_err(PTL_ERR_ARG, "%s: threshold %d = %g: must be in (0, max_dist = %g]", who, k, t, use.max_dist);
+        if (k > 0 && t < use.thresholds[k - 1])
+            return set_err(PTL_ERR_ARG, "%s: threshold %d = %g is below threshold %d = %g: ascending order", who, k, t, k - 1, use.thresholds[k - 1]);
+    }
+    if (n > (int64_t)POSE_MAX_POINTS)
+        return set_err(PTL_ERR_CAPACITY, "%s: n = %lld query points, at most %d are held resident for a call", who, (long long)n, POSE_MAX_POINTS);
+    if (n_poses > (int64_t)0x7fffffff - POSE_CHUNK)  // (k_pose_best ranks a candidate by a 31-bit index)
+        return set_err(PTL_ERR_CAPACITY, "%s: n_poses = %lld, at most %lld candidates a call", who, (long long)n_poses, (long long)0x7fffffff - POSE_CHUNK);
+    const int T = use.n_thresholds;
+    PoseArgs a;
+    memset(&a, 0, sizeof a);
+    memset(result, 0, sizeof *result);
+    result->max_dist = a.cmp.max_dist = use.max_dist;
+    a.cmp.max2 = use.max_dist * use.max_dist;
+    result->n_thresholds = a.cmp.n_thr = T;
+    for (int k = 0; k < T; ++k) { result->thresholds[k] = use.thresholds[k]; a.cmp.thr2[k] = use.thresholds[k] * use.thresholds[k]; }
+    for (int k = 0; k < POSE_MAX_THR; ++k) result->best_pose[k] = -1;
+    result->n_points = n;
+    result->n_poses = n_poses;
+    if (n == 0 && n_poses == 0) return PTL_OK;
+    HIPCHK(hipSetDevice(map->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    const int cap = (int)(n_poses < POSE_CHUNK ? n_poses : POSE_CHUNK);
+    DevOwner tmp;
+    double *d_xyz = nullptr, *d_poses = nullptr;
+    int *d_hits = nullptr, *d_cnt = nullptr;
+    long long* d_best = nullptr;
+    tmp.add(&d_xyz, (size_t)(n > 0 ? n : 1) * 3); tmp.add(&d_poses, (size_t)(cap > 0 ? cap : 1) * 16);
+    tmp.add(&d_hits, (size_t)(cap > 0 ? cap : 1) * POSE_MAX_THR); tmp.add(&d_best, POSE_MAX_THR);
+    tmp.add(&d_cnt, 3);  // [0] inconsistent probes (cmp_query's `bad`), [1] invalid query points, [2] invalid candidates
+    HIPCHK(tmp.err);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventDefault)); HIPCHK(e1.create(hipEventDefault));
+    hipStream_t s = map->stream;
+    a.cmp.bad = d_cnt; a.xyz = d_xyz; a.n = (int)n; a.poses = d_poses; a.hits = d_hits;
+    HIPCHK(hipEventRecord(e0, s));
+    HIPCHK(hipMemsetAsync(d_cnt, 0, 3 * sizeof(int), s));
+    if (n > 0) HIPCHK(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 24, hipMemcpyHostToDevice, s));
+    k_pose_invalid<<<1, 1024, 0, s>>>(d_xyz, (int)n, d_cnt + 1);
+    // (one staging buffer: the stream's order keeps a chunk's kernels and its copy back ahead of the next chunk's copy in)
+    for (int64_t off = 0; off < n_poses; off += POSE_CHUNK) {
+        const int m = (int)(n_poses - off < POSE_CHUNK ? n_poses - off : POSE_CHUNK);
+        HIPCHK(hipMemcpyAsync(d_poses, poses16 + 16 * off, (size_t)m * 128, hipMemcpyHostToDevice, s));
+        a.n_poses = m;
+        k_pose_hits<<<m < POSE_MAX_BLOCKS ? m : POSE_MAX_BLOCKS, POSE_THREADS, 0, s>>>(map->c, a);
+        k_pose_best<<<1, 1024, 0, s>>>(d_hits, m, T, (int)off, off == 0 ? 1 : 0, d_best, d_cnt + 2);
+        if (hits_out) HIPCHK(hipMemcpyAsync(hits_out + off * T, d_hits, (size_t)m * T * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipGetLastError());
+    int cnt[3] = {0, 0, 0};
+    long long best[POSE_MAX_THR] = {-1, -1, -1, -1};
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+    if (n_poses > 0) HIPCHK(hipMemcpyAsync(best, d_best, (size_t)T * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (cnt[0]) return set_err(PTL_ERR_STATE, "%s: the map's table led %d probes to a block that does not hold the probed voxel", who, cnt[0]);
+    result->n_invalid_points = cnt[1];
+    result->n_invalid_poses = cnt[2];
+    for (int k = 0; k < T; ++k)
+        if (best[k] >= 0) { result->best_hits[k] = best[k] >> 32; result->best_pose[k] = 0x7fffffffll - (best[k] & 0xffffffffll); }
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    result->device_ms = ms;
     return PTL_OK;
 }
 

@@ -223,6 +223,177 @@ class MapCarver:
         self.carver.close()
 
 
+# ------------------------------------------------------------------------------------------------ a sweep's pose in a saved map
+def candidate_poses(keyframes, n_yaw, spacing=None):
+    """Start poses for a search in a map: the keyframes (M, 4, 4) - poses the mapping run went through - thinned by travelled distance, each
+    composed on the right with Rz(2 pi j / n_yaw), j = 0 .. n_yaw - 1.  Thinning: the first keyframe is kept; the path length
+    sum |t_i - t_(i-1)| runs along ALL keyframes, and a keyframe is kept when that length since the last kept one has reached `spacing`
+    (None or 0: every keyframe is kept).  Order: keyframe-major; j = 0 is the keyframe itself, bit for bit.
+    Returns (poses (K, 4, 4), kept (K / n_yaw,) the indices of the kept keyframes)"""
+    kf = np.asarray(keyframes, dtype=np.float64).reshape(-1, 4, 4)
+    n_yaw = int(n_yaw)
+    if n_yaw < 1:
+        raise ValueError(f"n_yaw = {n_yaw}: at least one heading per keyframe")
+    if spacing is not None and not spacing >= 0.0:
+        raise ValueError(f"spacing = {spacing}: must not be negative")
+    kept, since = [], 0.0
+    for i in range(len(kf)):
+        if i > 0:
+            since += float(np.linalg.norm(kf[i, :3, 3] - kf[i - 1, :3, 3]))
+        if i == 0 or not spacing or since >= spacing:
+            kept.append(i)
+            since = 0.0
+    out = np.empty((len(kept) * n_yaw, 4, 4))
+    for a, i in enumerate(kept):
+        out[a * n_yaw] = kf[i]
+        for j in range(1, n_yaw):
+            out[a * n_yaw + j] = kf[i] @ _rot_z(360.0 * j / n_yaw)
+    return out, np.asarray(kept, dtype=np.int64)
+
+
+def top_candidates(hits, top):
+    """indices of the `top` largest entries of `hits` (K,), largest first, ties broken by the smaller index; negative entries (invalid
+    candidates) never qualify"""
+    h = np.asarray(hits).reshape(-1).astype(np.int64)
+    order = np.lexsort((np.arange(len(h)), -h))  # (primary key: hits descending; secondary: index ascending)
+    order = order[h[order] >= 0]
+    return order[:max(int(top), 0)]
+
+
+@dataclass
+class Localization:
+    """One fix of `MapLocalizer`: the sweep's pose in the map's frame, the query points within the last threshold of the map at that pose
+    (`hits` of `n_query`, `fraction` = hits / n_query), the candidate the pose was refined from (-1: tracked from the previous fixes), the
+    hits of the best OTHER refined candidate (-1: there was none) and the Gauss-Newton iterations of the winning refinement"""
+    pose: np.ndarray
+    hits: int
+    n_query: int
+    fraction: float
+    candidate: int
+    runner_up_hits: int
+    iterations: int
+
+
+class MapLocalizer:
+    """Finds and follows a sensor in a FROZEN map: `Icp.pose_hits` scores every candidate start pose on the device,
+    `Icp.align` - the registration's own Gauss-Newton loop, which changes neither map nor trajectory - refines the best ones.  The map is
+    never added to.
+    map: a core.Icp, a MapAccumulator, or an (N, 3) array (a handle is then built by core.map_from_points and closed with this object);
+    keyframes (M, 4, 4): poses the mapping run went through (`candidate_poses`).
+    Policy, the caller's - the defaults are untuned: n_yaw headings per keyframe, keyframe `spacing` (metres), the `top` candidates that are
+    refined, the hit fraction `min_fraction` below which `track` searches again, the side `query_voxel` of the voxels that thin a sweep.
+    sigma: the registration threshold of the refinements - max_dist = 3 sigma, kernel = sigma / 3 as the registration path derives them
+    (reference kiss.py:108-114) - fixed at the map handle's cfg.initial_threshold unless given: a frozen map has no trajectory to adapt it to.
+    max_dist / thresholds: of the hit counts (defaults: the map's voxel size); selection and `fraction` use the LAST threshold."""
+
+    def __init__(self, map, keyframes, n_yaw=16, spacing=None, top=4, min_fraction=0.5, query_voxel=1.0, sigma=None, max_dist=None,
+                 thresholds=None, **map_kw):
+        self._own = False
+        if isinstance(map, MapAccumulator):
+            map = map.icp
+        if not isinstance(map, core.Icp):
+            map = core.map_from_points(map, **map_kw)
+            self._own = True
+        self.icp = map
+        self.candidates, self.kept = candidate_poses(keyframes, n_yaw, spacing)
+        if not len(self.candidates):
+            raise ValueError("no keyframe: nothing to search from")
+        if int(top) < 1:
+            raise ValueError(f"top = {top}: at least one candidate is refined")
+        if not query_voxel > 0.0:
+            raise ValueError(f"query_voxel = {query_voxel}: must be positive")
+        self.n_yaw, self.top, self.min_fraction, self.query_voxel = int(n_yaw), int(top), float(min_fraction), float(query_voxel)
+        self.sigma = float(map.cfg.initial_threshold if sigma is None else sigma)
+        self.max_dist, self.thresholds = max_dist, thresholds
+        self.fixes = []              # the poses of the sweeps so far, oldest first
+        self.relocalizations = 0     # searches `track` ran because a tracked pose fell below min_fraction
+        self.search_ms = self.align_ms = self.rescore_ms = 0.0  # device time of the searches / wall time of the refinements / device time of the rescoring
+        self.query_ms = 0.0          # wall time of `query`: a scratch map handle is made and destroyed per sweep
+
+    def close(self):
+        if self._own and self.icp is not None:
+            self.icp.close()
+        self.icp = None
+
+    def query(self, points):
+        """the first point per voxel of side query_voxel of a sweep's returns (sensor frame; non-finite rows and the (0, 0, 0) of a pixel
+        without a return are dropped): a scratch map of one point per voxel and its `map_points()`, sorted by (x, y, z) - the export's
+        order is not specified, and the refinement's sums follow the order of its points: one sweep, one query, bit for bit"""
+        import time
+        t0 = time.perf_counter()
+        p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        p = p[np.isfinite(p).all(axis=1) & (p != 0.0).any(axis=1)]
+        if not len(p):
+            return p
+        scratch = core.map_from_points(p, voxel_size=self.query_voxel, max_points_per_voxel=1, device_id=self.icp.cfg.device_id,
+                                       max_points_per_scan=max(len(p), 1024), map_block_capacity=max(len(p), 1024),
+                                       map_table_capacity=1 << max(12, int(4 * len(p) - 1).bit_length()))
+        try:
+            out = scratch.map_points()
+            return np.ascontiguousarray(out[np.lexsort(out.T[::-1])])
+        finally:
+            scratch.close()
+            self.query_ms += 1000.0 * (time.perf_counter() - t0)
+
+    def _checked_query(self, points):
+        q = self.query(points)
+        if not len(q):
+            raise ValueError("the sweep has no return (no finite point other than (0, 0, 0)): nothing to localise")
+        return q
+
+    def _hits(self, q, poses):
+        return self.icp.pose_hits(q, poses, max_dist=self.max_dist, thresholds=self.thresholds)
+
+    def _refine(self, q, guess):
+        return self.icp.align(q, guess, 3.0 * self.sigma, self.sigma / 3.0)
+
+    def locate(self, points, query=None):
+        """search: the hit counts of every candidate, the `top` of them (by hits at the last threshold, ties to the smaller index) refined by
+        `Icp.align`, the refined poses scored once more; the best of those (ties to the better-ranked candidate) is the `Localization`.
+        query: the thinned points when the caller has them already"""
+        import time
+        q = self._checked_query(points) if query is None else np.asarray(query, dtype=np.float64).reshape(-1, 3)
+        if not len(q):
+            raise ValueError("an empty query: nothing to localise")
+        s, hits = self._hits(q, self.candidates)
+        self.search_ms += s.device_ms
+        order = top_candidates(hits[:, -1], self.top)
+        if not len(order):
+            raise RuntimeError("no valid candidate pose")
+        t0 = time.perf_counter()
+        refined = [self._refine(q, self.candidates[c]) for c in order]
+        self.align_ms += 1000.0 * (time.perf_counter() - t0)
+        s2, h2 = self._hits(q, np.array([r[0] for r in refined]))
+        self.rescore_ms += s2.device_ms
+        w = int(s2.best_pose[-1])
+        if w < 0:
+            raise RuntimeError("no refined pose is finite")
+        others = np.delete(h2[:, -1], w)
+        fix = Localization(refined[w][0], int(h2[w, -1]), len(q), int(h2[w, -1]) / len(q) if len(q) else 0.0, int(order[w]),
+                           int(others.max()) if len(others) else -1, int(refined[w][1]))
+        self.fixes.append(fix.pose)
+        return fix
+
+    def track(self, points):
+        """the next sweep of a run: `Icp.align` from the constant-velocity guess off the last two fixes (the last fix itself after one; a
+        search without any), one hit count at the result; below min_fraction the sweep is searched for again and counted"""
+        if not self.fixes:
+            return self.locate(points)
+        q = self._checked_query(points)
+        last = self.fixes[-1]
+        guess = last @ (np.linalg.inv(self.fixes[-2]) @ last) if len(self.fixes) > 1 else last
+        pose, it = self._refine(q, guess)
+        s, h = self._hits(q, pose[None])
+        self.rescore_ms += s.device_ms
+        hits = int(h[0, -1])
+        fraction = hits / len(q) if len(q) else 0.0
+        if hits < 0 or fraction < self.min_fraction:
+            self.relocalizations += 1
+            return self.locate(points, query=q)
+        self.fixes.append(pose)
+        return Localization(pose, hits, len(q), fraction, -1, -1, int(it))
+
+
 # ------------------------------------------------------------------------------------------------ the camera path (DESIGN.md 3.21)
 class FlyingState(Enum):
     """Camera movement states (reference fly.py:19-24)"""
