@@ -624,6 +624,48 @@ int ptl_pktdec_destroy(ptl_pktdec *d);
  * n_sweeps.  Arguments are checked before any HIP call. */
 int ptl_pktdec_decode(ptl_pktdec *d, const void *packets, int64_t stride_bytes, int64_t n, const int32_t *sweep_of_packet, int32_t n_sweeps,
                       uint32_t *range_out, uint64_t *col_ts_out, uint16_t *col_status_out, ptl_pkt_summary *summary_out);
+/* The channel fields of a pixel beside its range.  A field is `bytes` (1, 2 or 4) at byte `offset` from the start of the pixel,
+ * offset % bytes == 0 and offset + bytes <= the profile's pixel size (12 / 12 / 4 / 16 bytes); its value is (little-endian word & mask) << shift
+ * for shift >= 0 and >> -shift otherwise (|shift| <= 31), as u32; mask == 0 means all bits.  The descriptor is DATA: ptl_pkt_field_default fills
+ * it from this table (restated from Ouster's published pixel layouts and UNPINNED - no copy of them was at hand; a wrong row is a one-line fix
+ * there, or a descriptor of the caller's own, not a kernel change):
+ *   profile                       RANGE                 REFLECTIVITY  SIGNAL    NEAR_IR        second return
+ *   LEGACY                        u32 @0 & 0x000fffff   u16 @4        u16 @6    u16 @8         none
+ *   RNG19_RFL8_SIG16_NIR16        u32 @0 & 0x0007ffff   u8 @4         u16 @6    u16 @8         none
+ *   RNG15_RFL8_NIR8               u16 @0 & 0x7fff << 3  u8 @2         none      u8 @3 << 4     none
+ *   RNG19_RFL8_SIG16_NIR16_DUAL   u32 @0 & 0x0007ffff   u8 @3         u16 @8    u16 @12        RANGE2 u32 @4 & 0x0007ffff, REFLECTIVITY2 u8 @7, SIGNAL2 u16 @10
+ * A field image is u32[H][W], staggered like the range image: image column `id` is written by the packet column that supplies the range image's
+ * (the last counted one in arrival order) and by nobody else; a column that no counted packet column supplies is 0; a field is written whether
+ * or not the pixel's range is 0.  RANGE through this path equals range_out bit for bit. */
+#define PTL_PKT_FIELD_RANGE 0
+#define PTL_PKT_FIELD_REFLECTIVITY 1
+#define PTL_PKT_FIELD_SIGNAL 2
+#define PTL_PKT_FIELD_NEAR_IR 3
+#define PTL_PKT_FIELD_RANGE2 4
+#define PTL_PKT_FIELD_REFLECTIVITY2 5
+#define PTL_PKT_FIELD_SIGNAL2 6
+#define PTL_PKT_MAX_FIELDS 4 /* fields per ptl_pktdec_decode_fields call */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(ptl_pkt_field) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    int32_t offset;        /* bytes from the start of the pixel */
+    int32_t bytes;         /* 1, 2 or 4 */
+    uint32_t mask;         /* 0: all bits */
+    int32_t shift;         /* > 0 left, < 0 right */
+} ptl_pkt_field;
+/* the library's sizeof(ptl_pkt_field) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_pkt_sizeof_field(void);
+/* the table's descriptor of PTL_PKT_FIELD_* in fmt's profile; out->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a
+ * mismatch is refused with PTL_ERR_ARG and nothing is written.  PTL_ERR_ARG naming profile and field where the profile has no such field. */
+int ptl_pkt_field_default(const ptl_pkt_format *fmt, int32_t field_id, ptl_pkt_field *out);
+/* ptl_pktdec_decode and, from the same staged packets (they cross the bus once; the three passes run as they are, ONE added launch reads the
+ * staged packets again), n_fields (1 .. PTL_PKT_MAX_FIELDS) field images: field_out[f] (host, n_sweeps x H x W u32, none NULL) gets fields[f].
+ * The other outputs as ptl_pktdec_decode's (any may be NULL).  Checked before any HIP call and refused with the numbers (PTL_ERR_ARG): n_fields
+ * outside 1 .. 4, a descriptor of another size or version, bytes not 1, 2 or 4, a negative or misaligned offset, offset + bytes past the
+ * pixel, |shift| > 31 - and everything ptl_pktdec_decode checks.  The field staging is the decoder's, made by the first call that needs it. */
+int ptl_pktdec_decode_fields(ptl_pktdec *d, const void *packets, int64_t stride_bytes, int64_t n, const int32_t *sweep_of_packet, int32_t n_sweeps,
+                             const ptl_pkt_field *fields, int32_t n_fields, uint32_t *const *field_out, uint32_t *range_out,
+                             uint64_t *col_ts_out, uint16_t *col_status_out, ptl_pkt_summary *summary_out);
 /* profiling: HIP-event time of the device work of the decoder's calls (the initialisation and the three passes, not the copies) since the last
  * reset, and the number of calls timed; like ptl_icp_profile */
 int ptl_pktdec_profile(ptl_pktdec *d, int enable, double *ms_total, int64_t *calls, int reset);
@@ -735,6 +777,14 @@ int ptl_render_set_z_range(ptl_render *r, double z_lo, double z_hi);
 /* the overlay cloud (e.g. the trajectory's positions): n points xyz (n x 3 f64, world) with their colours, drawn point_px wide (1 .. 5) into
  * every frame after the map under the same depth test; n = 0 clears it (xyz / rgba may then be NULL) */
 int ptl_render_set_overlay(ptl_render *r, const double *xyz, const uint32_t *rgba, int64_t n, int32_t point_px);
+/* A colour of its own for every stored point of ONE map handle: n little-endian rgba words in pool order (block id, then slot:
+ * the order of ptl_paint_read's, ptl_carve_read's and ptl_icp_map_score's per-point outputs).  n must equal the map's stored point count, else
+ * PTL_ERR_ARG with both numbers; rgba == NULL or n == 0 clears the colours (map may then be NULL).  The renderer keeps the words, its own
+ * per-block prefix of that map and the count; the map handle must outlive them or they must be cleared first.  Frames of THAT handle with an
+ * unchanged point count then take a point's colour from its word instead of the height palette - projection, footprint, depth key, the
+ * minimum, the overlay and eye-dome lighting are unchanged; the same handle with a changed count gives PTL_ERR_STATE from ptl_render_frames;
+ * any other handle draws palette frames as before. */
+int ptl_render_set_point_colors(ptl_render *r, ptl_icp *map, const uint32_t *rgba, int64_t n);
 /* n_frames frames of `map` (nullable: the overlay only) through cams[n_frames], in launches of max_frames_per_call frames.  Like
  * ptl_icp_map_score it waits for the handle's map update, only reads the map and keeps nothing in the map handle.  Outputs (host): rgba_out
  * n_frames x height x width words; depth_out (nullable) as many float32, +inf = empty; keys_out (nullable) as many raw 64-bit keys;
@@ -918,6 +968,57 @@ int ptl_pose_search_default_cfg(ptl_pose_search_cfg *cfg, double voxel_size);
  * n = 0 as well. */
 int ptl_icp_pose_hits(ptl_icp *map, const ptl_pose_search_cfg *cfg, const double *xyz, int64_t n, const double *poses16, int64_t n_poses,
                       ptl_pose_search_result *result, int32_t *hits_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * The world map painted: a lidar channel field per STORED map point.  A second pass over the sweeps that built a map, posed by
+ * the same trajectory, each with a field image u32[H][W] of the same pixels (reflectivity, signal, near-infrared, the range itself): every
+ * stored point gets the sum of the field values of the rays that ended AT it and their number.  All outputs are integers; sums of integers have
+ * no order, so every output is an exact function of the stored points and the set of (ray, value) pairs - the lane mapping, the launch
+ * geometry and the order of the sweeps do not change it.
+ * Ray: a pixel with a return.  Its end w is the world point the posed-scan pass gives it (ptl_icp_map_add_posed_*; the same device functions,
+ * so the same bits).  A pixel without a return is counted in n_no_return and adds nothing, whatever its field value.  A sweep with any column
+ * outside the trajectory's bounds is skipped as a whole and counted (n_scans_skipped), as ptl_icp_map_add_posed_* skips it.
+ * Per ray: its voxel is the map's own truncating index (int)(coordinate / vs) per axis; a w outside the key range (2^20 voxels either side, or
+ * not finite) makes the ray unmatched.  The voxel is looked up; for every stored point p of that voxel with p.x == w.x && p.y == w.y &&
+ * p.z == w.z (comparison of doubles): sum[p] += field[pixel] (u64), count[p] += 1 (u32).  A ray that matched at least one point counts in
+ * n_rays_matched; any other ray - into a full voxel, into an absent voxel, out of the key range - in n_rays_unmatched.
+ * Consequence: a map built from sweeps S on trajectory T and painted with S on T has count >= 1 at EVERY stored point (a voxel's first
+ * max_points_per_voxel points are among those rays), and n_rays_unmatched is exactly the number of returns the build did not store.
+ * The mean of a point is the caller's sum / count (the Python layer's PaintValues.mean), as is any colour made of it. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_paint_result) as the caller knows it (PTL_CFG_INIT): ptl_paint_read refuses another size or version */
+    uint32_t abi_version;
+    int64_t n_points;                                      /* stored points of the map (the length of the per-point arrays) */
+    int64_t n_points_painted;                              /* points with count > 0 */
+    int64_t n_scans, n_scans_skipped;                      /* sweeps painted / skipped as outside the trajectory's bounds */
+    int64_t n_rays_matched, n_rays_unmatched, n_no_return; /* pixels of the painted sweeps */
+    int64_t sum_count;                                     /* the sum of count over the stored points */
+    double device_ms;                                      /* HIP-event time of the handle's device work so far: prefixes, sweeps, the read's reduction */
+} ptl_paint_result;
+typedef struct ptl_paint ptl_paint; /* the sums for one map: its own stream, column table, sweep and field staging, sum and count arrays */
+/* the library's sizeof(ptl_paint_result) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_paint_sizeof_result(void);
+/* Waits for the map's update, snapshots its point count and the per-block prefixes of the pool order (block id, then slot: the order of
+ * ptl_carve_read's, ptl_icp_map_score's and ptl_icp_map_compare's per-point outputs) and clears sum and count.  The map handle must outlive
+ * the paint handle and is only ever read.  Null map / out: PTL_ERR_ARG before any HIP call. */
+int ptl_paint_create(ptl_icp *map, ptl_paint **out);
+int ptl_paint_destroy(ptl_paint *p);
+/* one posed sweep, with the arguments of ptl_icp_map_add_posed_range / _xyz, and its field image (H x W u32, row-major, the pixels of the
+ * sweep): *n_matched = the sweep's matched rays (nullable), *skipped = 1 when a column lay outside the bounds and nothing was counted but the
+ * sweep (nullable).  Trajectory, LUT and map on one device (else PTL_ERR_ARG with the ids); W = the map handle's scan_cols and H W <= its
+ * max_points_per_scan (else PTL_ERR_CAPACITY with the numbers) - all before any HIP call.  Every add and read compares the map's point count with
+ * the snapshot: a map updated since ptl_paint_create gives PTL_ERR_STATE.  PTL_ERR_STATE as well when the map's table leads a probe to a block
+ * outside the pool or to one whose first point is not in the probed voxel. */
+int ptl_paint_add_posed_range(ptl_paint *p, ptl_traj *t, ptl_lut *lut, const uint32_t *range_mm, const uint32_t *field, const double *col_ts,
+                              int64_t *n_matched, int32_t *skipped);
+int ptl_paint_add_posed_xyz(ptl_paint *p, ptl_traj *t, const float *xyz, const uint32_t *field, int32_t H, int32_t W, const double *col_ts,
+                            int64_t *n_matched, int32_t *skipped);
+/* the summary so far, and (all three arrays given, or none) every stored point (3 doubles) with its sum and count in pool order; *n_written
+ * (nullable) their number.  result->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is refused with
+ * PTL_ERR_ARG and nothing is written.  max_points below the map's point count: PTL_ERR_CAPACITY naming the count, nothing written.  The values
+ * stay: sweeps may be added and read again. */
+int ptl_paint_read(ptl_paint *p, ptl_paint_result *result, double *xyz_out, uint64_t *sum_out, uint32_t *count_out, int64_t max_points,
+                   int64_t *n_written);
 
 #ifdef __cplusplus
 }

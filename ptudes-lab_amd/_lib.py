@@ -67,6 +67,16 @@ class PktFormat(_Cfg):
                 ("columns_per_frame", C.c_int32), ("columns_per_packet", C.c_int32)]
 
 
+class PktField(_Cfg):
+    """ptl_pkt_field (include/ptudes_mi.h): `bytes` at byte `offset` of a pixel, (word & mask) << shift (>> -shift)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("offset", C.c_int32), ("bytes", C.c_int32), ("mask", C.c_uint32),
+                ("shift", C.c_int32)]
+
+
+PKT_FIELDS = ("RANGE", "REFLECTIVITY", "SIGNAL", "NEAR_IR", "RANGE2", "REFLECTIVITY2", "SIGNAL2")  # PTL_PKT_FIELD_* in id order
+PKT_MAX_FIELDS = 4
+
+
 class PktSummary(C.Structure):
     _fields_ = [("frame_id", C.c_uint32), ("valid_columns", C.c_uint32), ("first_valid_id", C.c_uint32), ("last_valid_id", C.c_uint32),
                 ("first_valid_ts", C.c_uint64), ("last_valid_ts", C.c_uint64), ("nonzero_ranges", C.c_uint32),
@@ -124,6 +134,13 @@ class CarveResult(C.Structure):
                 ("n_rays_out_of_range", C.c_int64), ("n_no_return", C.c_int64), ("n_voxel_visits", C.c_int64), ("n_points_through", C.c_int64),
                 ("n_points_supported", C.c_int64), ("sum_through", C.c_int64), ("sum_support", C.c_int64), ("radius", C.c_double),
                 ("margin", C.c_double), ("step", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("device_ms", C.c_double)]
+
+
+class PaintResult(_Cfg):
+    """ptl_paint_result (include/ptudes_mi.h): an output that carries the caller's {struct_size, abi_version} in front"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("n_points", C.c_int64), ("n_points_painted", C.c_int64),
+                ("n_scans", C.c_int64), ("n_scans_skipped", C.c_int64), ("n_rays_matched", C.c_int64), ("n_rays_unmatched", C.c_int64),
+                ("n_no_return", C.c_int64), ("sum_count", C.c_int64), ("device_ms", C.c_double)]
 
 
 class PoseSearchCfg(_Cfg):
@@ -263,6 +280,11 @@ PROTOTYPES = {
     "ptl_pktdec_destroy": (C.c_int, [_vp]),
     "ptl_pktdec_decode": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp, _vp]),
     "ptl_pktdec_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),
+    # the channel fields of a pixel beside its range (include/ptudes_mi.h)
+    "ptl_pkt_sizeof_field": (C.c_int64, []),
+    "ptl_pkt_field_default": (C.c_int, [C.POINTER(PktFormat), C.c_int32, C.POINTER(PktField)]),
+    "ptl_pktdec_decode_fields": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.POINTER(PktField), C.c_int32, _vpp,
+                                           _vp, _vp, _vp, _vp]),
     "ptl_seq_upload_packets": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
     "ptl_batch_upload_packets": (C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PktSummary), _vp]),
     # sharpness of a map without ground truth (include/ptudes_mi.h)
@@ -277,6 +299,7 @@ PROTOTYPES = {
     "ptl_render_set_palette": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "ptl_render_set_z_range": (C.c_int, [_vp, C.c_double, C.c_double]),
     "ptl_render_set_overlay":(C.c_int, [_vp, c_d_p, C.POINTER(C.c_uint32), C.c_int64, C.c_int32]),
+    "ptl_render_set_point_colors": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), C.c_int64]),
     "ptl_render_frames": (C.c_int, [_vp, _vp, C.POINTER(RenderCam), C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                     C.POINTER(C.c_uint64), c_i64_p, c_d_p]),
     "ptl_render_debug_set_early_reject": (C.c_int, [_vp, C.c_int32]),
@@ -300,6 +323,14 @@ PROTOTYPES = {
     "ptl_pose_search_default_cfg": (C.c_int, [C.POINTER(PoseSearchCfg), C.c_double]),
     "ptl_icp_pose_hits": (C.c_int, [_vp, C.POINTER(PoseSearchCfg), c_d_p, C.c_int64, c_d_p, C.c_int64, C.POINTER(PoseSearchResult),
                                     C.POINTER(C.c_int32)]),
+    # the map painted: a lidar field summed per stored point (include/ptudes_mi.h)
+    "ptl_paint_sizeof_result": (C.c_int64, []),
+    "ptl_paint_create": (C.c_int, [_vp, _vpp]),
+    "ptl_paint_destroy": (C.c_int, [_vp]),
+    "ptl_paint_add_posed_range": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_paint_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int32, C.c_int32, c_d_p, c_i64_p,
+                                          C.POINTER(C.c_int32)]),
+    "ptl_paint_read": (C.c_int, [_vp, C.POINTER(PaintResult), c_d_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int64, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -13,7 +13,9 @@ own packet decoder (packets.py) when it is not, or with --native-packets - every
 cloud on the GPU: accuracy, completeness, precision / recall / F per threshold.  `--carve` passes over the same sweeps a
 second time and takes the points that later rays went through - a moving object's trail - out of the map before it is saved, scored or
 compared (both maps' figures are printed); `--save-carved` writes every stored point with its votes.  The frames draw the
-map as accumulated.
+map as accumulated.  `--color-by range|reflectivity|signal|near_ir` paints the map: a second pass over the same sweeps gives every stored point
+the mean of that lidar field over the rays that ended at it; `--save-painted` writes the points with it, and the frames after the map is built
+take its colours.
 """
 from typing import Optional
 
@@ -61,6 +63,38 @@ def frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_r
     return out
 
 
+COLOR_FIELDS = ("range", "reflectivity", "signal", "near_ir")
+
+
+def paint_options(color_by, color_range, save_painted, synthetic, carve, kitti_poses):
+    """the options of --color-by checked before a device is touched: None without it, else dict(field, lo, hi, save)"""
+    if not color_by:
+        for name, v in (("--color-range", color_range), ("--save-painted", save_painted)):
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --color-by")
+        return None
+    field = color_by.lower()
+    if field not in COLOR_FIELDS:
+        raise click.ClickException(f"--color-by {color_by}: one of {', '.join(COLOR_FIELDS)}")
+    if synthetic is not None and field != "range":
+        raise click.ClickException(f"--color-by {field}: the sweeps of --synthetic are range images only, they carry no {field}; --color-by range works")
+    if carve:
+        raise click.ClickException(f"--color-by {field} with --carve: painting a carved map is not supported (the paint is of the map as accumulated)")
+    if kitti_poses:
+        raise click.ClickException(f"--color-by {field} with --kitti-poses: the paint needs the column poses of --nc-gt-poses")
+    lo = hi = None
+    if color_range is not None:
+        try:
+            lo, hi = (float(x) for x in color_range.split(","))
+        except ValueError:
+            raise click.ClickException(f"--color-range {color_range}: expected LO,HI")
+        if not hi > lo:
+            raise click.ClickException(f"--color-range {color_range}: HI must be above LO")
+    if save_painted is not None and not str(save_painted).endswith(".ply"):
+        raise click.ClickException(f"--save-painted {save_painted}: a .ply path (the per-point values are written to a PLY file only)")
+    return dict(field=field, lo=lo, hi=hi, save=save_painted)
+
+
 @click.command(name="flyby")
 @click.argument("file", required=False, type=click.Path())
 @click.option("-m", "--meta", required=False, type=click.Path(exists=True, dir_okay=False, readable=True),
@@ -98,6 +132,15 @@ def frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_r
 @click.option("--z-range", type=str, default=None,
               help="heights LO,HI of the palette's ends for --save-frames (default: the map's own z extent once it is built; while it is "
                    "being built, the sensor's height +- 10 m)")
+@click.option("--color-by", type=str, default=None,
+              help="paint the map: a second pass over the same sweeps gives every stored point the mean of this lidar field (range, "
+                   "reflectivity, signal or near_ir) over the rays that ended at it, and prints the counts.  With --save-frames the frames "
+                   "AFTER the map is built take the field's colours; the frames drawn while it is being built keep the height palette "
+                   "(the order of the stored points moves while the map grows)")
+@click.option("--color-range", type=str, default=None,
+              help="field values LO,HI of the palette's ends for --color-by (default: the 1st and 99th percentile of the painted points)")
+@click.option("--save-painted", required=False, type=click.Path(dir_okay=False),
+              help="write every stored point with FIELD (the mean, NaN where no ray ended) and FIELD_count to this PLY file")
 @_compare_click_options
 @_carve_click_options
 def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional[str], nc_gt_poses: Optional[str], rate: float,
@@ -109,12 +152,14 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
                  compare_threshold: Optional[str] = None, compare_max_dist: Optional[float] = None, compare_pose: Optional[str] = None,
                  save_map_error: Optional[str] = None, carve: bool = False, save_carved: Optional[str] = None,
                  carve_radius: Optional[float] = None, carve_margin: Optional[float] = None, carve_max_range: Optional[float] = None,
-                 carve_min_through: Optional[int] = None, carve_min_fraction: Optional[float] = None) -> None:
+                 carve_min_through: Optional[int] = None, carve_min_fraction: Optional[float] = None, color_by: Optional[str] = None,
+                 color_range: Optional[str] = None, save_painted: Optional[str] = None) -> None:
     """Map of the lidar scans with poses (the flyby visualizer's map, headless).
 
     Data is provided via FILE in Ouster raw packets formats (PCAP or BAG with lidar/imu packets), or --synthetic SEED.
     """
     frames = frame_options(save_frames, frame_size, fps, max_frames, point_size, edl, z_range)
+    painting = paint_options(color_by, color_range, save_painted, synthetic, carve, kitti_poses)
     from .ekf_bench import compare_options, run_compare
     compare = compare_options(compare_map, compare_threshold, compare_max_dist, compare_pose, save_map_error, voxel_size)
     from .ekf_bench import carve_options, carve_report
@@ -172,8 +217,13 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
             raise click.ClickException("File not found, please specify a metadata file with `-m`")
         print(f"Reading metadata from: {meta}")
         info = pk.read_metadata_json(meta)
+        if painting is not None:
+            try:  # (the library's table, a host function: no device is touched)
+                core.pkt_field(pk.OusterPacketFormat.from_info(info), painting["field"])
+            except ValueError as e:
+                raise click.ClickException(f"--color-by {painting['field']}: {e}")
         lut = fly.sensor_lut(info)
-        bags = sorted(path.glob("*.bag")) if path.is_dir() else path
+        bags =sorted(path.glob("*.bag")) if path.is_dir() else path
         scans = None  # (fly.add_packet_bag below: a decoded sweep carries `range` and its decoded column times)
     else:
         from ..utils import read_metadata_json, read_packet_source
@@ -189,11 +239,33 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
                 if idx > end_scan:
                     break
                 if idx >= start_scan:
-                    yield fly.PosedScan(ls.field(client.ChanField.RANGE), np.asarray(ls.timestamp))
+                    scan = fly.PosedScan(ls.field(client.ChanField.RANGE), np.asarray(ls.timestamp))
+                    if painting is not None and painting["field"] != "range":
+                        scan.fields = {painting["field"]: np.asarray(ls.field(getattr(client.ChanField, painting["field"].upper())), dtype=np.uint32)}
+                    yield scan
         scans = real_scans()
 
     traj = core.Traj([t for t, _ in gts_poses], [p for _, p in gts_poses], TIME_BOUNDS, TIME_BOUNDS)
     acc = fly.MapAccumulator(lut, voxel_size=voxel_size)
+    painted = []  # the core.PaintValues of --color-by, once the pass has run
+
+    def paint_pass():
+        # the second pass over the same sweeps with their field, on the map as it stands
+        painter = fly.MapPainter(acc)
+        try:
+            if native:
+                fly.paint_packet_bag(painter, bags, info, traj, painting["field"], start_scan, end_scan)
+            else:
+                for scan in (scans if isinstance(scans, list) else real_scans()):
+                    painter.update(scan, traj, painting["field"])
+            painted.append(painter.values())
+        finally:
+            painter.close()
+        return painted[-1]
+
+    def point_colors():
+        return fly.scalar_colors(paint_pass().mean(), painting["lo"], painting["hi"])
+
     if frames is not None:
         import os
         from ..utils import save_png
@@ -219,7 +291,7 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
             print(f"playback: {rate}")
 
         fb = fly.FlyBy(acc, renderer, gts_poses, fps=frames["fps"], rate=rate, time_bounds=TIME_BOUNDS, z_range=frames["z_range"],
-                       max_frames=frames["max_frames"], on_state=osd)
+                       max_frames=frames["max_frames"], on_state=osd, point_colors=point_colors if painting is not None else None)
         n_written = 0
         for _, rgba in fb.frames(scans, traj=traj):
             save_png(os.path.join(frames["dir"], f"frame_{n_written:06d}.png"), rgba)
@@ -237,6 +309,17 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
     print(f"map of scans: {start_scan} - {end_scan}")
     print(f"map num points: {points}")
     print(f"map voxels: {voxels} (voxel size {voxel_size})")
+    if painting is not None:
+        values = painted[-1] if painted else paint_pass()  # (the frames ran the pass when they got past BUILDING)
+        name = painting["field"]
+        print(f"painted by {name}:")
+        print("\n".join(values.lines()))
+        mean = values.mean()
+        if np.isfinite(mean).any():
+            print(f"  {name}: mean of the painted points {float(np.nanmean(mean)):.6g}, min {float(np.nanmin(mean)):.6g}, max {float(np.nanmax(mean)):.6g}")
+        if painting["save"]:
+            save_map_ply(painting["save"], values.xyz, {name: mean, name + "_count": values.count})
+            print(f"Painted map saved to: {painting['save']}")
     if carving is not None:
         # the second pass over the same sweeps; the frames above drew the map as accumulated
         carver = fly.MapCarver(acc, **carving["cfg"])

@@ -617,6 +617,86 @@ class Carver:
         return CarveVotes(xyz[:k].copy(), thr[:k].copy(), sup[:k].copy(), *(int(v) for v in vals[:11]), *(float(v) for v in vals[11:]))
 
 
+@dataclass
+class PaintValues:
+    """What `Painter.values()` returns (include/ptudes_mi.h ptl_paint_result): every stored point of the map in pool order
+    with the sum of the field values of the rays that ended at it and their number, and the summary - a `_lib.PaintResult`, all counts exact"""
+    xyz: np.ndarray      # (N, 3)
+    sum: np.ndarray      # (N,) uint64
+    count: np.ndarray    # (N,) uint32
+    result: object
+
+    def mean(self):
+        """fp64 sum / count per stored point, NaN where no ray ended at the point"""
+        out = np.full(len(self.count), np.nan)
+        hit = self.count > 0
+        out[hit] = self.sum[hit].astype(np.float64) / self.count[hit].astype(np.float64)
+        return out
+
+    def lines(self):
+        """the block the commands print"""
+        r = self.result
+        return [f"paint: sweeps {r.n_scans} (skipped {r.n_scans_skipped}), rays matched {r.n_rays_matched}, unmatched {r.n_rays_unmatched}, "
+                f"no return {r.n_no_return}",
+                f"  points: {r.n_points} (painted {r.n_points_painted}), values added {r.sum_count}"]
+
+
+class Painter:
+    """The map painted (include/ptudes_mi.h ptl_paint_*): a second pass over the sweeps that built `map_icp`'s map, posed by
+    the same trajectory, each with a field image (H, W) uint32, sums for every stored point the field values of the rays that ended at it.
+    The map is only read and must not be updated (nor closed) while the painter lives: a map updated since gives a RuntimeError at the next
+    add or read"""
+
+    def __init__(self, map_icp):
+        self.map_icp = map_icp
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_paint_create(map_icp._h, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_paint_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_posed(self, traj, col_ts, field, range_mm=None, lut=None, xyz=None, H=None):
+        """one posed sweep, with the arguments of `Icp.map_add_posed`, and its field image.  Returns (n_matched, skipped): the sweep's rays
+        that ended at a stored point; a sweep with a column outside the trajectory's bounds is skipped as a whole"""
+        t = L.as_f64(col_ts).reshape(-1)
+        f = np.ascontiguousarray(field, dtype=np.uint32).reshape(-1)
+        nv, sk = C.c_int64(), C.c_int32()
+        u32p = C.POINTER(C.c_uint32)
+        if (range_mm is None) == (xyz is None):
+            raise ValueError("give range_mm (with lut) or xyz")
+        if range_mm is not None:
+            if lut is None:
+                raise ValueError("a range image needs its lut")
+            r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+            if r.size != lut.H * lut.W or len(t) != lut.W or f.size != r.size:
+                raise ValueError("need an H x W range image, an H x W field image and one time per column")
+            L.check(L.lib().ptl_paint_add_posed_range(self._h, traj._h, lut._h, r.ctypes.data_as(u32p), f.ctypes.data_as(u32p), L.dptr(t),
+                                                      C.byref(nv), C.byref(sk)))
+        else:
+            x = np.ascontiguousarray(xyz, dtype=np.float32)
+            W = len(t)
+            H = int(H) if H is not None else x.size // (3 * max(W, 1))
+            if x.size != H * W * 3 or f.size != H * W:
+                raise ValueError("need H x W x 3 points, an H x W field image and one time per column")
+            L.check(L.lib().ptl_paint_add_posed_xyz(self._h, traj._h, x.ctypes.data_as(C.POINTER(C.c_float)), f.ctypes.data_as(u32p), H, W,
+                                                    L.dptr(t), C.byref(nv), C.byref(sk)))
+        return nv.value, bool(sk.value)
+
+    def values(self):
+        """a `PaintValues` of the sweeps added so far; more may be added and read again"""
+        _, p = self.map_icp.map_size()
+        xyz, s, k = np.empty((max(p, 1), 3)), np.zeros(max(p, 1), dtype=np.uint64), np.zeros(max(p, 1), dtype=np.uint32)
+        res, w = L.PaintResult(), C.c_int64()
+        L.check(L.lib().ptl_paint_read(self._h, C.byref(res), L.dptr(xyz), s.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                       k.ctypes.data_as(C.POINTER(C.c_uint32)), p, C.byref(w)))
+        n = w.value
+        return PaintValues(xyz[:n].copy(), s[:n].copy(), k[:n].copy(), res)
+
+
 def rgba_word(rgba):
     """(..., 4) uint8 R, G, B, A -> the uint32 words the renderer's keys carry (R the lowest byte)"""
     a = np.ascontiguousarray(rgba, dtype=np.uint8)
@@ -673,6 +753,19 @@ class Renderer:
         col = np.asarray(rgba, dtype=np.uint8)
         w = np.ascontiguousarray(np.broadcast_to(rgba_word(col.reshape(-1, 4)), (len(x),)))
         L.check(L.lib().ptl_render_set_overlay(self._h, L.dptr(x), w.ctypes.data_as(C.POINTER(C.c_uint32)), len(x), int(point_px)))
+
+    def set_point_colors(self, icp, rgba):
+        """a colour of its own for every stored point of `icp`'s map (include/ptudes_mi.h ptl_render_set_point_colors): rgba
+        words (n,) uint32 or (n, 4) uint8 R G B A in pool order - the order of `Painter.values()`, `Carver.votes()` and the per-point map
+        score.  Frames of that handle then take a point's colour from its word instead of the height palette, until the colours are cleared;
+        a map that has grown since needs them set again"""
+        a = np.asarray(rgba)
+        w = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) if a.dtype != np.uint8 else np.ascontiguousarray(rgba_word(a.reshape(-1, 4)))
+        L.check(L.lib().ptl_render_set_point_colors(self._h, icp._h, w.ctypes.data_as(C.POINTER(C.c_uint32)), len(w)))
+
+    def clear_point_colors(self):
+        """back to the height palette for every map"""
+        L.check(L.lib().ptl_render_set_point_colors(self._h, None, None, 0))
 
     def set_early_reject(self, on):
         """measurement hook: the plain load in front of the atomic on or off (the frames do not change)"""
@@ -949,6 +1042,22 @@ def pkt_format(fmt):
     return f
 
 
+def pkt_field(fmt, name):
+    """the _lib.PktField of channel field `name` ("range", "reflectivity", "signal", "near_ir", "range2", "reflectivity2", "signal2", any
+    case, or a PTL_PKT_FIELD_* id) in the profile of `fmt` (a packets.OusterPacketFormat or an L.PktFormat): the library's table (include/
+    ptudes_mi.h, unpinned).  A ValueError naming profile and field where the profile has no such field"""
+    f = fmt if isinstance(fmt, L.PktFormat) else pkt_format(fmt)
+    if isinstance(name, str):
+        if name.upper() not in L.PKT_FIELDS:
+            raise ValueError(f"unknown lidar field '{name}' (known: {', '.join(n.lower() for n in L.PKT_FIELDS)})")
+        fid = L.PKT_FIELDS.index(name.upper())
+    else:
+        fid = int(name)
+    out = L.PktField()
+    L.check(L.lib().ptl_pkt_field_default(C.byref(f), fid, C.byref(out)))
+    return out
+
+
 def pkt_packet_bytes(fmt):
     """the library's size of a lidar packet of `fmt` (a packets.OusterPacketFormat or an L.PktFormat)"""
     f = fmt if isinstance(fmt, L.PktFormat) else pkt_format(fmt)
@@ -1016,11 +1125,38 @@ class PacketDecoder:
                                           C.c_void_p(ts.ctypes.data), C.c_void_p(st.ctypes.data), C.cast(sums, C.c_void_p)))
         return rng, ts, st, [sums[i].as_dict() for i in range(S)]
 
-    def decode(self, packets, sweep_of_packet, n_sweeps=None):
-        """-> [packets.PacketScan], one per sweep"""
+    def decode_field_arrays(self, packets, sweep_of_packet, fields, n_sweeps=None):
+        """`decode_arrays` and, from the same staged packets, the images of 1 .. 4 fields (names of `pkt_field`, or _lib.PktField
+        descriptors): ([field image (S, H, W) u32 per field], range, timestamp, status, [summary dict] * S); include/ptudes_mi.h
+        ptl_pktdec_decode_fields"""
+        a = _packet_rows(self.packet_bytes, packets)
+        sop = np.ascontiguousarray(sweep_of_packet, dtype=np.int32)
+        if len(sop) != len(a):
+            raise ValueError("one sweep index per packet")
+        desc = [f if isinstance(f, L.PktField) else pkt_field(self.format, f) for f in fields]
+        S = int(n_sweeps) if n_sweeps is not None else (int(sop.max()) + 1 if len(sop) else 0)
+        H, W = self.format.pixels_per_column, self.format.columns_per_frame
+        rng, ts, st = np.empty((S, H, W), np.uint32), np.empty((S, W), np.uint64), np.empty((S, W), np.uint16)
+        imgs = [np.empty((S, H, W), np.uint32) for _ in desc]
+        sums = (L.PktSummary * max(S, 1))()
+        cdesc = (L.PktField * max(len(desc), 1))(*desc)
+        outs = (C.c_void_p * max(len(desc), 1))(*[im.ctypes.data for im in imgs])
+        L.check(L.lib().ptl_pktdec_decode_fields(self._h, C.c_void_p(a.ctypes.data), a.strides[0] if len(a) else self.packet_bytes, len(a),
+                                                 sop.ctypes.data_as(C.POINTER(C.c_int32)), S, cdesc, len(desc), outs,
+                                                 C.c_void_p(rng.ctypes.data), C.c_void_p(ts.ctypes.data), C.c_void_p(st.ctypes.data),
+                                                 C.cast(sums, C.c_void_p)))
+        return imgs, rng, ts, st, [sums[i].as_dict() for i in range(S)]
+
+    def decode(self, packets, sweep_of_packet, n_sweeps=None, fields=()):
+        """-> [packets.PacketScan], one per sweep; fields: names of `pkt_field` (at most 4) whose images each scan carries in `.fields`"""
         from .packets import PacketScan
-        rng, ts, st, sums = self.decode_arrays(packets, sweep_of_packet, n_sweeps)
-        return [PacketScan(rng[i], ts[i], st[i], sums[i]["frame_id"], sums[i]) for i in range(len(sums))]
+        if not fields:
+            rng, ts, st, sums = self.decode_arrays(packets, sweep_of_packet, n_sweeps)
+            return [PacketScan(rng[i], ts[i], st[i], sums[i]["frame_id"], sums[i]) for i in range(len(sums))]
+        names = [str(f).lower() for f in fields]
+        imgs, rng, ts, st, sums = self.decode_field_arrays(packets, sweep_of_packet, names, n_sweeps)
+        return [PacketScan(rng[i], ts[i], st[i], sums[i]["frame_id"], sums[i], fields={n: im[i] for n, im in zip(names, imgs)})
+                for i in range(len(sums))]
 
 
 def _upload_packets(call, dec, packets, W, want_ts):

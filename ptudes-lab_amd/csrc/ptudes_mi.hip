@@ -8,10 +8,12 @@
 #include "seq_kernel.h"
 #include "fly_kernels.h"
 #include "packet_kernels.h"
+#include "packet_field_kernels.h"
 #include "score_kernels.h"
 #include "render_kernels.h"
 #include "compare_kernels.h"
 #include "carve_kernels.h"
+#include "paint_kernels.h"
 #include "pose_kernels.h"
 #include "hip_own.h"
 
@@ -3625,6 +3627,194 @@ extern "C" int ptl_carve_read(ptl_carve* h, ptl_carve_result* result, double* xy
     return PTL_OK;
 }
 
+// ================================================================================================ the map painted
+// The definition is in include/ptudes_mi.h, the kernels in paint_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// paint handle owns what its passes need - stream, column table, sweep and field staging, prefixes, sum and count arrays, counters - and only
+// reads the map handle.
+struct ptl_paint {
+    int device_id = 0;  // (first member, as in ptl_traj)
+    ptl_icp* map = nullptr;
+    int64_t n_points = 0;  // the map's point count at create: every add and read compares
+    int n_alloc = 1;
+    double device_ms = 0;
+    Stream stream;
+    Event e0, e1;
+    double* coltab = nullptr;   // [12][W]
+    double* d_ts = nullptr;     // [W]
+    void* d_raw = nullptr;      // one sweep of the caller's: n_max pixels of f32 xyz or u32 ranges
+    unsigned* d_field = nullptr;  // [n_max] the sweep's field image
+    FlyWs* d_fly = nullptr;     // k_fly_coltab's flag
+    int* d_blk_off = nullptr;   // [pool_cap]
+    unsigned long long* d_sum = nullptr;  // [n_alloc], pool order
+    unsigned* d_count = nullptr;          // [n_alloc]
+    double* d_xyz = nullptr;    // [n_alloc][3], made by the first read that asks for it
+    unsigned long long* d_counts = nullptr;  // [PAINT_COUNTERS] + 2 of the read's reduction
+    int* d_bad = nullptr;
+    unsigned long long counts[PAINT_COUNTERS] = {};  // the host's copy after the last add
+    DevOwner mem;
+};
+extern "C" int64_t ptl_paint_sizeof_result(void) { return (int64_t)sizeof(ptl_paint_result); }
+// the event pair around a piece of the handle's device work, added to its device_ms (the stream has been waited for)
+static int paint_clock(ptl_paint* h) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    h->device_ms += ms;
+    return PTL_OK;
+}
+// the map as it is now: its update waited for, its point count against the snapshot
+static int paint_map_unchanged(ptl_paint* h, const char* who) {
+    ptl_icp* m = h->map;
+    HIPCHK(hipSetDevice(h->device_id));
+    HIPCHK(hipStreamSynchronize(m->map_stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, m->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((int64_t)st.map_points != h->n_points)
+        return set_err(PTL_ERR_STATE, "%s: the map holds %lld points, it held %lld at ptl_paint_create: a map updated since then needs a new paint handle", who,
+                       (long long)st.map_points, (long long)h->n_points);
+    return PTL_OK;
+}
+extern "C" int ptl_paint_create(ptl_icp* map, ptl_paint** out) {
+    if (!map || !out) return set_err(PTL_ERR_ARG, "ptl_paint_create: null argument");
+    HIPCHK(hipSetDevice(map->cfg.device_id));
+    std::unique_ptr<ptl_paint> h(new ptl_paint());
+    h->device_id = map->cfg.device_id; h->map = map;
+    HIPCHK(h->stream.create());
+    HIPCHK(h->e0.create(hipEventDefault)); HIPCHK(h->e1.create(hipEventDefault));
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    HIPCHK(hipStreamSynchronize(map->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t n = st.map_points;
+    if (n < 0 || n > (int64_t)0x7fffffff) return set_err(PTL_ERR_STATE, "ptl_paint_create: the map reports %lld points", (long long)n);
+    h->n_points = n; h->n_alloc = n > 0 ? (int)n : 1;
+    const Ctx& c = map->c;
+    const int n_chunks = (c.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    const size_t px = (size_t)map->n_max;
+    h->mem.add(&h->coltab, (size_t)12 * c.W); h->mem.add(&h->d_ts, (size_t)c.W);
+    { unsigned char* raw = nullptr; h->mem.add(&raw, px * 12); h->d_raw = raw; }
+    h->mem.add(&h->d_field, px);
+    h->mem.add(&h->d_fly, 1); h->mem.add(&h->d_blk_off, (size_t)c.pool_cap);
+    h->mem.add(&h->d_sum, (size_t)h->n_alloc); h->mem.add(&h->d_count, (size_t)h->n_alloc);
+    h->mem.add(&h->d_counts, (size_t)PAINT_COUNTERS + 2); h->mem.add(&h->d_bad, 1);
+    HIPCHK(h->mem.err);
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1);
+    HIPCHK(tmp.err);
+    hipStream_t s = h->stream;
+    HIPCHK(hipEventRecord(h->e0, s));
+    HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), s));
+    HIPCHK(hipMemsetAsync(h->d_sum, 0, (size_t)h->n_alloc * 8, s));
+    HIPCHK(hipMemsetAsync(h->d_count, 0, (size_t)h->n_alloc * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_counts, 0, ((size_t)PAINT_COUNTERS + 2) * 8, s));
+    HIPCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), s));
+    k_score_count<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    k_carve_blkoff<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_off, h->d_blk_off);
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total != (int)n) return set_err(PTL_ERR_STATE, "ptl_paint_create: the block directory holds %d points, the map state %lld", total, (long long)n);
+    { int rc = paint_clock(h.get()); if (rc) return rc; }
+    *out = h.release();
+    return PTL_OK;
+}
+extern "C" int ptl_paint_destroy(ptl_paint* p) { return p ? handle_destroy(p, p->device_id) : PTL_OK; }
+// one sweep: checked before any HIP call, staged (sweep, field, column times), enqueued behind k_fly_coltab, the counters and the table's
+// verdict read back; the deltas of the counters are the call's
+static int paint_add_percall(ptl_paint* h, ptl_traj* t, ptl_lut* lut, const void* raw_host, size_t raw_bytes, bool is_range, const uint32_t* field,
+                             int64_t H, int64_t W, const double* col_ts, int64_t* n_matched, int32_t* skipped, const char* who) {
+    const ptl_icp* m = h->map;
+    if (t->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: trajectory on device %d, map on device %d", who, t->device_id, h->device_id);
+    if (lut && lut->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: LUT on device %d, map on device %d", who, lut->device_id, h->device_id);
+    if (H < 1 || W < 1) return set_err(PTL_ERR_ARG, "%s: empty scan (%lld x %lld)", who, (long long)H, (long long)W);
+    if (W != m->c.W) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld columns, the map handle's scan_cols is %d", who, (long long)W, m->c.W);
+    if (H * W > m->n_max) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the map handle's max_points_per_scan is %lld", who, (long long)(H * W), (long long)m->n_max);
+    int rc = paint_map_unchanged(h, who);
+    if (rc) return rc;
+    const Ctx& c = m->c;
+    hipStream_t s = h->stream;
+    const int n = (int)(H * W);
+    HIPCHK(hipEventRecord(h->e0, s));
+    HIPCHK(hipMemcpyAsync(h->d_raw, raw_host, raw_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_field, field, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_ts, col_ts, (size_t)W * 8, hipMemcpyHostToDevice, s));
+    PaintArgs a = {};
+    a.blk_off = h->d_blk_off; a.sum = h->d_sum; a.count = h->d_count; a.n_alloc = h->n_alloc; a.counts = h->d_counts; a.bad = h->d_bad;
+    const int wg = (n + PAINT_THREADS - 1) / PAINT_THREADS, grid = wg < PAINT_MAX_BLOCKS ? wg : PAINT_MAX_BLOCKS;
+    k_fly_coltab<<<1, 256, 0, s>>>(t->d_kt, t->d_kp, t->n, t->before, t->after, h->d_ts, 0.0, 0.0, (int)W, h->coltab, h->d_fly);
+    if (is_range) k_paint_rays<true><<<grid, PAINT_THREADS, 0, s>>>(h->d_raw, lut->dir, lut->off, h->d_field, n, (int)W, h->coltab, h->d_fly, c, a);
+    else k_paint_rays<false><<<grid, PAINT_THREADS, 0, s>>>(h->d_raw, nullptr, nullptr, h->d_field, n, (int)W, h->coltab, h->d_fly, c, a);
+    HIPCHK(hipGetLastError());
+    unsigned long long now[PAINT_COUNTERS];
+    int bad = 0;
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipMemcpyAsync(now, h->d_counts, sizeof now, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    rc = paint_clock(h);
+    if (rc) return rc;
+    if (n_matched) *n_matched = (int64_t)(now[PAINT_N_MATCHED] - h->counts[PAINT_N_MATCHED]);
+    if (skipped) *skipped = now[PAINT_N_SKIPPED] != h->counts[PAINT_N_SKIPPED] ? 1 : 0;
+    memcpy(h->counts, now, sizeof now);
+    if (bad) return set_err(PTL_ERR_STATE, "%s: the map's table led %d probes to a block that does not hold the probed voxel", who, bad);
+    return PTL_OK;
+}
+extern "C" int ptl_paint_add_posed_range(ptl_paint* p, ptl_traj* t, ptl_lut* lut, const uint32_t* range_mm, const uint32_t* field, const double* col_ts,
+                                         int64_t* n_matched, int32_t* skipped) {
+    if (!p || !t || !lut || !range_mm || !field || !col_ts) return set_err(PTL_ERR_ARG, "ptl_paint_add_posed_range: null argument");
+    return paint_add_percall(p, t, lut, range_mm, (size_t)lut->H * lut->W * 4, true, field, lut->H, lut->W, col_ts, n_matched, skipped, "ptl_paint_add_posed_range");
+}
+extern "C" int ptl_paint_add_posed_xyz(ptl_paint* p, ptl_traj* t, const float* xyz, const uint32_t* field, int32_t H, int32_t W, const double* col_ts,
+                                       int64_t* n_matched, int32_t* skipped) {
+    if (!p || !t || !xyz || !field || !col_ts) return set_err(PTL_ERR_ARG, "ptl_paint_add_posed_xyz: null argument");
+    return paint_add_percall(p, t, nullptr, xyz, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * 12, false, field, H, W, col_ts, n_matched, skipped, "ptl_paint_add_posed_xyz");
+}
+extern "C" int ptl_paint_read(ptl_paint* h, ptl_paint_result* result, double* xyz_out, uint64_t* sum_out, uint32_t* count_out, int64_t max_points,
+                              int64_t* n_written) {
+    if (!h || !result) return set_err(PTL_ERR_ARG, "ptl_paint_read: null argument");
+    ABI_CHECK(ptl_paint_result, result);
+    const int given = (xyz_out != nullptr) + (sum_out != nullptr) + (count_out != nullptr);
+    if (given != 0 && given != 3) return set_err(PTL_ERR_ARG, "ptl_paint_read: the three per-point arrays (xyz, sum, count) are given together or not at all (%d given)", given);
+    if (given && max_points < 0) return set_err(PTL_ERR_ARG, "ptl_paint_read: max_points = %lld: must not be negative", (long long)max_points);
+    const int64_t n = h->n_points;
+    if (given && max_points < n) return set_err(PTL_ERR_CAPACITY, "ptl_paint_read: the map holds %lld points, max_points = %lld", (long long)n, (long long)max_points);
+    { int rc = paint_map_unchanged(h, "ptl_paint_read"); if (rc) return rc; }
+    if (n_written) *n_written = 0;
+    hipStream_t s = h->stream;
+    if (given && n > 0 && !h->d_xyz) HIPCHK(h->mem.alloc(&h->d_xyz, (size_t)n * 3));
+    unsigned long long sums[2] = {0, 0};
+    HIPCHK(hipEventRecord(h->e0, s));
+    k_paint_reduce<<<1, 1024, 0, s>>>(h->d_count, (int)n, h->d_counts + PAINT_COUNTERS);
+    if (given && n > 0) k_carve_export<<<(h->map->c.pool_cap + 255) / 256, 256, 0, s>>>(h->map->c, h->d_blk_off, h->n_alloc, h->d_xyz);
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, h->d_counts + PAINT_COUNTERS, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    { int rc = paint_clock(h); if (rc) return rc; }
+    const uint32_t size = result->struct_size, abi = result->abi_version;
+    memset(result, 0, sizeof *result);
+    result->struct_size = size; result->abi_version = abi;
+    result->n_points = n; result->n_points_painted = (int64_t)sums[0];
+    result->n_scans = (int64_t)h->counts[PAINT_N_SCANS]; result->n_scans_skipped = (int64_t)h->counts[PAINT_N_SKIPPED];
+    result->n_rays_matched = (int64_t)h->counts[PAINT_N_MATCHED]; result->n_rays_unmatched = (int64_t)h->counts[PAINT_N_UNMATCHED];
+    result->n_no_return = (int64_t)h->counts[PAINT_N_NORET];
+    result->sum_count = (int64_t)sums[1];
+    result->device_ms = h->device_ms;
+    if (given && n > 0) {
+        HIPCHK(hipMemcpy(xyz_out, h->d_xyz, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sum_out, h->d_sum, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(count_out, h->d_count, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    if (given && n_written) *n_written = n;
+    return PTL_OK;
+}
+
 // ================================================================================================ fly-by frames
 // The definition is in include/ptudes_mi.h, the kernels in render_kernels.h.  Everything is checked on the host before the first HIP call.  The
 // renderer owns what one launch needs: the keys and the resolved outputs of max_frames_per_call frames, their cameras and counters.
@@ -3644,6 +3834,10 @@ struct ptl_render {
     unsigned* d_ov_rgba = nullptr;            // [ov_n]
     int64_t ov_n = 0;
     int ov_px = 1;
+    ptl_icp* col_map = nullptr;               // the map handle whose stored points carry colours of their own (ptl_render_set_point_colors)
+    int64_t col_n = 0;                        // its point count when they were set
+    unsigned* d_col_rgba = nullptr;           // [col_n], pool order
+    int* d_col_off = nullptr;                 // [pool_cap of col_map] exclusive prefix of the stored points per block id
     DevOwner mem;
 };
 static void render_defaults(ptl_render_cfg* cfg, int32_t width, int32_t height) {
@@ -3735,6 +3929,52 @@ extern "C" int ptl_render_set_overlay(ptl_render* r, const double* xyz, const ui
     r->ov_n = n; r->ov_px = point_px;
     return PTL_OK;
 }
+// colours per stored point of one map handle: the words, the renderer's own per-block prefix of that map, and the count
+extern "C" int ptl_render_set_point_colors(ptl_render* r, ptl_icp* map, const uint32_t* rgba, int64_t n) {
+    if (!r) return set_err(PTL_ERR_ARG, "ptl_render_set_point_colors: null renderer");
+    if (n < 0 || n > 0x7fffffffLL) return set_err(PTL_ERR_ARG, "ptl_render_set_point_colors: n = %lld (0 .. 2^31 - 1)", (long long)n);
+    const bool clear = !rgba || n == 0;
+    if (!clear && !map) return set_err(PTL_ERR_ARG, "ptl_render_set_point_colors: %lld colours without a map", (long long)n);
+    if (!clear && map->cfg.device_id != r->device_id)
+        return set_err(PTL_ERR_ARG, "ptl_render_set_point_colors: renderer on device %d, map on device %d", r->device_id, map->cfg.device_id);
+    HIPCHK(hipSetDevice(r->device_id));
+    HIPCHK(hipStreamSynchronize(r->stream));
+    r->mem.release(&r->d_col_rgba);
+    r->mem.release(&r->d_col_off);
+    r->col_map = nullptr; r->col_n = 0;
+    if (clear) return PTL_OK;
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, map->stream));
+    HIPCHK(hipStreamSynchronize(map->stream));
+    if ((int64_t)st.map_points != n)
+        return set_err(PTL_ERR_ARG, "ptl_render_set_point_colors: %lld colours for a map of %lld stored points: one word per stored point, in pool order",
+                       (long long)n, (long long)st.map_points);
+    const Ctx& c = map->c;
+    const int n_chunks = (c.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    HIPCHK(r->mem.alloc(&r->d_col_rgba, (size_t)n));
+    HIPCHK(r->mem.alloc(&r->d_col_off, (size_t)c.pool_cap));
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1);
+    HIPCHK(tmp.err);
+    const hipStream_t s = r->stream;
+    k_score_count<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    k_carve_blkoff<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_off, r->d_col_off);
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(r->d_col_rgba, rgba, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total != (int)n) {
+        r->mem.release(&r->d_col_rgba);
+        r->mem.release(&r->d_col_off);
+        return set_err(PTL_ERR_STATE, "ptl_render_set_point_colors: the block directory holds %d points, the map state %lld", total, (long long)n);
+    }
+    r->col_map = map; r->col_n = n;
+    return PTL_OK;
+}
 extern "C" int ptl_render_debug_set_early_reject(ptl_render* r, int32_t on) {
     if (!r) return set_err(PTL_ERR_ARG, "null argument");
     r->early_reject = on != 0;
@@ -3768,7 +4008,11 @@ extern "C" int ptl_render_frames(ptl_render* r, ptl_icp* map, const ptl_render_c
         HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, map->stream));
         HIPCHK(hipStreamSynchronize(map->stream));
         draw_map = st.map_points > 0;
+        if (map == r->col_map && (int64_t)st.map_points != r->col_n)
+            return set_err(PTL_ERR_STATE, "ptl_render_frames: the map holds %lld points, it held %lld when its point colours were set "
+                           "(ptl_render_set_point_colors): set them again for the map as it is, or clear them", (long long)st.map_points, (long long)r->col_n);
     }
+    const bool own_colors = map && map == r->col_map;
     const ptl_render_cfg& cfg = r->cfg;
     const hipStream_t s = r->stream;
     const size_t px = (size_t)cfg.width * (size_t)cfg.height;
@@ -3785,7 +4029,13 @@ extern "C" int ptl_render_frames(ptl_render* r, ptl_icp* map, const ptl_render_c
         HIPCHK(hipEventRecord(e0, s));
         HIPCHK(hipMemsetAsync(r->d_keys, 0xFF, (size_t)nf * px * 8, s));  // (k_render_clear: every key all ones)
         HIPCHK(hipMemsetAsync(r->d_in_view, 0, (size_t)nf * 8, s));
-        if (draw_map) {
+        if (draw_map && own_colors) {
+            ColorSrc src = {map->c, r->d_col_off, r->d_col_rgba, (int)r->col_n};
+            const int n_chunks = (map->c.pool_cap + 63) / 64, want = (n_chunks + RENDER_THREADS / 64 - 1) / (RENDER_THREADS / 64);
+            const dim3 grid((unsigned)std::max(1, std::min(want, RENDER_MAX_BLOCKS)), (unsigned)nf);
+            if (r->early_reject) k_render_splat<ColorSrc, true><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+            else k_render_splat<ColorSrc, false><<<grid, RENDER_THREADS, 0, s>>>(src, a);
+        } else if (draw_map) {
             MapSrc src = {map->c};
             const int n_chunks = (map->c.pool_cap + 63) / 64, want = (n_chunks + RENDER_THREADS / 64 - 1) / (RENDER_THREADS / 64);
             const dim3 grid((unsigned)std::max(1, std::min(want, RENDER_MAX_BLOCKS)), (unsigned)nf);
@@ -3867,6 +4117,7 @@ struct ptl_pktdec {
     int* d_sop = nullptr;             // [max_packets]
     PktOut o = {};                    // owner, first packet, timestamps, status, summaries: [max_sweeps]; o.img: the decoder's own images
     unsigned* d_img = nullptr;        // [max_sweeps][H][W]
+    unsigned* d_fimg = nullptr;       // [PKT_MAX_FIELDS][max_sweeps][H][W] field images, made by the first ptl_pktdec_decode_fields
     DevOwner mem;
 };
 extern "C" int ptl_pktdec_destroy(ptl_pktdec* d) { return d ? handle_destroy(d, d->device_id) : PTL_OK; }
@@ -3946,6 +4197,75 @@ extern "C" int ptl_pktdec_decode(ptl_pktdec* d, const void* packets, int64_t str
     const size_t S = (size_t)n_sweeps, W = (size_t)d->L.W;
     const hipStream_t st = d->stream;
     if (range_out) HIPCHK(hipMemcpyAsync(range_out, d->d_img, S * d->L.H * W * 4, hipMemcpyDeviceToHost, st));
+    if (col_ts_out) HIPCHK(hipMemcpyAsync(col_ts_out, d->o.ts, S * W * 8, hipMemcpyDeviceToHost, st));
+    if (col_status_out) HIPCHK(hipMemcpyAsync(col_status_out, d->o.status, S * W * 2, hipMemcpyDeviceToHost, st));
+    if (summary_out) HIPCHK(hipMemcpyAsync(summary_out, d->o.sum, S * sizeof(PktSummary), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return PTL_OK;
+}
+// ---- the channel fields of a pixel: the table of include/ptudes_mi.h as data, and one launch of packet_field_kernels.h behind
+// the three passes
+static_assert(PKT_MAX_FIELDS == PTL_PKT_MAX_FIELDS, "the kernel's field slots are the header's");
+extern "C" int64_t ptl_pkt_sizeof_field(void) { return (int64_t)sizeof(ptl_pkt_field); }
+static const char* const PKT_PROFILE_NAME[4] = {"LEGACY", "RNG19_RFL8_SIG16_NIR16", "RNG15_RFL8_NIR8", "RNG19_RFL8_SIG16_NIR16_DUAL"};
+static const char* const PKT_FIELD_NAME[7] = {"RANGE", "REFLECTIVITY", "SIGNAL", "NEAR_IR", "RANGE2", "REFLECTIVITY2", "SIGNAL2"};
+struct PktFieldRow { int offset, bytes; unsigned mask; int shift; };  // bytes == 0: the profile has no such field
+static const PktFieldRow PKT_FIELD_TABLE[4][7] = {
+    /* LEGACY */                      {{0, 4, 0x000fffffu, 0}, {4, 2, 0, 0}, {6, 2, 0, 0}, {8, 2, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}},
+    /* RNG19_RFL8_SIG16_NIR16 */      {{0, 4, 0x0007ffffu, 0}, {4, 1, 0, 0}, {6, 2, 0, 0}, {8, 2, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}},
+    /* RNG15_RFL8_NIR8 */             {{0, 2, 0x7fffu, 3}, {2, 1, 0, 0}, {0, 0, 0, 0}, {3, 1, 0, 4}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}},
+    /* RNG19_RFL8_SIG16_NIR16_DUAL */ {{0, 4, 0x0007ffffu, 0}, {3, 1, 0, 0}, {8, 2, 0, 0}, {12, 2, 0, 0}, {4, 4, 0x0007ffffu, 0}, {7, 1, 0, 0}, {10, 2, 0, 0}},
+};
+extern "C" int ptl_pkt_field_default(const ptl_pkt_format* fmt, int32_t field_id, ptl_pkt_field* out) {
+    if (!fmt || !out) return set_err(PTL_ERR_ARG, "ptl_pkt_field_default: null argument");
+    ABI_CHECK(ptl_pkt_format, fmt);
+    ABI_CHECK(ptl_pkt_field, out);
+    if (fmt->profile < 0 || fmt->profile > 3) return set_err(PTL_ERR_ARG, "ptl_pkt_field_default: unknown lidar packet profile %d (PTL_PKT_*)", fmt->profile);
+    if (field_id < 0 || field_id > 6) return set_err(PTL_ERR_ARG, "ptl_pkt_field_default: unknown field %d (PTL_PKT_FIELD_*: 0 .. 6)", field_id);
+    const PktFieldRow& r = PKT_FIELD_TABLE[fmt->profile][field_id];
+    if (r.bytes == 0)
+        return set_err(PTL_ERR_ARG, "ptl_pkt_field_default: profile %s (%d) has no field %s (%d)", PKT_PROFILE_NAME[fmt->profile], fmt->profile,
+                       PKT_FIELD_NAME[field_id], field_id);
+    out->offset = r.offset; out->bytes = r.bytes; out->mask = r.mask; out->shift = r.shift;
+    return PTL_OK;
+}
+extern "C" int ptl_pktdec_decode_fields(ptl_pktdec* d, const void* packets, int64_t stride_bytes, int64_t n, const int32_t* sweep_of_packet, int32_t n_sweeps,
+                                        const ptl_pkt_field* fields, int32_t n_fields, uint32_t* const* field_out, uint32_t* range_out,
+                                        uint64_t* col_ts_out, uint16_t* col_status_out, ptl_pkt_summary* summary_out) {
+    const char* who = "ptl_pktdec_decode_fields";
+    if (!sweep_of_packet || !fields || !field_out) return set_err(PTL_ERR_ARG, "%s: null argument", who);
+    int rc = pktdec_check(d, packets, stride_bytes, n, sweep_of_packet, n_sweeps, who);
+    if (rc) return rc;
+    if (n_fields < 1 || n_fields > PKT_MAX_FIELDS) return set_err(PTL_ERR_ARG, "%s: n_fields = %d: 1 .. %d fields per call", who, n_fields, PKT_MAX_FIELDS);
+    const PktLayout& L = d->L;
+    PktFields F = {};
+    F.n = n_fields;
+    for (int f = 0; f < n_fields; ++f) {
+        const ptl_pkt_field& q = fields[f];
+        ABI_CHECK(ptl_pkt_field, &q);
+        if (!field_out[f]) return set_err(PTL_ERR_ARG, "%s: field_out[%d] is null", who, f);
+        if (q.bytes != 1 && q.bytes != 2 && q.bytes != 4) return set_err(PTL_ERR_ARG, "%s: field %d: bytes = %d: a field has 1, 2 or 4 bytes", who, f, q.bytes);
+        if (q.offset < 0 || q.offset % q.bytes) return set_err(PTL_ERR_ARG, "%s: field %d: offset = %d is not a multiple of its %d bytes (or negative)", who, f, q.offset, q.bytes);
+        if ((int64_t)q.offset + q.bytes > L.pix)
+            return set_err(PTL_ERR_ARG, "%s: field %d: offset %d + %d bytes lies past the pixel of %d bytes", who, f, q.offset, q.bytes, L.pix);
+        if (q.shift < -31 || q.shift > 31) return set_err(PTL_ERR_ARG, "%s: field %d: shift = %d: -31 .. 31", who, f, q.shift);
+        F.off[f] = q.offset; F.bytes[f] = q.bytes; F.mask[f] = q.mask ? q.mask : 0xffffffffu; F.shift[f] = q.shift;
+    }
+    HIPCHK(hipSetDevice(d->device_id));
+    const size_t S = (size_t)n_sweeps, W = (size_t)L.W, image = (size_t)L.H * W;
+    if (!d->d_fimg) HIPCHK(d->mem.alloc(&d->d_fimg, (size_t)PKT_MAX_FIELDS * d->max_sweeps * image));
+    F.img_stride = image;
+    for (int f = 0; f < n_fields; ++f) F.img[f] = d->d_fimg + (size_t)f * d->max_sweeps * image;
+    rc = pktdec_run(d, packets, stride_bytes, n, sweep_of_packet, n_sweeps, d->o);
+    if (rc) return rc;
+    const hipStream_t st = d->stream;
+    HIPCHK(d->prof.begin(st));
+    hipLaunchKernelGGL(k_pkt_fields, dim3((unsigned)(n + (int64_t)n_sweeps * L.H)), dim3(PKT_THREADS), (size_t)L.stride, st, L, d->d_pkts, d->d_sop, (int)n,
+                       d->o, F);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d->prof.end(st));
+    for (int f = 0; f < n_fields; ++f) HIPCHK(hipMemcpyAsync(field_out[f], F.img[f], S * image * 4, hipMemcpyDeviceToHost, st));
+    if (range_out) HIPCHK(hipMemcpyAsync(range_out, d->d_img, S * image * 4, hipMemcpyDeviceToHost, st));
     if (col_ts_out) HIPCHK(hipMemcpyAsync(col_ts_out, d->o.ts, S * W * 8, hipMemcpyDeviceToHost, st));
     if (col_status_out) HIPCHK(hipMemcpyAsync(col_status_out, d->o.status, S * W * 2, hipMemcpyDeviceToHost, st));
     if (summary_out) HIPCHK(hipMemcpyAsync(summary_out, d->o.sum, S * sizeof(PktSummary), hipMemcpyDeviceToHost, st));

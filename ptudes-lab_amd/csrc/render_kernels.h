@@ -36,6 +36,7 @@
 // Clearing the keys is a memset with 0xFF on the renderer's stream.
 #pragma once
 #include "icp_kernels.h"
+#include "score_kernels.h"  // score_blk_count: the per-block count of the ColorSrc walk and of its prefix
 
 #define RENDER_THREADS 256
 #define RENDER_MAX_BLOCKS 2048   // workgroups per frame of a splat launch
@@ -136,6 +137,39 @@ template <bool EARLY>
 __device__ __forceinline__ void render_walk(const OverlaySrc& s, const RenderArgs& a, const RenderCam& cam, unsigned long long* keys, int& mine) {
     for (int i = blockIdx.x * RENDER_THREADS + threadIdx.x; i < s.n; i += gridDim.x * RENDER_THREADS)
         mine += render_point<EARLY>(a, cam, keys, s.xyz[3 * (size_t)i], s.xyz[3 * (size_t)i + 1], s.xyz[3 * (size_t)i + 2], s.rgba[i], s.point_px) ? 1 : 0;
+}
+
+// k_render_splat<ColorSrc>: the walk of MapSrc over the same pool with a colour word PER STORED POINT in pool order (block id, then slot:
+// ptl_render_set_point_colors) in place of the height palette; projection, footprint, depth key and the minimum are
+// render_point's, unchanged.  rgba[blk_off[b] + j] is point j of block b; blk_off is the exclusive prefix of score_blk_count over the block ids
+// (k_score_count / k_score_scan / k_carve_blkoff), and the walk's per-block count here is score_blk_count too: ONE function on both sides.
+struct ColorSrc {
+    Ctx c;
+    const int* blk_off;    // [pool_cap]
+    const unsigned* rgba;  // [n], pool order
+    int n;
+};
+template <bool EARLY>
+__device__ __forceinline__ void render_walk(const ColorSrc& s, const RenderArgs& a, const RenderCam& cam, unsigned long long* keys, int& mine) {
+    const Ctx& c = s.c;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = RENDER_THREADS / 64;
+    const int n_chunks = (c.pool_cap + 63) / 64;
+    const int S = c.n_small > 0 && c.P < SMALL_CAP ? SMALL_CAP : c.P;  // point slots per block of the walk
+    for (int ch = blockIdx.x * waves + wave; ch < n_chunks; ch += gridDim.x * waves) {
+        const int b = ch * 64 + lane;
+        const int cnt = b < c.pool_cap ? score_blk_count(c, b) : 0;
+        const int off = cnt > 0 ? s.blk_off[b] : 0;
+        if (__ballot(cnt > 0) == 0ull) continue;  // (uniform)
+        for (int it = 0; it < S; ++it) {
+            const int i = it * 64 + lane, bi = i / S, j = i - bi * S;
+            const int cb = __shfl(cnt, bi), ob = __shfl(off, bi);
+            if (j >= cb) continue;
+            const int oi = ob + j;
+            if (oi < 0 || oi >= s.n) continue;  // (cannot happen behind the set call's check of the directory's total)
+            const double* X = blk_x(c, ch * 64 + bi) + 3 * j;
+            mine += render_point<EARLY>(a, cam, keys, X[0], X[1], X[2], s.rgba[oi], a.point_px) ? 1 : 0;
+        }
+    }
 }
 
 template <class SRC, bool EARLY>

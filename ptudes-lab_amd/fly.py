@@ -223,6 +223,63 @@ class MapCarver:
         self.carver.close()
 
 
+class MapPainter:
+    """The second pass over the sweeps that built `acc`'s map with a channel field each: a core.Painter on the accumulator's
+    map handle, fed the way the accumulator was.  The map must not be updated while the painter lives"""
+
+    def __init__(self, acc):
+        self.acc = acc
+        self.painter = core.Painter(acc.icp)
+
+    def update(self, scan, traj, field):
+        """one PosedScan or packets.PacketScan, posed by `traj` (a core.Traj) at its column timestamps, as MapAccumulator.update(scan, traj)
+        adds it.  field: an (H, W) uint32 image of the sweep's pixels, or a name - "range" is the range image itself, any other name is looked
+        up in scan.fields (packets.PacketFeed(fields=...)).  Returns the sweep's rays that ended at a stored point"""
+        range_mm = scan.range_mm if hasattr(scan, "range_mm") else scan.range
+        if isinstance(field, str):
+            name = field.lower()
+            fields = getattr(scan, "fields", None) or {}
+            if name in fields:
+                field = fields[name]
+            elif name == "range":
+                field = range_mm
+            else:
+                raise ValueError(f"the scan carries no field '{name}' (it has: {', '.join(['range'] + sorted(fields))})")
+        n, _ = self.painter.add_posed(traj, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9, field, range_mm=range_mm, lut=self.acc.lut)
+        return n
+
+    def values(self):
+        return self.painter.values()
+
+    def close(self):
+        self.painter.close()
+
+
+def scalar_colors(values, lo=None, hi=None, palette=None, unpainted=(128, 128, 128, 255)):
+    """HOST POLICY, not part of the library's definition and not tuned: rgba words (n,) uint32 for per-point scalars (e.g. PaintValues.mean()),
+    for core.Renderer.set_point_colors.  Linear between lo and hi: palette entry clamp(floor((v - lo) 256 / (hi - lo)), 0, 255) - lo and
+    everything below it take entry 0, hi and everything above it entry 255; lo / hi default to the 1st / 99th percentile of the finite values
+    (0 and 1 when there is none).  hi <= lo leaves no slope: values below lo take entry 0, all others entry 255.  A value that is not finite
+    (a point no ray ended at) takes `unpainted`.  palette: (256, 4) uint8 R G B A, default the renderer's height ramp"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    finite = np.isfinite(v)
+    if lo is None:
+        lo = float(np.percentile(v[finite], 1.0)) if finite.any() else 0.0
+    if hi is None:
+        hi = float(np.percentile(v[finite], 99.0)) if finite.any() else 1.0
+    lo, hi = float(lo), float(hi)
+    pal = core.rgba_word(core.default_palette() if palette is None else np.asarray(palette, dtype=np.uint8).reshape(256, 4))
+    idx = np.zeros(len(v), dtype=np.int64)
+    x = np.where(finite, v, lo)
+    if hi > lo:
+        idx = np.clip(np.floor((x - lo) * (256.0 / (hi - lo))), 0.0, 255.0).astype(np.int64)
+    else:
+        idx = np.where(x < lo, 0, 255)
+    words = np.asarray(pal, dtype=np.uint32)[idx]
+    words[~finite] = core.rgba_word(np.asarray(unpainted, dtype=np.uint8).reshape(4))
+    return words
+
+
 # ------------------------------------------------------------------------------------------------ a sweep's pose in a saved map (DESIGN.md 3.26)
 def candidate_poses(keyframes, n_yaw, spacing=None):
     """Start poses for a search in a map: the keyframes (M, 4, 4) - poses the mapping run went through - thinned by travelled distance, each
@@ -558,8 +615,12 @@ class FlyBy:
     `frames(scans)` yields (state name, (H, W, 4) uint8) frame by frame; the trajectory's positions are the overlay."""
 
     def __init__(self, acc, renderer, poses, fps: float = 30, rate: float = 1.0, time_bounds: float = 1.5, z_range=None,
-                 max_frames: Optional[int] = None, track_px: int = 3, on_state=None):
+                 max_frames: Optional[int] = None, track_px: int = 3, on_state=None, point_colors=None):
         self.acc, self.renderer, self.poses = acc, renderer, list(poses)
+        # point_colors: a callable without arguments that returns one rgba word per stored point of acc's map in pool order
+        # (core.Renderer.set_point_colors).  It is called ONCE, when BUILDING has ended and the map stands: the pool order moves while blocks
+        # are added, so the BUILDING frames keep the height palette and the colours start with the first frame after them (DESIGN.md 3.27)
+        self.point_colors = point_colors
         self.dt = float(rate) / float(fps)
         self.time_bounds, self.z_range, self.max_frames, self.track_px = float(time_bounds), z_range, max_frames, int(track_px)
         self.camera = Camera()
@@ -630,6 +691,8 @@ class FlyBy:
             z = self.acc.map_points()[:, 2]
             lo, hi = (float(z.min()), float(z.max())) if len(z) else (0.0, 1.0)
             r.set_z_range(lo, hi if hi > lo else lo + 1.0)
+        if self.point_colors is not None:
+            r.set_point_colors(self.acc.icp, self.point_colors())
         state = self._create_state(building.update(self.dt, self.camera))
         self._enter(state.name)
         batch = int(r.cfg.max_frames_per_call)
@@ -693,6 +756,23 @@ def add_packet_bag(acc, bags, info, traj, start_scan=0, end_scan=None, device_id
         for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
             if not hasattr(d, "lacc"):
                 acc.update(d, traj=traj)
+    finally:
+        feed.close()
+
+
+def paint_packet_bag(painter, bags, info, traj, field, start_scan=0, end_scan=None, device_id=0):
+    """the counterpart of `add_packet_bag` for a `MapPainter`: the same sweeps of the same bag(s), decoded again by the package's packet feed -
+    with the channel field `field` ("range", "reflectivity", "signal", "near_ir"; a ValueError naming profile and field where the sensor's
+    profile has no such field) beside the range - and posed by `traj` at their decoded column times"""
+    from . import packets as pk
+    from .bag import OusterPacketBagSource
+    name = str(field).lower()
+    core.pkt_field(pk.OusterPacketFormat.from_info(info), name)  # (refused here, before the bag is opened)
+    feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info, device_id=device_id, fields=() if name == "range" else (name,))
+    try:
+        for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+            if not hasattr(d, "lacc"):
+                painter.update(d, traj, name)
     finally:
         feed.close()
 

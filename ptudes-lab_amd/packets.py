@@ -205,8 +205,9 @@ class PacketScan:
     `ts` = the last valid column's time in seconds (ouster client.last_valid_column_ts) - what KissICPWrapper.register_frame takes
     for device-LUT input and StreamStatsTracker.trackScan for its span."""
 
-    def __init__(self, range_mm, timestamp, status, frame_id, summary: Optional[dict] = None):
+    def __init__(self, range_mm, timestamp, status, frame_id, summary: Optional[dict] = None, fields: Optional[dict] = None):
         self.range = range_mm
+        self.fields = dict(fields or {})  # name -> (H, W) u32 image of a channel field, staggered like `range` (PacketFeed(fields=...))
         self.timestamp, self.status, self.frame_id = timestamp, status, int(frame_id)
         self.h, self.w = range_mm.shape
         self.summary = summary
@@ -225,11 +226,14 @@ class PacketFeed:
     `OusterLidarData` (data.py:12-92) with the package's own batching rule and the device decode.
     source: iterable of ("lidar" | "imu", payload bytes, bag time) - bag.OusterPacketBagSource.  decoder: anything with
     `decode(packets (n, packet bytes) u8, sweep_of_packet) -> [PacketScan]` (default: core.PacketDecoder on `device_id`).
-    Closed sweeps are held back until `chunk_sweeps` of them are complete, then decoded in one launch; the events leave in arrival order."""
+    Closed sweeps are held back until `chunk_sweeps` of them are complete, then decoded in one launch; the events leave in arrival order.
+    fields: up to 4 channel fields ("reflectivity", "signal", "near_ir", ... - core.pkt_field) decoded beside the range from the same staged
+    packets; each PacketScan then carries their (H, W) u32 images in `.fields`; the decoder must take `decode(..., fields=)`."""
 
-    def __init__(self, source, info, device_id: int = 0, decoder=None, chunk_sweeps: int = 8):
+    def __init__(self, source, info, device_id: int = 0, decoder=None, chunk_sweeps: int = 8, fields=()):
         self._source, self._info, self._device_id = source, info, device_id
         self.format = OusterPacketFormat.from_info(info)
+        self._fields = tuple(str(f).lower() for f in fields)  # channel fields each PacketScan carries in `.fields` (core.pkt_field names)
         self._decoder = decoder
         self._chunk = max(1, int(chunk_sweeps))
         self.dropped_wrong_length = 0
@@ -259,7 +263,10 @@ class PacketFeed:
                     buf[i] = np.frombuffer(p, dtype=np.uint8)
                     sop[i] = s
                     i += 1
-            scans = iter(self._dec().decode(buf, sop, n_sweeps=len(sweeps)))
+            if self._fields:
+                scans = iter(self._dec().decode(buf, sop, n_sweeps=len(sweeps), fields=self._fields))
+            else:
+                scans = iter(self._dec().decode(buf, sop, n_sweeps=len(sweeps)))
         for idx, d in pending:
             yield (idx, next(scans)) if isinstance(d, list) else (idx, d)
 

@@ -248,6 +248,8 @@ _PLY_SCORED_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("neighbours", "<i4"), ("pla
 _PLY_DIST_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("dist", "<f8")])
 _PLY_CARVE = (("uint", "through"), ("uint", "support"), ("uchar", "dynamic"))
 _PLY_CARVE_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("through", "<u4"), ("support", "<u4"), ("dynamic", "u1")])
+_PLY_PAINT_FIELDS = ("range", "reflectivity", "signal", "near_ir")
+_PLY_PAINT_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("mean", "<f8"), ("count", "<u4")])
 
 
 def save_map_ply(path: str, xyz, scalars=None) -> None:
@@ -258,6 +260,8 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
     scalars = {"dist": (N,)} - the per-point distance to a reference cloud (NaN = unmatched): one more property, `double dist`.
     scalars = {"through": (N,), "support": (N,), "dynamic": (N,)} - the votes of a carve and the host policy's flag: `uint
     through`, `uint support`, `uchar dynamic`.
+    scalars = {FIELD: (N,), FIELD + "_count": (N,)}, FIELD one of range / reflectivity / signal / near_ir - a painted map: `double
+    FIELD` (the mean of the field at the point, NaN where no ray ended) and `uint FIELD_count`; `load_map_ply(scalars=True)` gives the dict back.
     Without scalars the file is what it always was, byte for byte."""
     pts = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
     if isinstance(scalars, dict) and list(scalars) == ["through", "support", "dynamic"]:
@@ -272,6 +276,22 @@ def save_map_ply(path: str, xyz, scalars=None) -> None:
         extra = "".join(f"property {t} {name}\n" for t, name in _PLY_CARVE)
         with open(path, "wb") as f:
             f.write(_PLY_HEADER.format(n=len(pts)).replace("end_header\n", extra + "end_header\n").encode("ascii"))
+            f.write(rec.tobytes())
+        return
+    if isinstance(scalars, dict) and len(scalars) == 2 and list(scalars)[1] == list(scalars)[0] + "_count":
+        # a painted map: `double FIELD` (the mean of the field at the point, NaN = no ray ended there) and `uint FIELD_count`
+        name = list(scalars)[0]
+        if name not in _PLY_PAINT_FIELDS:
+            raise ValueError(f"scalars: a painted map's field is one of {', '.join(_PLY_PAINT_FIELDS)}, not '{name}'")
+        mean, count = np.asarray(scalars[name], dtype=np.float64).reshape(-1), np.asarray(scalars[name + "_count"]).reshape(-1)
+        if len(mean) != len(pts) or len(count) != len(pts):
+            raise ValueError(f"scalars: one {name} / {name}_count value per point")
+        if str(path).endswith(".npy"):
+            raise ValueError("per-point scalars are written to a PLY file only: a .npy map holds the points")
+        rec = np.empty(len(pts), dtype=_PLY_PAINT_DTYPE)
+        rec["xyz"], rec["mean"], rec["count"] = pts, mean, count
+        with open(path, "wb") as f:
+            f.write(_PLY_HEADER.format(n=len(pts)).replace("end_header\n", f"property double {name}\nproperty uint {name}_count\nend_header\n").encode("ascii"))
             f.write(rec.tobytes())
         return
     if isinstance(scalars, dict):
@@ -341,6 +361,15 @@ def load_map_ply(path: str, scalars: bool = False):
             rec = np.frombuffer(data, dtype=_PLY_CARVE_DTYPE)
             pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
             return (pts, {k: rec[k].copy() for _, k in _PLY_CARVE}) if scalars else pts
+        painted = [nm for nm in _PLY_PAINT_FIELDS if props == _PLY_XYZ + [("double", nm), ("uint", nm + "_count")]]
+        if painted and fmt == "binary_little_endian" and n is not None:
+            size = _PLY_PAINT_DTYPE.itemsize
+            data = f.read(n * size)
+            if len(data) != n * size:
+                raise ValueError(f"{path}: {n} vertices announced, {len(data) // size} present")
+            rec = np.frombuffer(data, dtype=_PLY_PAINT_DTYPE)
+            pts = np.ascontiguousarray(rec["xyz"], dtype=np.float64)
+            return (pts, {painted[0]: rec["mean"].astype(np.float64), painted[0] + "_count": rec["count"].copy()}) if scalars else pts
         if with_dist and fmt == "binary_little_endian" and n is not None:
             data = f.read(n * 32)
             if len(data) != n * 32:
