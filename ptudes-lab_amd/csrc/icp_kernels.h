@@ -28,6 +28,7 @@
 #pragma once
 #include "devmath.h"
 #include "diag.h"
+#include "top2.h"
 #include <stdint.h>
 #include <type_traits>
 
@@ -1789,12 +1790,14 @@ template <int RE> __device__ __forceinline__ int sel_entry(const int (&r)[RE], i
 }
 // NV stored voxels against the point with LP lanes: lane l <-> stored points l, l + LP, ... - every load of the call in
 // flight before the first distance is formed.  (bd, border, bp) / (b2d, b2o, b2p): the best and the second-best candidate
-// this lane has seen; sd = the smallest distance it has seen lose to both.
+// this lane has seen; sd = the smallest distance it has seen lose to both (top2.h: selects behind one branch per slot, the
+// same state whatever order the slots come in).
 template <int PC, int LP, int NV, class CT>
 __device__ __forceinline__ void scan_voxelsL(const CT& c, const int (&pb)[NV], const int (&vx)[NV], V3 s, int laneL, double& bd, double& sd,
                                              unsigned& border, V3& bp, double& b2d, unsigned& b2o, V3& b2p) {
     const int P = (PC > 0) ? PC : c.P;
     constexpr int NCH = (PC > 0) ? (PC + LP - 1) / LP : 24 / LP;  // chunks of LP stored points (P <= 24 when not compile-time)
+    Top2 st{bd, b2d, sd, border, b2o, bp, b2p};
     if (P <= 24) {
         double q[NV][NCH][3];
         bool act[NV][NCH];
@@ -1811,21 +1814,15 @@ __device__ __forceinline__ void scan_voxelsL(const CT& c, const int (&pb)[NV], c
                 q[v][k][2] = act[v][k] ? X[3 * idx + 2] : 0.0;
             }
         }
+        Top2Cand cd[NV * NCH];
 #pragma unroll
         for (int v = 0; v < NV; ++v)
 #pragma unroll
-            for (int k = 0; k < NCH; ++k)
-                if (act[v][k]) {
-                    const double dx = q[v][k][0] - s.x, dy = q[v][k][1] - s.y, dz = q[v][k][2] - s.z;
-                    const double d2 = dx * dx + dy * dy + dz * dz;
-                    const unsigned id = (unsigned)(vx[v] * 32 + LP * k + laneL);
-                    if (d2 < bd || (d2 == bd && id < border)) {
-                        sd = fmin(sd, b2d); b2d = bd; b2o = border; b2p = bp;
-                        bd = d2; border = id; bp = v3(q[v][k][0], q[v][k][1], q[v][k][2]);
-                    } else if (d2 < b2d || (d2 == b2d && id < b2o)) {
-                        sd = fmin(sd, b2d); b2d = d2; b2o = id; b2p = v3(q[v][k][0], q[v][k][1], q[v][k][2]);
-                    } else sd = fmin(sd, d2);
-                }
+            for (int k = 0; k < NCH; ++k) {
+                const double dx = q[v][k][0] - s.x, dy = q[v][k][1] - s.y, dz = q[v][k][2] - s.z;
+                cd[NCH * v + k] = Top2Cand{v3(q[v][k][0], q[v][k][1], q[v][k][2]), dx * dx + dy * dy + dz * dz, (unsigned)(vx[v] * 32 + LP * k + laneL), act[v][k]};
+            }
+        st = top2_update(st, cd);
     } else {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -1833,21 +1830,15 @@ __device__ __forceinline__ void scan_voxelsL(const CT& c, const int (&pb)[NV], c
             const double* X = blk_x(c, pb[v] & BLK_ID_MASK);
             for (int base = 0; __any(base < cnt); base += LP) {
                 const int idx = base + laneL;
-                if (idx < cnt) {
-                    const double qx = X[3 * idx], qy = X[3 * idx + 1], qz = X[3 * idx + 2];
-                    const double dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
-                    const double d2 = dx * dx + dy * dy + dz * dz;
-                    const unsigned id = (unsigned)(vx[v] * 32 + idx);
-                    if (d2 < bd || (d2 == bd && id < border)) {
-                        sd = fmin(sd, b2d); b2d = bd; b2o = border; b2p = bp;
-                        bd = d2; border = id; bp = v3(qx, qy, qz);
-                    } else if (d2 < b2d || (d2 == b2d && id < b2o)) {
-                        sd = fmin(sd, b2d); b2d = d2; b2o = id; b2p = v3(qx, qy, qz);
-                    } else sd = fmin(sd, d2);
-                }
+                const bool a = idx < cnt;
+                const double qx = a ? X[3 * idx] : 0.0, qy = a ? X[3 * idx + 1] : 0.0, qz = a ? X[3 * idx + 2] : 0.0;
+                const double dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
+                const Top2Cand cd[1] = {Top2Cand{v3(qx, qy, qz), dx * dx + dy * dy + dz * dz, (unsigned)(vx[v] * 32 + idx), a}};
+                st = top2_update(st, cd);
             }
         }
     }
+    bd = st.bd; b2d = st.b2d; sd = st.sd; border = st.border; b2o = st.b2o; bp = st.bp; b2p = st.b2p;
 }
 // The full 27-voxel search of source point i at s by a group of LP lanes (all of them call it): probe row (rebuild, uniform
 // over the group: the point changed voxel since its last search, or this is a scan's first iteration - phase A of gn8_body
