@@ -1020,6 +1020,91 @@ int ptl_paint_add_posed_xyz(ptl_paint *p, ptl_traj *t, const float *xyz, const u
 int ptl_paint_read(ptl_paint *p, ptl_paint_result *result, double *xyz_out, uint64_t *sum_out, uint32_t *count_out, int64_t max_points,
                    int64_t *n_written);
 
+/* ------------------------------------------------------------------------------------------------
+ * The occupancy grid of a run: free, occupied and unknown cells of a top-down 2-D grid (no reference counterpart).  A pass over
+ * the sweeps of a run, posed by its trajectory: for every CELL it counts the rays that crossed the cell on their way (free) and the rays that
+ * ended in it (hit).  No map handle is involved.  All outputs are integers; sums of integers have no order, so free and hit are an exact
+ * function of the SET of rays and the parameters - the lane mapping, the launch geometry and the order of the sweeps do not change them.  All
+ * arithmetic fp64 in the written order, without contraction.
+ * Parameters: cell > 0; x0, y0 the world coordinates of the corner of cell (0, 0); nx, ny >= 1 with nx ny <= 2^26; z_lo <= z_hi, the height
+ * band RELATIVE TO THE RAY'S OWN ORIGIN; margin >= 0; 0 < step <= cell; min_range >= 0; max_range > min_range, max_range / step <= 65536.
+ * ptl_grid_default_cfg fills step = cell / 2, margin = cell, min_range = 0, max_range = 600 cell, band [-0.5, +0.5] m; the bounds (x0, y0, nx,
+ * ny) and the staging sizes have no default.  The defaults are a caller's choice that the result echoes back, NOT tuned values: nobody has run
+ * this on a real recording.
+ * Ray: ptl_carve's ray.  A pixel with a return; its end w is the world point the posed-scan pass gives it (ptl_icp_map_add_posed_*), its origin
+ * o the translation of its own column's pose; d = w - o, len2 = (dx dx + dy dy) + dz dz, len = sqrt(len2).  The ray is used iff
+ * min_range <= len <= max_range, otherwise it is counted in n_rays_out_of_range; a pixel without a return is counted in n_no_return.  A sweep
+ * with any column outside the trajectory's bounds is skipped as a whole and counted (n_scans_skipped).
+ * Samples: k = 0, 1, ... while t_k = ((double)k + 0.5) step < len: a_k = t_k / len, s_k[c] = o[c] + a_k d[c].  A sample is a FREE sample iff
+ * also t_k <= len - margin.
+ * Cell of a point p: fx = (p.x - x0) / cell, fy = (p.y - y0) / cell; p is in the grid iff fx >= 0 && fx < (double)nx && fy >= 0 &&
+ * fy < (double)ny, compared in fp64 before any integer conversion (a NaN fails it); then ix = (int)fx, iy = (int)fy.  p is in the band iff
+ * z_lo <= p.z - o.z && p.z - o.z <= z_hi.
+ * Runs: consecutive free samples with the same cell state - "outside the grid" or the pair (ix, iy) - form a run (run-based, like the carve's
+ * "consecutive samples with one key visit the voxel once"; nothing rests on monotonicity).
+ * Votes of one used ray: if w is in the grid and in the band, hit[cell(w)] += 1.  Every run whose cell is in the grid and which has at least one
+ * sample in the band gives free[cell] += 1 - except the LAST run when its cell equals cell(w) and the ray scored a hit there.  A ray adds at
+ * most 1 to any counter of a cell per run.
+ * The counters are u32.  The handle keeps the number of used rays so far; an add that could carry it past 2^32 - 1 (every pixel of the add
+ * taken as a used ray) is refused before any HIP call with PTL_ERR_CAPACITY and the numbers: no counter can wrap.
+ * Which cells count as occupied is the caller's policy on the two counts (the Python layer's GridCounts.classify), not the library's. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_grid_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double cell, x0, y0;
+    double z_lo, z_hi, margin, step, min_range, max_range;
+    int64_t max_pixels_per_scan; /* sizes the handle's sweep staging for the per-call adds: scan_cols .. 2^24 */
+    int32_t nx, ny;
+    int32_t scan_cols;           /* W of every sweep: sizes the handle's column table */
+} ptl_grid_cfg;
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_grid_result) as the caller knows it (PTL_CFG_INIT): ptl_grid_read refuses another size or version */
+    uint32_t abi_version;
+    int64_t n_scans, n_scans_skipped;                  /* sweeps used / skipped as outside the trajectory's bounds */
+    int64_t n_rays, n_rays_out_of_range, n_no_return;  /* pixels of the used sweeps: used rays, returns outside [min_range, max_range], no return */
+    int64_t n_runs_voted;                              /* free votes over all rays (= sum_free) */
+    int64_t n_ends_outside;                            /* used rays whose end lies outside the grid */
+    int64_t n_cells_free, n_cells_hit;                 /* cells with a non-zero count */
+    int64_t sum_free, sum_hit;
+    int32_t box_ix0, box_iy0, box_ix1, box_iy1;        /* the touched box: min and max ix, iy (inclusive) over the cells with any count; an empty
+                                                          box is (0, 0, -1, -1) */
+    double cell, x0, y0, z_lo, z_hi, margin, step, min_range, max_range; /* the parameters as used */
+    int32_t nx, ny;
+    double device_ms;                                  /* HIP-event time of the handle's device work so far: sweeps, the reads' reductions */
+} ptl_grid_result;
+typedef struct ptl_grid ptl_grid; /* the counts of one grid: its own stream, column table, sweep staging, count arrays and counters */
+/* the library's sizeof(ptl_grid_cfg) / sizeof(ptl_grid_result) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_grid_sizeof_cfg(void);
+int64_t ptl_grid_sizeof_result(void);
+/* the defaults above for that cell size, everything else zero; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a
+ * mismatch is refused with PTL_ERR_ARG and nothing is written */
+int ptl_grid_default_cfg(ptl_grid_cfg *cfg, double cell);
+/* a grid of nx x ny cells on that device, all counts zero.  Checked before any HIP call, refused with the numbers (PTL_ERR_ARG): null cfg / out,
+ * a cfg of another size or version, each parameter bound above, scan_cols < 1, max_pixels_per_scan outside scan_cols .. 2^24. */
+int ptl_grid_create(int32_t device_id, const ptl_grid_cfg *cfg, ptl_grid **out);
+int ptl_grid_destroy(ptl_grid *g);
+/* one posed sweep, with the arguments of ptl_carve_add_posed_range / _xyz: *n_valid = the sweep's used rays (nullable), *skipped = 1 when a
+ * column lay outside the bounds and nothing was counted but the sweep (nullable).  Trajectory, LUT and grid on one device (else PTL_ERR_ARG with
+ * the ids); W = the handle's scan_cols and H W <= its max_pixels_per_scan, used rays so far + H W <= 2^32 - 1 (else PTL_ERR_CAPACITY with the
+ * numbers) - all before any HIP call. */
+int ptl_grid_add_posed_range(ptl_grid *g, ptl_traj *t, ptl_lut *lut, const uint32_t *range_mm, const double *col_ts, int64_t *n_valid,
+                             int32_t *skipped);
+int ptl_grid_add_posed_xyz(ptl_grid *g, ptl_traj *t, const float *xyz, int32_t H, int32_t W, const double *col_ts, int64_t *n_valid,
+                           int32_t *skipped);
+/* the RESIDENT sweeps [first, last] of a runner, no sweep crosses the bus; arguments, column times and state errors as ptl_carve_add_seq /
+ * ptl_carve_add_batch.  *n_valid = used rays, *n_skipped = sweeps skipped (both nullable) */
+int ptl_grid_add_seq(ptl_grid *g, ptl_seq *s, ptl_traj *t, const double *t0t1, int64_t first, int64_t last, int64_t *n_valid,
+                     int64_t *n_skipped);
+int ptl_grid_add_batch(ptl_grid *g, ptl_batch *b, int32_t seq, ptl_traj *t, const double *t0t1, int64_t first, int64_t last,
+                       int64_t *n_valid, int64_t *n_skipped);
+/* the summary so far, and (both arrays given, or neither) the counts of the rectangle of w x h cells at (ix0, iy0), row-major [h][w] with ix
+ * contiguous.  result->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is refused with PTL_ERR_ARG and
+ * nothing is written.  With the arrays, a rectangle that is empty or not inside the grid is PTL_ERR_ARG with the numbers; without them the
+ * rectangle is not looked at.  The counts stay: sweeps may be added and read again. */
+int ptl_grid_read(ptl_grid *g, ptl_grid_result *result, int32_t ix0, int32_t iy0, int32_t w, int32_t h, uint32_t *free_out, uint32_t *hit_out);
+/* all counts and counters back to zero (the used rays too); the parameters stay */
+int ptl_grid_clear(ptl_grid *g);
+
 #ifdef __cplusplus
 }
 #endif

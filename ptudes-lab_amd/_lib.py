@@ -143,6 +143,24 @@ class PaintResult(_Cfg):
                 ("n_no_return", C.c_int64), ("sum_count", C.c_int64), ("device_ms", C.c_double)]
 
 
+class GridCfg(_Cfg):
+    """ptl_grid_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("cell", C.c_double), ("x0", C.c_double), ("y0", C.c_double),
+                ("z_lo", C.c_double), ("z_hi", C.c_double), ("margin", C.c_double), ("step", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double), ("max_pixels_per_scan", C.c_int64), ("nx", C.c_int32), ("ny", C.c_int32), ("scan_cols", C.c_int32)]
+
+
+class GridResult(_Cfg):
+    """ptl_grid_result (include/ptudes_mi.h): an output that carries the caller's {struct_size, abi_version} in front"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("n_scans", C.c_int64), ("n_scans_skipped", C.c_int64),
+                ("n_rays", C.c_int64), ("n_rays_out_of_range", C.c_int64), ("n_no_return", C.c_int64), ("n_runs_voted", C.c_int64),
+                ("n_ends_outside", C.c_int64), ("n_cells_free", C.c_int64), ("n_cells_hit", C.c_int64), ("sum_free", C.c_int64),
+                ("sum_hit", C.c_int64), ("box_ix0", C.c_int32), ("box_iy0", C.c_int32), ("box_ix1", C.c_int32), ("box_iy1", C.c_int32),
+                ("cell", C.c_double), ("x0", C.c_double), ("y0", C.c_double), ("z_lo", C.c_double), ("z_hi", C.c_double), ("margin", C.c_double),
+                ("step", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("device_ms", C.c_double)]
+
+
 class PoseSearchCfg(_Cfg):
     """ptl_pose_search_cfg (include/ptudes_mi.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
@@ -331,6 +349,19 @@ PROTOTYPES = {
     "ptl_paint_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int32, C.c_int32, c_d_p, c_i64_p,
                                           C.POINTER(C.c_int32)]),
     "ptl_paint_read": (C.c_int, [_vp, C.POINTER(PaintResult), c_d_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int64, c_i64_p]),
+    # the occupancy grid of a run: free / hit counts per cell (include/ptudes_mi.h)
+    "ptl_grid_sizeof_cfg": (C.c_int64, []),
+    "ptl_grid_sizeof_result": (C.c_int64, []),
+    "ptl_grid_default_cfg": (C.c_int, [C.POINTER(GridCfg), C.c_double]),
+    "ptl_grid_create": (C.c_int, [C.c_int32, C.POINTER(GridCfg), _vpp]),
+    "ptl_grid_destroy": (C.c_int, [_vp]),
+    "ptl_grid_add_posed_range": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32), c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_grid_add_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, c_i64_p, C.POINTER(C.c_int32)]),
+    "ptl_grid_add_seq": (C.c_int, [_vp, _vp, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    "ptl_grid_add_batch": (C.c_int, [_vp, _vp, C.c_int32, _vp, c_d_p, C.c_int64, C.c_int64, c_i64_p, c_i64_p]),
+    "ptl_grid_read": (C.c_int, [_vp, C.POINTER(GridResult), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32),
+                                C.POINTER(C.c_uint32)]),
+    "ptl_grid_clear": (C.c_int, [_vp]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

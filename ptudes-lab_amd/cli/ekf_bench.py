@@ -473,6 +473,140 @@ def carve_report(map_icp, votes, carve):
     return clean
 
 
+GRID_OPTIONS = [
+    click.option("--save-grid", required=False, type=click.Path(dir_okay=False),
+                 help="after the trajectory is known, pass over the same sweeps and write the top-down occupancy grid of the run (GPU): "
+                      "PREFIX.pgm (254 free, 0 occupied, 205 unknown) with PREFIX.yaml beside it, as ROS map_server reads them; a PREFIX "
+                      "ending in .png writes that PNG instead of the .pgm"),
+    click.option("--grid-cell", type=float, default=None, help="cell size of --save-grid, metres (default 0.25)"),
+    click.option("--grid-band", type=str, default=None,
+                 help="heights LO,HI relative to the sensor between which a ray counts for --save-grid, metres (default -0.5,0.5; untuned)"),
+    click.option("--grid-margin", type=float, default=None,
+                 help="a ray proves free space up to this distance before its end, metres (default: the cell size; untuned)"),
+    click.option("--grid-max-range", type=float, default=None, help="longest ray used, metres (default: 600 cells; untuned)"),
+    click.option("--grid-bounds", type=str, default=None,
+                 help="X0,Y0,X1,Y1 of the grid in the trajectory's frame, metres (default: the trajectory's positions padded by --grid-max-range)"),
+    click.option("--grid-min-hits", type=int, default=None, help="policy: rays that ended in a cell before it can count as occupied (default 2; untuned)"),
+    click.option("--grid-min-fraction", type=float, default=None,
+                 help="policy: share of hits among the rays that met the cell, hit / (hit + free) (default 0.25; untuned)"),
+    click.option("--save-grid-counts", required=False, type=click.Path(dir_okay=False),
+                 help="also write the counts of the touched box to this .npz: free, hit, classes (0 free, 1 occupied, 2 unknown), cell, origin"),
+]
+GRID_CELL = 0.25
+
+
+def grid_click_options(f):
+    for opt in reversed(GRID_OPTIONS):
+        f = opt(f)
+    return f
+
+
+def _numbers(name, text, n, what):
+    try:
+        vals = [float(x) for x in text.split(",")]
+    except ValueError:
+        vals = []
+    if len(vals) != n or not all(np.isfinite(vals)):
+        raise click.ClickException(f"{name} {text}: expected {what}")
+    return vals
+
+
+def grid_options(save_grid, grid_cell, grid_band, grid_margin, grid_max_range, grid_bounds, grid_min_hits, grid_min_fraction, save_grid_counts,
+                 kitti_poses=None):
+    """the options of --save-grid checked before any device is touched: None without it, else a dict with the policy's defaults filled in"""
+    given = {"--grid-cell": grid_cell, "--grid-band": grid_band, "--grid-margin": grid_margin, "--grid-max-range": grid_max_range,
+             "--grid-bounds": grid_bounds, "--grid-min-hits": grid_min_hits, "--grid-min-fraction": grid_min_fraction,
+             "--save-grid-counts": save_grid_counts}
+    if not save_grid:
+        for name, v in given.items():
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --save-grid")
+        return None
+    if kitti_poses:
+        raise click.ClickException("--save-grid with --kitti-poses: the grid needs the column poses of --nc-gt-poses")
+    cell = GRID_CELL if grid_cell is None else grid_cell
+    if not (cell > 0.0 and np.isfinite(cell)):
+        raise click.ClickException(f"--grid-cell {cell:g}: must be positive")
+    z_lo = z_hi = None
+    if grid_band is not None:
+        z_lo, z_hi = _numbers("--grid-band", grid_band, 2, "LO,HI")
+        if not z_lo <= z_hi:
+            raise click.ClickException(f"--grid-band {grid_band}: LO must not be above HI")
+    if grid_margin is not None and not grid_margin >= 0.0:
+        raise click.ClickException(f"--grid-margin {grid_margin:g}: must not be negative")
+    if grid_max_range is not None and not 0.0 < grid_max_range <= 32768.0 * cell:
+        raise click.ClickException(f"--grid-max-range {grid_max_range:g}: must be in (0, {32768.0 * cell:g}] (65536 steps of half a cell)")
+    bounds = None
+    if grid_bounds is not None:
+        bounds = tuple(_numbers("--grid-bounds", grid_bounds, 4, "X0,Y0,X1,Y1"))
+        if not (bounds[2] > bounds[0] and bounds[3] > bounds[1]):
+            raise click.ClickException(f"--grid-bounds {grid_bounds}: X1 must be above X0 and Y1 above Y0")
+        nx, ny = int(np.ceil((bounds[2] - bounds[0]) / cell)), int(np.ceil((bounds[3] - bounds[1]) / cell))
+        if nx * ny > 1 << 26:
+            raise click.ClickException(f"--grid-bounds {grid_bounds}: {nx} x {ny} = {nx * ny} cells of {cell:g} m, the limit is {1 << 26} (2^26)")
+    if grid_min_hits is not None and grid_min_hits < 0:
+        raise click.ClickException(f"--grid-min-hits {grid_min_hits}: must not be negative")
+    if grid_min_fraction is not None and not 0.0 <= grid_min_fraction <= 1.0:
+        raise click.ClickException(f"--grid-min-fraction {grid_min_fraction:g}: must be in [0, 1]")
+    if save_grid_counts and not str(save_grid_counts).endswith(".npz"):
+        raise click.ClickException(f"--save-grid-counts {save_grid_counts}: the counts are written to a .npz file")
+    return dict(prefix=save_grid, cell=cell, bounds=bounds, cfg=dict(z_lo=z_lo, z_hi=z_hi, margin=grid_margin, max_range=grid_max_range),
+                min_hits=2 if grid_min_hits is None else grid_min_hits,
+                min_fraction=0.25 if grid_min_fraction is None else grid_min_fraction, counts=save_grid_counts)
+
+
+def grid_builder(lut, knots, grid):
+    """the fly.GridBuilder of --save-grid (`grid_options`): --grid-bounds, else the positions of `knots` [(ts, pose)] padded by the longest ray;
+    a grid too large is refused with its cell count"""
+    from .. import fly
+    try:
+        return fly.GridBuilder(lut, grid["bounds"] if grid["bounds"] is not None else list(knots), grid["cell"], **grid["cfg"])
+    except ValueError as e:
+        raise click.ClickException(f"--save-grid: {e}")
+
+
+def grid_report(counts, grid):
+    """--save-grid: prints the counts' block and writes the files"""
+    from ..utils import save_occupancy_map
+    print("\n".join(counts.lines(grid["min_hits"], grid["min_fraction"])))
+    classes = counts.classify(grid["min_hits"], grid["min_fraction"])
+    image, yaml = save_occupancy_map(grid["prefix"], classes, counts.cell, counts.origin)
+    print(f"Occupancy grid saved to: {image}, {yaml}")
+    if grid["counts"]:
+        np.savez(grid["counts"], free=counts.free, hit=counts.hit, classes=classes, cell=counts.cell, origin=np.asarray(counts.origin))
+        print(f"Grid counts saved to: {grid['counts']}")
+
+
+def _run_grid(seq, first, knots, grid, device_id=0):
+    """--save-grid of a synthetic sequence: the sweeps [first, n_scans) are uploaded once and counted where they lie (OccupancyGrid.add_run),
+    every column at its own pose, bounds 1.5 s; returns the core.GridCounts of the touched box"""
+    from .. import core
+    from ..sequence import sweep_times
+    builder = grid_builder((seq.H, seq.W), knots, grid)
+    traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
+    runner = core.SeqRunner(seq.n_scans, seq.H * seq.W, 0, with_ekf=False, device_id=device_id, scan_cols=seq.W)
+    for k in range(first, seq.n_scans):
+        runner.upload_scan(k, seq.scan(k))
+    builder.add_run(runner, traj, sweep_times(seq), first=first)
+    counts = builder.counts()
+    for h in (runner, traj, builder):
+        h.close()
+    return counts
+
+
+def _bag_grid(bags, info, start_scan, end_scan, knots, grid, device_id=0):
+    """... of a raw packet bag: a pass over the bag through the package's packet feed, as `_bag_map` makes it"""
+    from .. import core, fly
+    lut = fly.sensor_lut(info, use_extrinsics=True, device_id=device_id)
+    builder = grid_builder(lut, knots, grid)
+    traj = core.Traj([t for t, _ in knots], [p for _, p in knots], MAP_TIME_BOUNDS, MAP_TIME_BOUNDS, device_id=device_id)
+    fly.grid_packet_bag(builder, bags, info, traj, start_scan, end_scan, device_id=device_id)
+    counts = builder.counts()
+    for h in (traj, builder, lut):
+        h.close()
+    return counts
+
+
 def score_options(map_score, score_radius, voxel_size):
     """the keyword arguments of Icp.map_score for --map-score / --score-radius, or None; refusals before any device is touched"""
     if score_radius is not None and not map_score:
@@ -535,6 +669,7 @@ def score_options(map_score, score_radius, voxel_size):
                                                                "map's voxel size, 0.5)")
 @compare_click_options
 @carve_click_options
+@grid_click_options
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
@@ -545,7 +680,11 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                       compare_pose: Optional[str] = None, save_map_error: Optional[str] = None, carve: bool = False,
                       save_carved: Optional[str] = None, carve_radius: Optional[float] = None, carve_margin: Optional[float] = None,
                       carve_max_range: Optional[float] = None, carve_min_through: Optional[int] = None,
-                      carve_min_fraction: Optional[float] = None, synthetic_size: Optional[str] = None) -> None:
+                      carve_min_fraction: Optional[float] = None, synthetic_size: Optional[str] = None,
+                      save_grid: Optional[str] = None, grid_cell: Optional[float] = None, grid_band: Optional[str] = None,
+                      grid_margin: Optional[float] = None, grid_max_range: Optional[float] = None, grid_bounds: Optional[str] = None,
+                      grid_min_hits: Optional[int] = None, grid_min_fraction: Optional[float] = None,
+                      save_grid_counts: Optional[str] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     if synthetic_size is not None and synthetic is None:
         raise click.ClickException("--synthetic-size belongs to --synthetic")
@@ -558,7 +697,10 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
     want_map = bool(save_map) or map_score or compare is not None
     carving = carve_options(carve, save_carved, carve_radius, carve_margin, carve_max_range, carve_min_through, carve_min_fraction, MAP_VOXEL_SIZE,
                             want_map)
-    if want_map and map_from == "smoothed" and not save_smoothed_poses:
+    gridding = grid_options(save_grid, grid_cell, grid_band, grid_margin, grid_max_range, grid_bounds, grid_min_hits, grid_min_fraction,
+                            save_grid_counts)
+    want_sweeps = want_map or gridding is not None  # (the grid is a product of the same kind: it needs the sweeps' column times)
+    if want_sweeps and map_from == "smoothed" and not save_smoothed_poses:
         raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
         raise click.ClickException("--imu-deskew needs --synthetic and the fused loop (no -p)")
@@ -573,12 +715,12 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             have_sdk = True
         except Exception:
             pass
-    if want_map and synthetic is None:
+    if want_sweeps and synthetic is None:
         from pathlib import Path
         native_bag = bool(file) and (native_packets or not have_sdk) and ((Path(file).is_file() and Path(file).suffix == ".bag") or Path(file).is_dir())
         if not native_bag:
             raise click.ClickException("--save-map needs --synthetic or a raw packet .bag read by the package's own decoder (--native-packets): "
-                                       "the sweep times of other recordings are not decoded here (the same holds for --map-score)")
+                                       "the sweep times of other recordings are not decoded here (the same holds for --map-score and --save-grid)")
     bags = None
     if synthetic is None and (native_packets or not have_sdk):
         # the package's own feed (packets.py): raw payloads from the bag(s), batched on the host, decoded on the device
@@ -714,6 +856,18 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             print("\n".join(ms.lines()))
         if save_map:
             print(f"Map saved to: {save_map}")
+    if gridding is not None:
+        # the occupancy grid of the same sweeps under the same trajectory; it needs no map
+        from ..utils import nc_gt_file_rows
+        rows_t, rows_p = {"filter": (res_t, res_poses), "kiss": (res_t, kiss_poses),
+                          "smoothed": (out.get("smoothed_t"), out.get("smoothed_poses"))}[map_from]
+        if len(rows_t) < 2:
+            raise click.ClickException("the grid needs a trajectory of at least two poses")
+        knots = nc_gt_file_rows(list(rows_t), list(rows_p))
+        if seq is not None:
+            grid_report(_run_grid(seq, start_scan, knots, gridding), gridding)
+        else:
+            grid_report(_bag_grid(bags, info, start_scan, end_scan, knots, gridding), gridding)
     tm = out["timings"]
     if tm["n_imu"] and tm["n_corr"]:  # reference :590-595
         print("\nTimings:")

@@ -15,7 +15,8 @@ second time and takes the points that later rays went through - a moving object'
 compared (both maps' figures are printed); `--save-carved` writes every stored point with its votes.  The frames draw the
 map as accumulated.  `--color-by range|reflectivity|signal|near_ir` paints the map: a second pass over the same sweeps gives every stored point
 the mean of that lidar field over the rays that ended at it; `--save-painted` writes the points with it, and the frames after the map is built
-take its colours.
+take its colours.  `--save-grid PREFIX` passes over the same sweeps once more and writes the top-down occupancy grid of the run -
+free, occupied and unknown cells - as PREFIX.pgm / PREFIX.yaml.
 """
 from typing import Optional
 
@@ -26,6 +27,7 @@ from ..utils import read_newer_college_gt, save_map_ply
 
 from .ekf_bench import carve_click_options as _carve_click_options
 from .ekf_bench import compare_click_options as _compare_click_options
+from .ekf_bench import grid_click_options as _grid_click_options
 
 TIME_BOUNDS = 1.5  # seconds a column may lie outside the poses file (reference utils.py:368)
 
@@ -143,6 +145,7 @@ def paint_options(color_by, color_range, save_painted, synthetic, carve, kitti_p
               help="write every stored point with FIELD (the mean, NaN where no ray ended) and FIELD_count to this PLY file")
 @_compare_click_options
 @_carve_click_options
+@_grid_click_options
 def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional[str], nc_gt_poses: Optional[str], rate: float,
                  accum_map_ratio: Optional[float], start_scan: int, end_scan: Optional[int], voxel_size: float,
                  save_map: Optional[str], synthetic: Optional[int], native_packets: bool = False, map_score: bool = False,
@@ -153,7 +156,10 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
                  save_map_error: Optional[str] = None, carve: bool = False, save_carved: Optional[str] = None,
                  carve_radius: Optional[float] = None, carve_margin: Optional[float] = None, carve_max_range: Optional[float] = None,
                  carve_min_through: Optional[int] = None, carve_min_fraction: Optional[float] = None, color_by: Optional[str] = None,
-                 color_range: Optional[str] = None, save_painted: Optional[str] = None) -> None:
+                 color_range: Optional[str] = None, save_painted: Optional[str] = None, save_grid: Optional[str] = None,
+                 grid_cell: Optional[float] = None, grid_band: Optional[str] = None, grid_margin: Optional[float] = None,
+                 grid_max_range: Optional[float] = None, grid_bounds: Optional[str] = None, grid_min_hits: Optional[int] = None,
+                 grid_min_fraction: Optional[float] = None, save_grid_counts: Optional[str] = None) -> None:
     """Map of the lidar scans with poses (the flyby visualizer's map, headless).
 
     Data is provided via FILE in Ouster raw packets formats (PCAP or BAG with lidar/imu packets), or --synthetic SEED.
@@ -165,6 +171,9 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
     from .ekf_bench import carve_options, carve_report
     carving = carve_options(carve, save_carved, carve_radius, carve_margin, carve_max_range, carve_min_through, carve_min_fraction, voxel_size,
                             bool(save_map) or map_score or compare is not None)
+    from .ekf_bench import grid_builder, grid_options, grid_report
+    gridding = grid_options(save_grid, grid_cell, grid_band, grid_margin, grid_max_range, grid_bounds, grid_min_hits, grid_min_fraction,
+                            save_grid_counts, kitti_poses)
     if kitti_poses:
         raise click.ClickException("--kitti-poses is not supported here: the column timing of one-pose-per-scan files is defined inside "
                                    "ouster-sdk's pose_scans_from_kitti, which this build cannot read; use --nc-gt-poses")
@@ -320,6 +329,18 @@ def ptudes_flyby(file: Optional[str], meta: Optional[str], kitti_poses: Optional
         if painting["save"]:
             save_map_ply(painting["save"], values.xyz, {name: mean, name + "_count": values.count})
             print(f"Painted map saved to: {painting['save']}")
+    if gridding is not None:
+        # the occupancy grid of the same sweeps under the same trajectory: a pass of its own, it needs no map
+        builder = grid_builder(lut, gts_poses[start_scan:end_scan + 1], gridding)
+        try:
+            if native:
+                fly.grid_packet_bag(builder, bags, info, traj, start_scan, end_scan)
+            else:
+                for scan in (scans if isinstance(scans, list) else real_scans()):
+                    builder.update(scan, traj)
+            grid_report(builder.counts(), gridding)
+        finally:
+            builder.close()
     if carving is not None:
         # the second pass over the same sweeps; the frames above drew the map as accumulated
         carver = fly.MapCarver(acc, **carving["cfg"])

@@ -697,6 +697,142 @@ class Painter:
         return PaintValues(xyz[:n].copy(), s[:n].copy(), k[:n].copy(), res)
 
 
+GRID_FREE, GRID_OCCUPIED, GRID_UNKNOWN = 0, 1, 2  # the classes of `grid_classify`
+GRID_MAX_CELLS = 1 << 26
+
+
+def grid_classify(free, hit, min_hits=2, min_fraction=0.25, min_free=1):
+    """HOST POLICY on the two counts of `OccupancyGrid.read()`, not part of the library's definition, and its defaults are UNTUNED (nobody has
+    run this on a real recording): a cell is occupied (GRID_OCCUPIED) iff hit >= min_hits and hit >= min_fraction * (hit + free); else free
+    (GRID_FREE) iff free >= min_free; else unknown (GRID_UNKNOWN).  Returns a uint8 array of the counts' shape"""
+    f, h = np.asarray(free, dtype=np.int64), np.asarray(hit, dtype=np.int64)
+    occ = (h >= int(min_hits)) & (h >= float(min_fraction) * (h + f))
+    out = np.full(f.shape, GRID_UNKNOWN, dtype=np.uint8)
+    out[f >= int(min_free)] = GRID_FREE
+    out[occ] = GRID_OCCUPIED
+    return out
+
+
+@dataclass
+class GridCounts:
+    """What `OccupancyGrid.read()` returns (include/ptudes_mi.h ptl_grid_result): the counts of a rectangle of cells, row-major
+    (h, w) with ix along the columns - free[j, i] is cell (ix0 + i, iy0 + j) -, the cell size, the world coordinates of the rectangle's own
+    corner, and the summary of the WHOLE grid (a `_lib.GridResult`, all counts exact)"""
+    free: np.ndarray       # (h, w) uint32
+    hit: np.ndarray        # (h, w) uint32
+    cell: float
+    origin: tuple          # (x, y) of the corner of free[0, 0]
+    result: object
+
+    def classify(self, min_hits=2, min_fraction=0.25, min_free=1):
+        """`grid_classify` of these counts: host policy with untuned defaults, not the library's"""
+        return grid_classify(self.free, self.hit, min_hits, min_fraction, min_free)
+
+    def lines(self, min_hits=2, min_fraction=0.25, min_free=1):
+        """the block the commands print"""
+        r = self.result
+        cls = self.classify(min_hits, min_fraction, min_free)
+        return [f"grid: {r.nx} x {r.ny} cells of {r.cell:g} m from ({r.x0:g}, {r.y0:g}), band [{r.z_lo:g}, {r.z_hi:g}] m, margin {r.margin:g} m, "
+                f"step {r.step:g} m, range [{r.min_range:g}, {r.max_range:g}] m",
+                f"  sweeps: {r.n_scans} (skipped {r.n_scans_skipped}), rays {r.n_rays} (out of range {r.n_rays_out_of_range}, "
+                f"no return {r.n_no_return}, ends outside the grid {r.n_ends_outside})",
+                f"  cells: crossed {r.n_cells_free}, hit {r.n_cells_hit}, votes free {r.sum_free}, hit {r.sum_hit}, "
+                f"touched box [{r.box_ix0}, {r.box_ix1}] x [{r.box_iy0}, {r.box_iy1}]",
+                f"  classes (hits >= {int(min_hits)}, fraction >= {float(min_fraction):g}, free >= {int(min_free)}; untuned): "
+                f"free {int((cls == GRID_FREE).sum())}, occupied {int((cls == GRID_OCCUPIED).sum())}, unknown {int((cls == GRID_UNKNOWN).sum())} "
+                f"of {cls.size} cells read"]
+
+
+def grid_cfg(cell, x0, y0, nx, ny, scan_cols, max_pixels_per_scan, z_lo=None, z_hi=None, margin=None, step=None, min_range=None, max_range=None):
+    """the _lib.GridCfg of a grid of that cell size: the library's defaults with the bounds, the staging sizes and the given fields on top"""
+    cfg = L.GridCfg()
+    L.check(L.lib().ptl_grid_default_cfg(C.byref(cfg), float(cell)))
+    cfg.x0, cfg.y0, cfg.nx, cfg.ny = float(x0), float(y0), int(nx), int(ny)
+    cfg.scan_cols, cfg.max_pixels_per_scan = int(scan_cols), int(max_pixels_per_scan)
+    for k, v in (("z_lo", z_lo), ("z_hi", z_hi), ("margin", margin), ("step", step), ("min_range", min_range), ("max_range", max_range)):
+        if v is not None:
+            setattr(cfg, k, float(v))
+    return cfg
+
+
+class OccupancyGrid:
+    """The occupancy grid of a run (include/ptudes_mi.h ptl_grid_*): a pass over the sweeps of a run, posed by its trajectory,
+    counts for every cell of a top-down grid the rays that crossed it (free) and the rays that ended in it (hit).  No map is involved.
+    The grid is nx x ny cells of `cell` metres with the corner of cell (0, 0) at (x0, y0); scan_cols and max_pixels_per_scan size the
+    handle's staging (W of every sweep, the largest H W of a per-call sweep)"""
+
+    def __init__(self, cell, x0, y0, nx, ny, scan_cols, max_pixels_per_scan, device_id=0, **cfg):
+        self.cfg = grid_cfg(cell, x0, y0, nx, ny, scan_cols, max_pixels_per_scan, **cfg)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_grid_create(int(device_id), C.byref(self.cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_grid_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_posed(self, traj, col_ts, range_mm=None, lut=None, xyz=None, H=None):
+        """one posed sweep, with the arguments of `Carver.add_posed`.  Returns (n_rays, skipped): the sweep's used rays; a sweep with a
+        column outside the trajectory's bounds is skipped as a whole"""
+        t = L.as_f64(col_ts).reshape(-1)
+        nv, sk = C.c_int64(), C.c_int32()
+        if (range_mm is None) == (xyz is None):
+            raise ValueError("give range_mm (with lut) or xyz")
+        if range_mm is not None:
+            if lut is None:
+                raise ValueError("a range image needs its lut")
+            r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+            if r.size != lut.H * lut.W or len(t) != lut.W:
+                raise ValueError("need an H x W range image and one time per column")
+            L.check(L.lib().ptl_grid_add_posed_range(self._h, traj._h, lut._h, r.ctypes.data_as(C.POINTER(C.c_uint32)), L.dptr(t),
+                                                     C.byref(nv), C.byref(sk)))
+        else:
+            x = np.ascontiguousarray(xyz, dtype=np.float32)
+            W = len(t)
+            H = int(H) if H is not None else x.size // (3 * max(W, 1))
+            if x.size != H * W * 3:
+                raise ValueError("need H x W x 3 points and one time per column")
+            L.check(L.lib().ptl_grid_add_posed_xyz(self._h, traj._h, x.ctypes.data_as(C.POINTER(C.c_float)), H, W, L.dptr(t),
+                                                   C.byref(nv), C.byref(sk)))
+        return nv.value, bool(sk.value)
+
+    def add_run(self, runner, traj, t0t1, s=None, first=0, last=None):
+        """the RESIDENT sweeps [first, last] of a SeqRunner (s=None) or of sequence s of a BatchRunner, as `build_map` takes them: no sweep
+        crosses the bus.  Returns (n_rays, n_skipped)"""
+        t = _sweep_times(t0t1, runner.n_scans)
+        last = runner.n_scans - 1 if last is None else int(last)
+        nv, ns = C.c_int64(), C.c_int64()
+        if s is None:
+            L.check(L.lib().ptl_grid_add_seq(self._h, runner._h, traj._h, L.dptr(t), int(first), last, C.byref(nv), C.byref(ns)))
+        else:
+            L.check(L.lib().ptl_grid_add_batch(self._h, runner._h, int(s), traj._h, L.dptr(t), int(first), last, C.byref(nv), C.byref(ns)))
+        return nv.value, ns.value
+
+    def summary(self):
+        """the `_lib.GridResult` of the sweeps added so far, without any cell"""
+        res = L.GridResult()
+        L.check(L.lib().ptl_grid_read(self._h, C.byref(res), 0, 0, 0, 0, None, None))
+        return res
+
+    def read(self, ix0=0, iy0=0, w=None, h=None):
+        """a `GridCounts` of the rectangle of w x h cells at (ix0, iy0) (default: the whole grid) for the sweeps added so far; more may be
+        added and read again"""
+        w = self.cfg.nx - int(ix0) if w is None else int(w)
+        h = self.cfg.ny - int(iy0) if h is None else int(h)
+        shape = (h, w) if h >= 1 and w >= 1 else (1, 1)  # (an empty rectangle still reaches the library, which refuses it with the numbers)
+        free, hit = np.zeros(shape, dtype=np.uint32), np.zeros(shape, dtype=np.uint32)
+        res = L.GridResult()
+        u32p = C.POINTER(C.c_uint32)
+        L.check(L.lib().ptl_grid_read(self._h, C.byref(res), int(ix0), int(iy0), w, h, free.ctypes.data_as(u32p), hit.ctypes.data_as(u32p)))
+        return GridCounts(free, hit, float(res.cell), (res.x0 + int(ix0) * res.cell, res.y0 + int(iy0) * res.cell), res)
+
+    def clear(self):
+        """all counts and counters back to zero; the parameters stay"""
+        L.check(L.lib().ptl_grid_clear(self._h))
+
+
 def rgba_word(rgba):
     """(..., 4) uint8 R, G, B, A -> the uint32 words the renderer's keys carry (R the lowest byte)"""
     a = np.ascontiguousarray(rgba, dtype=np.uint8)

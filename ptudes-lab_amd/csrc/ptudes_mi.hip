@@ -13,6 +13,7 @@
 #include "render_kernels.h"
 #include "compare_kernels.h"
 #include "carve_kernels.h"
+#include "grid_kernels.h"
 #include "paint_kernels.h"
 #include "pose_kernels.h"
 #include "hip_own.h"
@@ -3812,6 +3813,260 @@ extern "C" int ptl_paint_read(ptl_paint* h, ptl_paint_result* result, double* xy
         HIPCHK(hipMemcpy(count_out, h->d_count, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     if (given && n_written) *n_written = n;
+    return PTL_OK;
+}
+
+// ================================================================================================ occupancy grid
+// The definition is in include/ptudes_mi.h, the kernels in grid_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// grid handle owns what its passes need - stream, events, column table, sweep staging, both count arrays, counters - and knows no map.
+struct ptl_grid {
+    int device_id = 0;             // (first member, as in ptl_traj)
+    uint64_t n_rays_used = 0;      // used rays so far, the host's copy after the last add (second member: a test reaches it as it reaches device_id)
+    ptl_grid_cfg cfg;
+    int64_t n_cells = 0;
+    double device_ms = 0;
+    Stream stream;
+    Event e0, e1;
+    double* coltab = nullptr;      // [12][W]
+    double* d_ts = nullptr;        // [W]
+    void* d_raw = nullptr;         // one sweep of the caller's: max_pixels_per_scan pixels of f32 xyz or u32 ranges
+    FlyWs* d_fly = nullptr;        // k_fly_coltab's flag
+    unsigned *d_free = nullptr, *d_hit = nullptr;  // [ny][nx]
+    unsigned long long* d_counts = nullptr;        // [GRID_COUNTERS] + GRID_SUMS of the read's reduction
+    int* d_box = nullptr;          // [4] of the read's reduction
+    unsigned long long counts[GRID_COUNTERS] = {};  // the host's copy after the last add
+    DevOwner mem;
+};
+#define GRID_MAX_RAYS 0xffffffffull
+#define GRID_MAX_PIXELS ((int64_t)1 << 24)
+extern "C" int64_t ptl_grid_sizeof_cfg(void) { return (int64_t)sizeof(ptl_grid_cfg); }
+extern "C" int64_t ptl_grid_sizeof_result(void) { return (int64_t)sizeof(ptl_grid_result); }
+extern "C" int ptl_grid_default_cfg(ptl_grid_cfg* cfg, double cell) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "ptl_grid_default_cfg: cfg is null");
+    ABI_CHECK(ptl_grid_cfg, cfg);
+    if (!(cell > 0.0) || !(cell < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_grid_default_cfg: cell must be positive and finite (got %g)", cell);
+    PTL_CFG_INIT(cfg);
+    cfg->cell = cell; cfg->step = cell / 2.0; cfg->margin = cell; cfg->min_range = 0.0; cfg->max_range = 600.0 * cell;
+    cfg->z_lo = -0.5; cfg->z_hi = 0.5;
+    return PTL_OK;
+}
+static int grid_clock(ptl_grid* h) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    h->device_ms += ms;
+    return PTL_OK;
+}
+static int grid_zero(ptl_grid* h) {
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), s));
+    HIPCHK(hipMemsetAsync(h->d_free, 0, (size_t)h->n_cells * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_hit, 0, (size_t)h->n_cells * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_counts, 0, ((size_t)GRID_COUNTERS + GRID_SUMS) * 8, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memset(h->counts, 0, sizeof h->counts);
+    h->n_rays_used = 0;
+    return PTL_OK;
+}
+extern "C" int ptl_grid_create(int32_t device_id, const ptl_grid_cfg* cfg, ptl_grid** out) {
+    if (!cfg || !out) return set_err(PTL_ERR_ARG, "ptl_grid_create: null argument");
+    ABI_CHECK(ptl_grid_cfg, cfg);
+    const ptl_grid_cfg& u = *cfg;
+    if (!(u.cell > 0.0) || !(u.cell < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_grid_create: cell = %g: must be positive and finite", u.cell);
+    if (!(fabs(u.x0) < 1.0e150) || !(fabs(u.y0) < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_grid_create: origin (x0, y0) = (%g, %g): must be finite", u.x0, u.y0);
+    if (u.nx < 1 || u.ny < 1) return set_err(PTL_ERR_ARG, "ptl_grid_create: nx x ny = %d x %d: both must be >= 1", u.nx, u.ny);
+    if ((int64_t)u.nx * u.ny > (int64_t)GRID_MAX_CELLS)
+        return set_err(PTL_ERR_ARG, "ptl_grid_create: nx x ny = %d x %d = %lld cells: the limit is %d (2^26)", u.nx, u.ny, (long long)((int64_t)u.nx * u.ny), GRID_MAX_CELLS);
+    if (!(u.z_lo <= u.z_hi)) return set_err(PTL_ERR_ARG, "ptl_grid_create: band [z_lo, z_hi] = [%g, %g]: z_lo must not be above z_hi", u.z_lo, u.z_hi);
+    if (!(u.margin >= 0.0) || !(u.margin < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_grid_create: margin = %g: must be >= 0 and finite", u.margin);
+    if (!(u.step > 0.0) || !(u.step <= u.cell)) return set_err(PTL_ERR_ARG, "ptl_grid_create: step = %g: the march needs 0 < step <= cell = %g", u.step, u.cell);
+    if (!(u.min_range >= 0.0)) return set_err(PTL_ERR_ARG, "ptl_grid_create: min_range = %g: must be >= 0", u.min_range);
+    if (!(u.max_range > u.min_range)) return set_err(PTL_ERR_ARG, "ptl_grid_create: max_range = %g: must be above min_range = %g", u.max_range, u.min_range);
+    if (!(u.max_range / u.step <= (double)GRID_MAX_SAMPLES))
+        return set_err(PTL_ERR_ARG, "ptl_grid_create: max_range / step = %g / %g = %g samples per ray: the limit is %d", u.max_range, u.step,
+                       u.max_range / u.step, GRID_MAX_SAMPLES);
+    if (u.scan_cols < 1) return set_err(PTL_ERR_ARG, "ptl_grid_create: scan_cols = %d: must be >= 1", u.scan_cols);
+    if (u.max_pixels_per_scan < u.scan_cols || u.max_pixels_per_scan > GRID_MAX_PIXELS)
+        return set_err(PTL_ERR_ARG, "ptl_grid_create: max_pixels_per_scan = %lld: must be in scan_cols = %d .. %lld", (long long)u.max_pixels_per_scan, u.scan_cols,
+                       (long long)GRID_MAX_PIXELS);
+    if (device_id < 0) return set_err(PTL_ERR_ARG, "ptl_grid_create: device_id = %d: must not be negative", device_id);
+    if (ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    std::unique_ptr<ptl_grid> h(new ptl_grid());
+    h->device_id = device_id; h->cfg = u; h->n_cells = (int64_t)u.nx * u.ny;
+    HIPCHK(h->stream.create());
+    HIPCHK(h->e0.create(hipEventDefault)); HIPCHK(h->e1.create(hipEventDefault));
+    h->mem.add(&h->coltab, (size_t)12 * u.scan_cols); h->mem.add(&h->d_ts, (size_t)u.scan_cols);
+    { unsigned char* raw = nullptr; h->mem.add(&raw, (size_t)u.max_pixels_per_scan * 12); h->d_raw = raw; }
+    h->mem.add(&h->d_fly, 1);
+    h->mem.add(&h->d_free, (size_t)h->n_cells); h->mem.add(&h->d_hit, (size_t)h->n_cells);
+    h->mem.add(&h->d_counts, (size_t)GRID_COUNTERS + GRID_SUMS); h->mem.add(&h->d_box, 4);
+    HIPCHK(h->mem.err);
+    { int rc = grid_zero(h.get()); if (rc) return rc; }
+    *out = h.release();
+    return PTL_OK;
+}
+extern "C" int ptl_grid_destroy(ptl_grid* g) { return g ? handle_destroy(g, g->device_id) : PTL_OK; }
+extern "C" int ptl_grid_clear(ptl_grid* g) {
+    if (!g) return set_err(PTL_ERR_ARG, "ptl_grid_clear: null argument");
+    HIPCHK(hipSetDevice(g->device_id));
+    return grid_zero(g);
+}
+// what every add checks before any HIP call; pixels = every pixel the add could turn into a used ray
+static int grid_check(ptl_grid* h, const ptl_traj* t, const ptl_lut* lut, int64_t H, int64_t W, int64_t sweeps, bool staged, const char* who) {
+    if (t->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: trajectory on device %d, grid on device %d", who, t->device_id, h->device_id);
+    if (lut && lut->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: LUT on device %d, grid on device %d", who, lut->device_id, h->device_id);
+    if (H < 1 || W < 1) return set_err(PTL_ERR_ARG, "%s: empty scan (%lld x %lld)", who, (long long)H, (long long)W);
+    if (W != h->cfg.scan_cols) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld columns, the grid handle's scan_cols is %d", who, (long long)W, h->cfg.scan_cols);
+    if (H * W > (staged ? h->cfg.max_pixels_per_scan : (int64_t)0x7fffffff))
+        return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the grid handle's max_pixels_per_scan is %lld", who, (long long)(H * W),
+                       (long long)h->cfg.max_pixels_per_scan);
+    const uint64_t pixels = (uint64_t)(H * W) * (uint64_t)sweeps;
+    if (h->n_rays_used + pixels > GRID_MAX_RAYS)
+        return set_err(PTL_ERR_CAPACITY, "%s: %llu used rays so far + %llu pixels could pass %llu (2^32 - 1), the range of the u32 counts: read the grid and "
+                       "ptl_grid_clear it, or use another handle", who, (unsigned long long)h->n_rays_used, (unsigned long long)pixels, (unsigned long long)GRID_MAX_RAYS);
+    return PTL_OK;
+}
+// one sweep enqueued on the grid handle's stream; raw (device): the sweep; d_col_ts (device, W) or the sweep's (t0, t1)
+static int grid_enqueue(ptl_grid* h, const ptl_traj* t, const void* raw, bool is_range, const ptl_lut* lut, int H, int W, const double* d_col_ts,
+                        double t0, double t1) {
+    hipStream_t s = h->stream;
+    const int n = H * W;
+    const ptl_grid_cfg& u = h->cfg;
+    GridArgs a = {};
+    a.cell = u.cell; a.x0 = u.x0; a.y0 = u.y0; a.z_lo = u.z_lo; a.z_hi = u.z_hi; a.margin = u.margin; a.step = u.step;
+    a.min_range = u.min_range; a.max_range = u.max_range; a.nx = u.nx; a.ny = u.ny;
+    a.free = h->d_free; a.hit = h->d_hit; a.counts = h->d_counts;
+    const int wg = (n + GRID_THREADS - 1) / GRID_THREADS, grid = wg < GRID_MAX_BLOCKS ? wg : GRID_MAX_BLOCKS;
+    k_fly_coltab<<<1, 256, 0, s>>>(t->d_kt, t->d_kp, t->n, t->before, t->after, d_col_ts, t0, t1, W, h->coltab, h->d_fly);
+    if (is_range) k_grid_rays<true><<<grid, GRID_THREADS, 0, s>>>(raw, lut->dir, lut->off, n, W, h->coltab, h->d_fly, a);
+    else k_grid_rays<false><<<grid, GRID_THREADS, 0, s>>>(raw, nullptr, nullptr, n, W, h->coltab, h->d_fly, a);
+    HIPCHK(hipGetLastError());
+    return PTL_OK;
+}
+// closes an add: the counters come back, the host's copy moves on; the deltas are the call's
+static int grid_finish(ptl_grid* h, int64_t* n_valid, int64_t* n_skipped) {
+    unsigned long long now[GRID_COUNTERS];
+    HIPCHK(hipEventRecord(h->e1, h->stream));
+    HIPCHK(hipMemcpyAsync(now, h->d_counts, sizeof now, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    { int rc = grid_clock(h); if (rc) return rc; }
+    if (n_valid) *n_valid = (int64_t)(now[GRID_N_RAYS] - h->counts[GRID_N_RAYS]);
+    if (n_skipped) *n_skipped = (int64_t)(now[GRID_N_SKIPPED] - h->counts[GRID_N_SKIPPED]);
+    memcpy(h->counts, now, sizeof now);
+    h->n_rays_used = now[GRID_N_RAYS];
+    return PTL_OK;
+}
+static int grid_add_percall(ptl_grid* h, ptl_traj* t, ptl_lut* lut, const void* raw_host, size_t raw_bytes, bool is_range, int64_t H, int64_t W,
+                            const double* col_ts, int64_t* n_valid, int32_t* skipped, const char* who) {
+    int rc = grid_check(h, t, lut, H, W, 1, true, who);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device_id));
+    HIPCHK(hipEventRecord(h->e0, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_raw, raw_host, raw_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_ts, col_ts, (size_t)W * 8, hipMemcpyHostToDevice, h->stream));
+    rc = grid_enqueue(h, t, h->d_raw, is_range, lut, (int)H, (int)W, h->d_ts, 0.0, 0.0);
+    if (rc) return rc;
+    int64_t sk = 0;
+    rc = grid_finish(h, n_valid, &sk);
+    if (skipped) *skipped = sk ? 1 : 0;
+    return rc;
+}
+extern "C" int ptl_grid_add_posed_range(ptl_grid* g, ptl_traj* t, ptl_lut* lut, const uint32_t* range_mm, const double* col_ts, int64_t* n_valid,
+                                        int32_t* skipped) {
+    if (!g || !t || !lut || !range_mm || !col_ts) return set_err(PTL_ERR_ARG, "ptl_grid_add_posed_range: null argument");
+    return grid_add_percall(g, t, lut, range_mm, (size_t)lut->H * lut->W * 4, true, lut->H, lut->W, col_ts, n_valid, skipped, "ptl_grid_add_posed_range");
+}
+extern "C" int ptl_grid_add_posed_xyz(ptl_grid* g, ptl_traj* t, const float* xyz, int32_t H, int32_t W, const double* col_ts, int64_t* n_valid,
+                                      int32_t* skipped) {
+    if (!g || !t || !xyz || !col_ts) return set_err(PTL_ERR_ARG, "ptl_grid_add_posed_xyz: null argument");
+    return grid_add_percall(g, t, nullptr, xyz, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * 12, false, H, W, col_ts, n_valid, skipped, "ptl_grid_add_posed_xyz");
+}
+// resident form, as carve_build: sweeps [first, last] of a lane, `slot` bytes apart.  The caller has checked the runner's side; the lane is
+// only read.  `wait_a`, `wait_b`: the runner's streams, waited for after the checks and before the first launch
+static int grid_build(ptl_grid* h, ptl_traj* t, const SeqLane& l, size_t slot, const unsigned char* is_range_k, bool all_range, const ptl_lut* lut,
+                      int64_t pps, const double* t0t1, int64_t first, int64_t last, hipStream_t wait_a, hipStream_t wait_b, int64_t* n_valid,
+                      int64_t* n_skipped, const char* who) {
+    const int64_t W = h->cfg.scan_cols;
+    if (pps % W) return set_err(PTL_ERR_CAPACITY, "%s: %lld points per sweep are no multiple of the grid handle's scan_cols = %lld", who, (long long)pps, (long long)W);
+    if (l.icp->c.W != W) return set_err(PTL_ERR_CAPACITY, "%s: the runner's scan_cols is %d, the grid handle's %lld", who, l.icp->c.W, (long long)W);
+    int rc = grid_check(h, t, lut, pps / W, W, last - first + 1, false, who);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device_id));
+    HIPCHK(hipStreamSynchronize(wait_a));  // the runner's own work first; its sweeps are then only read
+    HIPCHK(hipStreamSynchronize(wait_b));
+    HIPCHK(hipEventRecord(h->e0, h->stream));
+    for (int64_t k = first; k <= last; ++k) {
+        const bool rg = all_range || (is_range_k && is_range_k[(size_t)k]);
+        rc = grid_enqueue(h, t, (const char*)l.d_scans + (size_t)k * slot, rg, lut, (int)(pps / W), (int)W, nullptr, t0t1[2 * k], t0t1[2 * k + 1]);
+        if (rc) return rc;
+    }
+    return grid_finish(h, n_valid, n_skipped);
+}
+extern "C" int ptl_grid_add_seq(ptl_grid* g, ptl_seq* s, ptl_traj* t, const double* t0t1, int64_t first, int64_t last, int64_t* n_valid,
+                                int64_t* n_skipped) {
+    if (!g || !s || !t || !t0t1) return set_err(PTL_ERR_ARG, "ptl_grid_add_seq: null argument");
+    if (first < 0 || last < first || last >= s->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_grid_add_seq: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)s->cfg.n_scans);
+    if (s->cfg.icp.device_id != g->device_id) return set_err(PTL_ERR_ARG, "ptl_grid_add_seq: runner on device %d, grid on device %d", s->cfg.icp.device_id, g->device_id);
+    bool any_range = false;
+    for (int64_t k = first; k <= last; ++k) any_range = any_range || s->is_range[(size_t)k];
+    if (any_range && !s->lut) return set_err(PTL_ERR_STATE, "ptl_grid_add_seq: the sweeps are range images but no LUT was set (ptl_seq_set_lut)");
+    return grid_build(g, t, s->lane, (size_t)s->cfg.points_per_scan * 12, s->is_range.data(), false, any_range ? s->lut : nullptr, s->cfg.points_per_scan,
+                      t0t1, first, last, s->stream, s->ekf_stream, n_valid, n_skipped, "ptl_grid_add_seq");
+}
+extern "C" int ptl_grid_add_batch(ptl_grid* g, ptl_batch* b, int32_t seq, ptl_traj* t, const double* t0t1, int64_t first, int64_t last,
+                                  int64_t* n_valid, int64_t* n_skipped) {
+    if (!g || !b || !t || !t0t1) return set_err(PTL_ERR_ARG, "ptl_grid_add_batch: null argument");
+    if (seq < 0 || seq >= b->S) return set_err(PTL_ERR_ARG, "ptl_grid_add_batch: sequence %d of %d", seq, b->S);
+    if (first < 0 || last < first || last >= b->cfg.n_scans) return set_err(PTL_ERR_ARG, "ptl_grid_add_batch: sweeps [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)b->cfg.n_scans);
+    if (b->cfg.icp.device_id != g->device_id) return set_err(PTL_ERR_ARG, "ptl_grid_add_batch: batch on device %d, grid on device %d", b->cfg.icp.device_id, g->device_id);
+    if (b->ring < b->cfg.n_scans) return set_err(PTL_ERR_STATE, "ptl_grid_add_batch: the batch keeps a ring of %lld sweep slots (resident_scans): earlier sweeps are gone", (long long)b->ring);
+    if (b->cfg.range_input && !b->lut) return set_err(PTL_ERR_STATE, "ptl_grid_add_batch: a range-input batch needs its LUT (ptl_batch_set_lut)");
+    const size_t slot = (size_t)b->cfg.points_per_scan * (b->cfg.range_input ? 4 : 12);
+    return grid_build(g, t, b->lane[seq], slot, nullptr, b->is_range != 0, b->is_range ? b->lut : nullptr, b->cfg.points_per_scan, t0t1, first, last,
+                      b->stream, b->side, n_valid, n_skipped, "ptl_grid_add_batch");
+}
+extern "C" int ptl_grid_read(ptl_grid* h, ptl_grid_result* result, int32_t ix0, int32_t iy0, int32_t w, int32_t hh, uint32_t* free_out, uint32_t* hit_out) {
+    if (!h || !result) return set_err(PTL_ERR_ARG, "ptl_grid_read: null argument");
+    ABI_CHECK(ptl_grid_result, result);
+    const int given = (free_out != nullptr) + (hit_out != nullptr);
+    if (given == 1) return set_err(PTL_ERR_ARG, "ptl_grid_read: the two arrays (free, hit) are given together or not at all (1 given)");
+    const ptl_grid_cfg& u = h->cfg;
+    if (given && (w < 1 || hh < 1 || ix0 < 0 || iy0 < 0 || (int64_t)ix0 + w > u.nx || (int64_t)iy0 + hh > u.ny))
+        return set_err(PTL_ERR_ARG, "ptl_grid_read: the rectangle of %d x %d cells at (%d, %d) is empty or not inside the grid of %d x %d", w, hh, ix0, iy0, u.nx, u.ny);
+    HIPCHK(hipSetDevice(h->device_id));
+    hipStream_t s = h->stream;
+    unsigned long long sums[GRID_SUMS] = {0, 0, 0, 0};
+    int box[4] = {0x7fffffff, 0x7fffffff, -1, -1};
+    const int64_t wg = (h->n_cells + 255) / 256;
+    HIPCHK(hipEventRecord(h->e0, s));
+    HIPCHK(hipMemsetAsync(h->d_counts + GRID_COUNTERS, 0, (size_t)GRID_SUMS * 8, s));
+    HIPCHK(hipMemcpyAsync(h->d_box, box, sizeof box, hipMemcpyHostToDevice, s));
+    k_grid_reduce<<<(int)(wg < 1024 ? wg : 1024), 256, 0, s>>>(h->d_free, h->d_hit, u.nx, (int)h->n_cells, h->d_counts + GRID_COUNTERS, h->d_box);
+    HIPCHK(hipEventRecord(h->e1, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, h->d_counts + GRID_COUNTERS, sizeof sums, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(box, h->d_box, sizeof box, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    { int rc = grid_clock(h); if (rc) return rc; }
+    const uint32_t size = result->struct_size, abi = result->abi_version;
+    memset(result, 0, sizeof *result);
+    result->struct_size = size; result->abi_version = abi;
+    result->n_scans = (int64_t)h->counts[GRID_N_SCANS]; result->n_scans_skipped = (int64_t)h->counts[GRID_N_SKIPPED];
+    result->n_rays = (int64_t)h->counts[GRID_N_RAYS]; result->n_rays_out_of_range = (int64_t)h->counts[GRID_N_OOR];
+    result->n_no_return = (int64_t)h->counts[GRID_N_NORET]; result->n_runs_voted = (int64_t)h->counts[GRID_N_RUNS];
+    result->n_ends_outside = (int64_t)h->counts[GRID_N_ENDS_OUT];
+    result->n_cells_free = (int64_t)sums[0]; result->n_cells_hit = (int64_t)sums[1];
+    result->sum_free = (int64_t)sums[2]; result->sum_hit = (int64_t)sums[3];
+    const bool empty = box[2] < 0;
+    result->box_ix0 = empty ? 0 : box[0]; result->box_iy0 = empty ? 0 : box[1]; result->box_ix1 = box[2]; result->box_iy1 = box[3];
+    result->cell = u.cell; result->x0 = u.x0; result->y0 = u.y0; result->z_lo = u.z_lo; result->z_hi = u.z_hi; result->margin = u.margin;
+    result->step = u.step; result->min_range = u.min_range; result->max_range = u.max_range; result->nx = u.nx; result->ny = u.ny;
+    result->device_ms = h->device_ms;
+    if (given) {
+        const size_t at = (size_t)iy0 * u.nx + ix0;
+        HIPCHK(hipMemcpy2D(free_out, (size_t)w * 4, h->d_free + at, (size_t)u.nx * 4, (size_t)w * 4, (size_t)hh, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(hit_out, (size_t)w * 4, h->d_hit + at, (size_t)u.nx * 4, (size_t)w * 4, (size_t)hh, hipMemcpyDeviceToHost));
+    }
     return PTL_OK;
 }
 

@@ -255,6 +255,75 @@ class MapPainter:
         self.painter.close()
 
 
+def grid_bounds(positions, cell, pad):
+    """(x0, y0, nx, ny) of the grid that holds the xy of `positions` (N, >= 2) padded by `pad` metres, snapped outward to multiples of `cell`"""
+    p = np.asarray(positions, dtype=np.float64).reshape(len(positions), -1)[:, :2]
+    if len(p) == 0 or not np.isfinite(p).all():
+        raise ValueError("the grid's bounds need at least one finite position")
+    cell, pad = float(cell), float(pad)
+    lo = np.floor((p.min(axis=0) - pad) / cell)
+    hi = np.ceil((p.max(axis=0) + pad) / cell)
+    n = np.maximum(hi - lo, 1.0)
+    return float(lo[0] * cell), float(lo[1] * cell), int(n[0]), int(n[1])
+
+
+class GridBuilder:
+    """The occupancy grid of a run: a core.OccupancyGrid fed the way a MapAccumulator is.
+    lut: the sweeps' core.Lut, or an (H, W) pair for sweeps that come as xyz (a runner's resident ones).
+    traj_or_bounds: the grid's bounds (x0, y0, x1, y1) in metres (snapped outward to multiples of `cell` from x0, y0), or the trajectory's knots
+    - [(t, pose)] as utils.read_newer_college_gt gives them, or an array of poses (N, 4, 4) or positions (N, 3) - whose positions, padded by
+    max_range and snapped outward to multiples of `cell`, give the bounds.  A grid of more than 2^26 cells is refused with the count.
+    cfg: z_lo, z_hi, margin, step, min_range, max_range (defaults: the library's for the cell size, untuned)"""
+
+    def __init__(self, lut, traj_or_bounds, cell, device_id=0, **cfg):
+        self.lut = lut if hasattr(lut, "_h") else None
+        H, W = (lut.H, lut.W) if self.lut is not None else (int(lut[0]), int(lut[1]))
+        cell = float(cell)
+        if not cell > 0.0:
+            raise ValueError(f"cell = {cell:g}: must be positive")
+        max_range = 600.0 * cell if cfg.get("max_range") is None else float(cfg["max_range"])
+        tb = traj_or_bounds
+        if isinstance(tb, (tuple, list)) and len(tb) == 4 and all(np.isscalar(v) for v in tb):
+            bx0, by0, bx1, by1 = (float(v) for v in tb)
+            if not (bx1 > bx0 and by1 > by0):
+                raise ValueError(f"grid bounds ({bx0:g}, {by0:g}, {bx1:g}, {by1:g}): X1 must be above X0 and Y1 above Y0")
+            x0, y0, nx, ny = bx0, by0, max(int(np.ceil((bx1 - bx0) / cell)), 1), max(int(np.ceil((by1 - by0) / cell)), 1)
+        else:
+            if isinstance(tb, (tuple, list)) and len(tb) and isinstance(tb[0], (tuple, list)) and len(tb[0]) == 2:
+                tb = [p for _, p in tb]
+            a = np.asarray(tb, dtype=np.float64)
+            pos = a[:, :3, 3] if a.ndim == 3 else a.reshape(len(a), -1)[:, :3]
+            x0, y0, nx, ny = grid_bounds(pos, cell, max_range)
+        if nx * ny > core.GRID_MAX_CELLS:
+            raise ValueError(f"the grid would have {nx} x {ny} = {nx * ny} cells of {cell:g} m, the limit is {core.GRID_MAX_CELLS} (2^26): give "
+                             "narrower bounds (--grid-bounds X0,Y0,X1,Y1), a larger cell or a shorter --grid-max-range")
+        self.grid = core.OccupancyGrid(cell, x0, y0, nx, ny, W, H * W, device_id=device_id, **{k: v for k, v in cfg.items() if v is not None})
+
+    def update(self, scan, traj):
+        """one PosedScan or packets.PacketScan, posed by `traj` (a core.Traj) at its column timestamps, as MapAccumulator.update(scan, traj)
+        adds it.  Returns the sweep's used rays (0 for a sweep skipped as outside the bounds)"""
+        if self.lut is None:
+            raise ValueError("a range image needs the builder's lut")
+        range_mm = scan.range_mm if hasattr(scan, "range_mm") else scan.range
+        n_rays, _ = self.grid.add_posed(traj, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9, range_mm=range_mm, lut=self.lut)
+        return n_rays
+
+    def add_run(self, runner, traj, t0t1, s=None, first=0, last=None):
+        """the RESIDENT sweeps [first, last] of a core.SeqRunner (s=None) or of sequence s of a core.BatchRunner, as MapAccumulator.add_run"""
+        return self.grid.add_run(runner, traj, t0t1, s=s, first=first, last=last)
+
+    def counts(self):
+        """a core.GridCounts of the TOUCHED box only (the cells with any count; one empty cell when there is none): a grid sized by
+        max_range is mostly cells no ray came near"""
+        r = self.grid.summary()
+        if r.box_ix1 < r.box_ix0:
+            return self.grid.read(0, 0, 1, 1)
+        return self.grid.read(r.box_ix0, r.box_iy0, r.box_ix1 - r.box_ix0 + 1, r.box_iy1 - r.box_iy0 + 1)
+
+    def close(self):
+        self.grid.close()
+
+
 def scalar_colors(values, lo=None, hi=None, palette=None, unpainted=(128, 128, 128, 255)):
     """HOST POLICY, not part of the library's definition and not tuned: rgba words (n,) uint32 for per-point scalars (e.g. PaintValues.mean()),
     for core.Renderer.set_point_colors.  Linear between lo and hi: palette entry clamp(floor((v - lo) 256 / (hi - lo)), 0, 255) - lo and
@@ -773,6 +842,20 @@ def paint_packet_bag(painter, bags, info, traj, field, start_scan=0, end_scan=No
         for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
             if not hasattr(d, "lacc"):
                 painter.update(d, traj, name)
+    finally:
+        feed.close()
+
+
+def grid_packet_bag(builder, bags, info, traj, start_scan=0, end_scan=None, device_id=0):
+    """the counterpart of `add_packet_bag` for a `GridBuilder`: the same sweeps of the same bag(s), decoded by the package's packet feed and
+    posed by `traj` at their decoded column times"""
+    from . import packets as pk
+    from .bag import OusterPacketBagSource
+    feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info, device_id=device_id)
+    try:
+        for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+            if not hasattr(d, "lacc"):
+                builder.update(d, traj)
     finally:
         feed.close()
 

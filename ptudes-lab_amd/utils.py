@@ -523,6 +523,86 @@ def load_png(path: str) -> np.ndarray:
     return raw[:, 1:].reshape(h, w, 4).copy()
 
 
+_MAP_GRAY = (254, 0, 205)  # pixel of class 0 free, 1 occupied, 2 unknown (core.GRID_*): what ROS map_server's files use
+
+
+def _occupancy_paths(prefix: str):
+    import os
+    stem, ext = os.path.splitext(str(prefix))
+    if ext.lower() == ".png":
+        return str(prefix), stem + ".yaml"
+    return str(prefix) + ".pgm", str(prefix) + ".yaml"
+
+
+def save_occupancy_map(prefix: str, classes, cell: float, origin) -> Tuple[str, str]:
+    """An occupancy grid as ROS map_server reads it: `prefix`.pgm (binary P5, 254 free, 0 occupied, 205 unknown; the FIRST image row is the
+    LARGEST y) with `prefix`.yaml beside it (six lines: image, resolution, origin: [x, y, 0.0], negate: 0, occupied_thresh: 0.65, free_thresh:
+    0.196).  classes: (ny, nx) with 0 free, 1 occupied, 2 unknown (core.grid_classify), row 0 the smallest y; origin: (x, y) of the corner of
+    classes[0, 0].  A prefix that ends in .png writes that PNG (the same grey values, through `save_png`) and the .yaml beside it.  Standard
+    library and numpy only.  Returns (image path, yaml path)"""
+    import os
+    c = np.asarray(classes)
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1 or not np.isin(c, (0, 1, 2)).all():
+        raise ValueError("save_occupancy_map: need an (ny, nx) array of the classes 0 free, 1 occupied, 2 unknown")
+    if not float(cell) > 0.0:
+        raise ValueError(f"save_occupancy_map: cell = {cell}: must be positive")
+    gray = np.ascontiguousarray(np.array(_MAP_GRAY, dtype=np.uint8)[c.astype(np.int64)][::-1])
+    image, yaml = _occupancy_paths(prefix)
+    if image.lower().endswith(".png"):
+        save_png(image, np.dstack([gray, gray, gray, np.full_like(gray, 255)]))
+    else:
+        with open(image, "wb") as f:
+            f.write(b"P5\n%d %d\n255\n" % (gray.shape[1], gray.shape[0]) + gray.tobytes())
+    with open(yaml, "w") as f:
+        f.write(f"image: {os.path.basename(image)}\nresolution: {float(cell)!r}\norigin: [{float(origin[0])!r}, {float(origin[1])!r}, 0.0]\n"
+                "negate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n")
+    return image, yaml
+
+
+def load_occupancy_map(prefix: str):
+    """(classes (ny, nx) uint8 with row 0 the smallest y, cell, (x, y) of the corner of classes[0, 0]) of the files `save_occupancy_map(prefix,
+    ...)` wrote; `prefix` may also name the .yaml itself.  A grey value other than 254 / 0 / 205 is a ValueError"""
+    import os
+    yaml = str(prefix) if str(prefix).endswith(".yaml") else _occupancy_paths(prefix)[1]
+    meta = {}
+    with open(yaml) as f:
+        for line in f:
+            if ":" in line:
+                k, v = line.split(":", 1)
+                meta[k.strip()] = v.strip()
+    for k in ("image", "resolution", "origin"):
+        if k not in meta:
+            raise ValueError(f"{yaml}: no `{k}` line")
+    if meta.get("negate", "0") != "0":
+        raise ValueError(f"{yaml}: negate: {meta['negate']} is not written by save_occupancy_map")
+    image = os.path.join(os.path.dirname(yaml), meta["image"])
+    ox, oy = (float(v) for v in meta["origin"].strip("[]").split(",")[:2])
+    if image.lower().endswith(".png"):
+        gray = load_png(image)[:, :, 0]
+    else:
+        with open(image, "rb") as f:
+            data = f.read()
+        tokens, pos = [], 0
+        while len(tokens) < 4:  # P5, width, height, maxval: separated by white space, one white-space byte before the pixels
+            while data[pos:pos + 1].isspace():
+                pos += 1
+            end = pos
+            while end < len(data) and not data[end:end + 1].isspace():
+                end += 1
+            tokens.append(data[pos:end])
+            pos = end
+        if tokens[0] != b"P5" or tokens[3] != b"255":
+            raise ValueError(f"{image}: expected a binary P5 image with maxval 255")
+        w, h = int(tokens[1]), int(tokens[2])
+        gray = np.frombuffer(data, dtype=np.uint8, count=w * h, offset=pos + 1).reshape(h, w)
+    classes = np.full(gray.shape, 255, dtype=np.uint8)
+    for k, g in enumerate(_MAP_GRAY):
+        classes[gray == g] = k
+    if (classes == 255).any():
+        raise ValueError(f"{image}: a grey value other than {_MAP_GRAY}")
+    return np.ascontiguousarray(classes[::-1]), float(meta["resolution"]), (ox, oy)
+
+
 def nc_gt_file_rows(t, poses) -> List[Tuple[float, np.ndarray]]:
     """[(ts, pose)] as `read_newer_college_gt` gives them back from the file `save_poses_nc_gt_format(t, poses)` writes (through the
     same text, in memory): what a later `flyby --nc-gt-poses` of that file works with"""
