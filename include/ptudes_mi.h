@@ -1105,6 +1105,75 @@ int ptl_grid_read(ptl_grid *g, ptl_grid_result *result, int32_t ix0, int32_t iy0
 /* all counts and counters back to zero (the used rays too); the parameters stay */
 int ptl_grid_clear(ptl_grid *g);
 
+/* ------------------------------------------------------------------------------------------------
+ * A sweep's rays cast through a saved map: per pixel the first stored point along the pixel's ray (no reference counterpart).
+ * It answers what a posed sweep sees that the map does not and what the map holds that the sweep no longer sees, and - cast on a constant
+ * range image - gives the virtual sweep that the map predicts at a pose.  The map is only read.  Every output is plainly stored per pixel; a
+ * minimum with a total tie order has no order of evaluation, so status, t_hit, len and index are an exact function of the map's stored points
+ * and the ray - the lane mapping and the launch geometry do not change them.  All arithmetic fp64 in the written order, without contraction.
+ * Parameters: radius > 0; 0 < step <= the map's voxel size vs; min_range >= 0; max_range > min_range, max_range / step <= 65536.  The
+ * defaults (radius = vs / 5, step = vs / 2, min_range = 0, max_range = 120 vs) are a caller's choice that the result echoes back, NOT tuned
+ * values: nobody has run this on a real recording.  The map keeps a bounded number of points per voxel, so a thin ray can pass a wall's voxel
+ * without meeting a point: radius is the caller's lever on the share of rays that hit.
+ * Ray: ptl_carve's ray.  A pixel with a return; its end w is the world point the posed-scan pass gives it (ptl_icp_map_add_posed_*), its origin
+ * o the translation of its own column's pose; d = w - o, len2 = (dx dx + dy dy) + dz dz, len = sqrt(len2).  status 0: no return.  status 3
+ * (degenerate, counted): a return with len2 == 0 or a non-finite coordinate of w.  Every other return is cast, whatever its length: the
+ * measured length is reported and never used to stop the march.  A sweep with any column outside the trajectory's bounds is skipped as a whole
+ * and reported (result->skipped), as ptl_icp_map_add_posed_* skips it: every pixel then has status 0, t_hit = len = -1, index = -1.
+ * March: the samples are k = 0, 1, ... while t_k = ((double)k + 0.5) step < max_range: a_k = t_k / len, s_k[c] = o[c] + a_k d[c]; there is no
+ * end sample.  A sample's voxel is the map's own truncating index (int)(coordinate / vs) per axis; a sample outside the key range (2^20 voxels
+ * either side) is passed over; consecutive samples with one key visit the voxel once.
+ * Hit: for a point p stored in a visited voxel, e = p - o: c = e x d with six separately rounded products (cx = ey dz - ez dy, ...); p is near
+ * iff (cx cx + cy cy) + cz cz <= (radius radius) len2 (the left factor made once per call, the product once per ray);
+ * t_p = ((ex dx + ey dy) + ez dz) / len; p qualifies iff it is near and min_range <= t_p <= max_range.  The FIRST visited voxel, in march
+ * order, that holds a qualifying point decides: the hit is that voxel's qualifying point with the smallest t_p; ties go to the lexicographically
+ * smaller (x, y, z), then to the smaller pool index.  A voxel without a qualifying point is left for good, and a qualifying point with a smaller
+ * t_p in a LATER voxel does not change the answer.  status 1: hit.  status 2: marched to max_range without one.
+ * ONLY the voxels on the centre line are looked at.  Both rules are part of the definition, as in ptl_carve, and both are what allows a ray to
+ * stop at its first hit.
+ * Outputs per pixel, row-major [H][W]: status (u8); t_hit (fp64, -1 unless a hit); len (fp64, -1 unless a return; for a degenerate return the
+ * value as computed, which may be 0, inf or NaN); index (i32: the hit point's index in POOL ORDER - block id, then slot: the order of
+ * ptl_cast_points and of ptl_icp_map_score's, ptl_icp_map_compare's, ptl_carve_read's and ptl_paint_read's per-point outputs; -1 unless a hit).
+ * What has changed is the caller's policy on len against t_hit (the Python layer's CastSweep.changes), not the library's.
+ * Launch constants (ptl_build_info has no free slot): 256 threads per workgroup, a half-wave of 32 lanes per ray, at most 16384 workgroups. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_cast_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double radius, step, min_range, max_range;
+} ptl_cast_cfg;
+typedef struct {
+    int64_t n_pixels;                                  /* H W of the sweep */
+    int64_t n_no_return, n_degenerate, n_hit, n_miss;  /* pixels per status 0, 3, 1, 2; all zero but n_pixels when the sweep was skipped */
+    int64_t n_voxel_visits;                            /* visited voxels that the map holds, over all rays, up to and including each ray's deciding one */
+    int32_t skipped;                                   /* 1: a column lay outside the trajectory's bounds, nothing was cast */
+    int32_t reserved;
+    double radius, step, min_range, max_range;         /* the parameters as used */
+    double device_ms;                                  /* HIP-event time of this call's device work: upload, column table, the cast */
+} ptl_cast_result;
+typedef struct ptl_cast ptl_cast; /* casts through one map: its own stream, column table, sweep staging, prefixes and per-pixel output buffers */
+/* the library's sizeof(ptl_cast_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_cast_sizeof_cfg(void);
+/* the defaults for a map of that voxel size; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is
+ * refused with PTL_ERR_ARG and nothing is written */
+int ptl_cast_default_cfg(ptl_cast_cfg *cfg, double voxel_size);
+/* cfg nullable: the defaults of the map's voxel size.  Waits for the map's update, snapshots its point count and the per-block prefixes of the
+ * pool order.  The map handle must outlive the cast handle and is only ever read.  Checked before any HIP call, refused with the numbers
+ * (PTL_ERR_ARG): null map / out, a cfg of another size or version, each parameter bound above. */
+int ptl_cast_create(ptl_icp *map, const ptl_cast_cfg *cfg, ptl_cast **out);
+int ptl_cast_destroy(ptl_cast *c);
+/* one posed sweep, with the arguments of ptl_carve_add_posed_range / _xyz.  result and every output array are nullable; an array that is given
+ * holds H W elements.  Trajectory, LUT and map on one device (else PTL_ERR_ARG with the ids); W = the map handle's scan_cols and
+ * H W <= its max_points_per_scan (else PTL_ERR_CAPACITY with the numbers) - all before any HIP call.  Every call compares the map's point
+ * count with the snapshot: a map updated since ptl_cast_create gives PTL_ERR_STATE.  PTL_ERR_STATE as well when the map's table leads a probe
+ * to a block that does not hold the probed voxel.  Nothing is kept between calls: two calls with the same arguments give the same bytes. */
+int ptl_cast_posed_range(ptl_cast *c, ptl_traj *t, ptl_lut *lut, const uint32_t *range_mm, const double *col_ts, ptl_cast_result *result,
+                         uint8_t *status_out, double *t_out, double *len_out, int32_t *index_out);
+int ptl_cast_posed_xyz(ptl_cast *c, ptl_traj *t, const float *xyz, int32_t H, int32_t W, const double *col_ts, ptl_cast_result *result,
+                       uint8_t *status_out, double *t_out, double *len_out, int32_t *index_out);
+/* the stored points (3 doubles each) in pool order, so that an index can be resolved; *n_written (nullable) their number.  max_points below
+ * the map's point count: PTL_ERR_CAPACITY naming the count, nothing written. */
+int ptl_cast_points(ptl_cast *c, double *xyz_out, int64_t max_points, int64_t *n_written);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,18 @@ class GridResult(_Cfg):
                 ("device_ms", C.c_double)]
 
 
+class CastCfg(_Cfg):
+    """ptl_cast_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("radius", C.c_double), ("step", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double)]
+
+
+class CastResult(C.Structure):
+    _fields_ = [("n_pixels", C.c_int64), ("n_no_return", C.c_int64), ("n_degenerate", C.c_int64), ("n_hit", C.c_int64), ("n_miss", C.c_int64),
+                ("n_voxel_visits", C.c_int64), ("skipped", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double), ("step", C.c_double),
+                ("min_range", C.c_double), ("max_range", C.c_double), ("device_ms", C.c_double)]
+
+
 class PoseSearchCfg(_Cfg):
     """ptl_pose_search_cfg (include/ptudes_mi.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
@@ -362,6 +374,16 @@ PROTOTYPES = {
     "ptl_grid_read": (C.c_int, [_vp, C.POINTER(GridResult), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint32)]),
     "ptl_grid_clear": (C.c_int, [_vp]),
+    # a sweep's rays cast through a saved map: the first stored point along each pixel's ray (include/ptudes_mi.h)
+    "ptl_cast_sizeof_cfg": (C.c_int64, []),
+    "ptl_cast_default_cfg": (C.c_int, [C.POINTER(CastCfg), C.c_double]),
+    "ptl_cast_create": (C.c_int, [_vp, C.POINTER(CastCfg), _vpp]),
+    "ptl_cast_destroy": (C.c_int, [_vp]),
+    "ptl_cast_posed_range": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32), c_d_p, C.POINTER(CastResult), C.POINTER(C.c_uint8), c_d_p, c_d_p,
+                                       C.POINTER(C.c_int32)]),
+    "ptl_cast_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, C.POINTER(CastResult), C.POINTER(C.c_uint8), c_d_p,
+                                     c_d_p, C.POINTER(C.c_int32)]),
+    "ptl_cast_points": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

@@ -52,6 +52,29 @@ def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fract
     return out
 
 
+def change_options(changes, cast_radius, change_margin, cast_max_range, save_changes):
+    """the options of --changes, checked before any device is touched: None without --changes, else the cfg of fly.SweepDiffer"""
+    if not changes:
+        for opt, v in (("--save-changes", save_changes), ("--cast-radius", cast_radius), ("--change-margin", change_margin),
+                       ("--cast-max-range", cast_max_range)):
+            if v is not None:
+                raise click.ClickException(f"{opt} belongs to --changes")
+        return None
+    if cast_radius is not None and not cast_radius > 0.0:
+        raise click.ClickException(f"--cast-radius {cast_radius:g}: must be positive")
+    if change_margin is not None and not change_margin > 0.0:
+        raise click.ClickException(f"--change-margin {change_margin:g}: must be positive")
+    if cast_max_range is not None and not cast_max_range > 0.0:
+        raise click.ClickException(f"--cast-max-range {cast_max_range:g}: must be positive")
+    return dict(radius=cast_radius, margin=change_margin, max_range=cast_max_range)
+
+
+def fix_knots(t, fix):
+    """the knots of the trajectory that poses a sweep for --changes: its own fix, the same pose at two knot times.  A fix is one pose per
+    sweep and every column is evaluated at the sweep's time, the last knot, so an earlier fix would not enter the pose"""
+    return [t - 1.0, t], [fix, fix]
+
+
 @click.command(name="localize")
 @click.argument("source", required=False, type=click.Path())
 @click.option("-m", "--meta", required=False, type=click.Path(exists=True, dir_okay=False, readable=True),
@@ -75,11 +98,22 @@ def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fract
               help="write the sweeps' poses in the map's frame, Newer College format")
 @click.option("--save-kitti-poses", required=False, type=click.Path(exists=False, dir_okay=False),
               help="write the sweeps' poses in the map's frame, KITTI format")
+@click.option("--changes", is_flag=True, help="cast every sweep's rays through the map at its fix and print the pixels per class "
+              "(agree / new / gone / unmapped)")
+@click.option("--cast-radius", type=float, default=None, help="--changes: radius of a ray, metres (default: voxel size / 5, untuned)")
+@click.option("--change-margin", type=float, default=None,
+              help="--changes: a measured length within this of the map's is `agree`, metres (default: the voxel size, untuned)")
+@click.option("--cast-max-range", type=float, default=None, help="--changes: how far a ray is marched, metres (default: 120 voxels, untuned)")
+@click.option("--save-changes", required=False, type=click.Path(file_okay=False),
+              help="--changes: write changes_%06d.png per sweep into this directory, one fixed colour per class")
 def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optional[int], synthetic_size: Optional[str],
                     map_path: Optional[str], keyframes: Optional[str], yaws: Optional[int], keyframe_spacing: Optional[float],
                     top: Optional[int], min_fraction: Optional[float], query_voxel: Optional[float], start_scan: int,
-                    end_scan: Optional[int], save_nc_gt_poses: Optional[str], save_kitti_poses: Optional[str]) -> None:
+                    end_scan: Optional[int], save_nc_gt_poses: Optional[str], save_kitti_poses: Optional[str], changes: bool,
+                    cast_radius: Optional[float], change_margin: Optional[float], cast_max_range: Optional[float],
+                    save_changes: Optional[str]) -> None:
     """Poses of the sweeps of SOURCE in the frame of a saved map."""
+    diff_cfg = change_options(changes, cast_radius, change_margin, cast_max_range, save_changes)
     opts = localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan)
     if synthetic_size is not None and synthetic is None:
         raise click.ClickException("--synthetic-size belongs to --synthetic")
@@ -107,7 +141,7 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
         from .. import synth
         n_scans = (end_scan + 1) if end_scan is not None else 100
         seq = synth.make_sequence(seed=synthetic, n_scans=n_scans, H=H, W=W)
-        points_per_sweep = H * W
+        points_per_sweep, sweep_hw = H * W, (H, W)
 
         def sweeps():
             for k in range(start_scan, n_scans):
@@ -118,7 +152,7 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
         info = pk.read_metadata_json(meta)
         lut = fly.sensor_lut(info, use_extrinsics=True)  # (the registration's: lidar_to_sensor and the extrinsic)
         bags = sorted(path.glob("*.bag")) if path.is_dir() else path
-        points_per_sweep = lut.H * lut.W
+        points_per_sweep, sweep_hw = lut.H * lut.W, (lut.H, lut.W)
 
         def sweeps():
             feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info)
@@ -131,18 +165,43 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
 
     loc = fly.MapLocalizer(map_pts, [p for _, p in kf], n_yaw=opts["yaws"], spacing=opts["spacing"], top=opts["top"],
                            min_fraction=opts["min_fraction"], query_voxel=opts["query_voxel"], voxel_size=MAP_VOXEL_SIZE,
-                           max_points_per_scan=max(points_per_sweep, 1 << 16))
+                           max_points_per_scan=max(points_per_sweep, 1 << 16), **(dict(scan_cols=sweep_hw[1]) if diff_cfg else {}))
     print(f"map: {opts['map']} ({len(map_pts)} points, voxel size {MAP_VOXEL_SIZE})")
     print(f"keyframes: {opts['keyframes']} ({len(kf)} poses, {len(loc.kept)} kept) x {opts['yaws']} yaws = {len(loc.candidates)} candidates")
     res_t, res_poses, fractions = [], [], []
+    differ, totals = None, {}
     try:
+        if diff_cfg is not None:
+            import os
+            from .. import core
+            from ..utils import save_png
+            differ = fly.SweepDiffer(loc.icp, **{k: v for k, v in diff_cfg.items() if v is not None})
+            c = differ.caster.cfg
+            print(f"changes: radius {c.radius:g} m, step {c.step:g} m, range [{c.min_range:g}, {c.max_range:g}] m, margin {differ.margin:g} m")
+            if save_changes:
+                os.makedirs(save_changes, exist_ok=True)
         for ts, xyz in sweeps():
             fix = loc.track(xyz)
             res_t.append(ts)
             res_poses.append(fix.pose)
             fractions.append(fix.fraction)
+            if differ is not None:
+                kt, kp = fix_knots(ts, fix.pose)
+                traj = core.Traj(kt, kp, 0.0, 0.0)
+                try:
+                    classes, n = differ.update_xyz(np.asarray(xyz, dtype=np.float32), sweep_hw[0], sweep_hw[1], traj, np.full(sweep_hw[1], kt[-1]))
+                finally:
+                    traj.close()
+                k = start_scan + len(res_poses) - 1
+                print(f"changes {k:06d}: " + ", ".join(f"{name} {n[name]}" for name in core.CHANGE_NAMES))
+                for name, v in n.items():
+                    totals[name] = totals.get(name, 0) + v
+                if save_changes:
+                    save_png(os.path.join(save_changes, f"changes_{k:06d}.png"), differ.image(classes))
         relocalizations, search_ms, rescore_ms, query_ms = loc.relocalizations, loc.search_ms, loc.rescore_ms, loc.query_ms
     finally:
+        if differ is not None:
+            differ.close()
         loc.close()
     header = f"localize: map {opts['map']}, keyframes {opts['keyframes']}\n(sweeps num: {len(res_poses)})"
     if save_kitti_poses:
@@ -155,4 +214,8 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
     print(f"re-localisations: {relocalizations}")
     print(f"mean hit fraction: {float(np.mean(fractions)) if fractions else 0.0:.6f}")
     print(f"search device time: {search_ms + rescore_ms:.3f} ms (candidate searches {search_ms:.3f} ms, rescoring {rescore_ms:.3f} ms)")
+    if diff_cfg is not None:
+        print("changes, all sweeps: " + ", ".join(f"{name} {v}" for name, v in totals.items()))
+        if save_changes:
+            print(f"change images saved to: {save_changes}")
     print(f"sweep thinning: {query_ms:.3f} ms of wall time (a scratch one-point-per-voxel map per sweep)")

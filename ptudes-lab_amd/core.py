@@ -479,6 +479,7 @@ class Traj:
         if len(kt) != len(kp):
             raise ValueError("one pose per knot timestamp")
         self.n_knots, self.bounds, self.device_id = len(kt), (float(bound_before), float(bound_after)), int(device_id)
+        self.t_first = float(kt[0]) if len(kt) else 0.0
         self._h = C.c_void_p()
         L.check(L.lib().ptl_traj_create(int(device_id), L.dptr(kt), L.dptr(kp), len(kt), float(bound_before), float(bound_after),
                                         C.byref(self._h)))
@@ -615,6 +616,146 @@ class Carver:
         k = w.value
         vals = [getattr(res, f) for f, _ in res._fields_]
         return CarveVotes(xyz[:k].copy(), thr[:k].copy(), sup[:k].copy(), *(int(v) for v in vals[:11]), *(float(v) for v in vals[11:]))
+
+
+CAST_NONE, CAST_HIT, CAST_MISS, CAST_DEGENERATE = 0, 1, 2, 3                      # pixel status of a cast (include/ptudes_mi.h)
+CHANGE_NONE, CHANGE_AGREE, CHANGE_NEW, CHANGE_GONE, CHANGE_UNMAPPED = 0, 1, 2, 3, 4  # classes of `cast_changes`
+CHANGE_NAMES = ("none", "agree", "new", "gone", "unmapped")
+
+
+def cast_changes(status, t_hit, length, margin):
+    """HOST POLICY on the outputs of a cast, not part of the library's definition: a u8 class per pixel.  For a hit (status 1):
+    AGREE |len - t_hit| <= margin, NEW len < t_hit - margin (the sweep ends in front of what the map holds), GONE len > t_hit + margin (the
+    sweep goes on behind it); UNMAPPED a return that marched to max_range without a hit (status 2); NONE everything else - no return, or a
+    degenerate one: nothing to say"""
+    st, t, ln = np.asarray(status), np.asarray(t_hit, dtype=np.float64), np.asarray(length, dtype=np.float64)
+    m = float(margin)
+    if not m >= 0.0:
+        raise ValueError(f"margin = {margin}: must be >= 0")
+    out = np.full(st.shape, CHANGE_NONE, dtype=np.uint8)
+    hit = st == CAST_HIT
+    with np.errstate(invalid="ignore"):
+        out[hit & (np.abs(ln - t) <= m)] = CHANGE_AGREE
+        out[hit & (ln < t - m)] = CHANGE_NEW
+        out[hit & (ln > t + m)] = CHANGE_GONE
+    out[st == CAST_MISS] = CHANGE_UNMAPPED
+    return out
+
+
+@dataclass
+class CastSweep:
+    """What `Caster.cast_range` / `cast_xyz` return (include/ptudes_mi.h ptl_cast_result): per pixel (H, W) the status, the
+    hit's distance along the ray (-1 unless a hit), the measured length (-1 unless a return) and the hit point's index in pool order (-1 unless
+    a hit: a row of `Caster.points()` and of every per-point array in pool order); `result` the counts and the parameters as used"""
+    status: np.ndarray   # (H, W) uint8
+    t_hit: np.ndarray    # (H, W) float64
+    len: np.ndarray      # (H, W) float64
+    index: np.ndarray    # (H, W) int32
+    result: dict
+    voxel_size: float = 0.0
+
+    def changes(self, margin=None):
+        """`cast_changes` of this sweep (default margin: the map's voxel size, untuned): host policy, not the library's"""
+        return cast_changes(self.status, self.t_hit, self.len, self.voxel_size if margin is None else margin)
+
+    def expected_range_mm(self):
+        """the range image the map predicts: t_hit in mm rounded to u32, 0 where there is no hit"""
+        hit = self.status == CAST_HIT
+        return np.where(hit, np.rint(np.where(hit, self.t_hit, 0.0) * 1000.0), 0.0).astype(np.uint32)
+
+    def gather(self, values, fill=0):
+        """per-pixel values of a per-point array in pool order (e.g. `PaintValues.mean()`): values[index] where there is a hit, else `fill`"""
+        v = np.asarray(values)
+        hit = self.index >= 0
+        if hit.any() and int(self.index.max()) >= len(v):
+            raise ValueError(f"a hit points at stored point {int(self.index.max())}, `values` has {len(v)} rows: not this map's pool order")
+        out = np.empty(self.index.shape + v.shape[1:], dtype=np.result_type(v.dtype, np.asarray(fill).dtype))
+        out[...] = fill
+        out[hit] = v[self.index[hit]]
+        return out
+
+
+def change_counts(classes):
+    """{name: pixels} of a class image of `cast_changes`"""
+    n = np.bincount(np.asarray(classes, dtype=np.uint8).reshape(-1), minlength=len(CHANGE_NAMES))
+    return {name: int(n[i]) for i, name in enumerate(CHANGE_NAMES)}
+
+
+def cast_cfg(voxel_size, radius=None, step=None, min_range=None, max_range=None):
+    """the _lib.CastCfg of a map of that voxel size: the library's defaults with the given fields on top"""
+    cfg = L.CastCfg()
+    L.check(L.lib().ptl_cast_default_cfg(C.byref(cfg), float(voxel_size)))
+    for k, v in (("radius", radius), ("step", step), ("min_range", min_range), ("max_range", max_range)):
+        if v is not None:
+            setattr(cfg, k, float(v))
+    return cfg
+
+
+class Caster:
+    """A sweep's rays cast through `map_icp`'s map (include/ptudes_mi.h ptl_cast_*): per pixel of a posed sweep the first
+    stored point along the pixel's ray.  The map is only read and must not be updated (nor closed) while the caster lives: a map updated since
+    gives a RuntimeError at the next call"""
+
+    def __init__(self, map_icp, radius=None, step=None, min_range=None, max_range=None):
+        self.map_icp = map_icp
+        self.cfg = cast_cfg(map_icp.cfg.voxel_size, radius, step, min_range, max_range)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_cast_create(map_icp._h, C.byref(self.cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_cast_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @staticmethod
+    def _col_ts(traj, col_ts, W):
+        """one time per column; None: every column at the trajectory's first knot time (a pose held still)"""
+        return np.full(W, traj.t_first) if col_ts is None else L.as_f64(col_ts).reshape(-1)
+
+    def _cast(self, H, W, call):
+        st, t, ln, ix = np.zeros((H, W), dtype=np.uint8), np.empty((H, W)), np.empty((H, W)), np.empty((H, W), dtype=np.int32)
+        res = L.CastResult()
+        L.check(call(C.byref(res), st.ctypes.data_as(C.POINTER(C.c_uint8)), L.dptr(t), L.dptr(ln), ix.ctypes.data_as(C.POINTER(C.c_int32))))
+        out = {f: getattr(res, f) for f, _ in res._fields_ if f != "reserved"}
+        out["skipped"] = bool(out["skipped"])
+        return CastSweep(st, t, ln, ix, out, float(self.map_icp.cfg.voxel_size))
+
+    def cast_range(self, traj, lut, range_mm, col_ts=None):
+        """one posed range image (H x W u32 mm, 0 = no return) of `lut`; col_ts one time per column (None: every column at the trajectory's
+        first knot time) - returns a `CastSweep`"""
+        r = np.ascontiguousarray(range_mm, dtype=np.uint32).reshape(-1)
+        t = self._col_ts(traj, col_ts, lut.W)
+        if r.size != lut.H * lut.W or len(t) != lut.W:
+            raise ValueError("need an H x W range image and one time per column")
+        return self._cast(lut.H, lut.W, lambda *out: L.lib().ptl_cast_posed_range(self._h, traj._h, lut._h, r.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                                   L.dptr(t), *out))
+
+    def cast_xyz(self, traj, xyz, H, W, col_ts=None):
+        """one posed sweep of H x W f32 points in the sensor frame, (0, 0, 0) = no return - returns a `CastSweep`"""
+        x = np.ascontiguousarray(xyz, dtype=np.float32)
+        H, W = int(H), int(W)
+        t = self._col_ts(traj, col_ts, W)
+        if x.size != H * W * 3 or len(t) != W:
+            raise ValueError("need H x W x 3 points and one time per column")
+        return self._cast(max(H, 1), max(W, 1), lambda *out: L.lib().ptl_cast_posed_xyz(self._h, traj._h, x.ctypes.data_as(C.POINTER(C.c_float)), H, W,
+                                                                                        L.dptr(t), *out))
+
+    def expected(self, traj, lut, col_ts=None, ref_range=None):
+        """the VIRTUAL SWEEP the map predicts at the trajectory's poses: `cast_range` of a constant range image of `ref_range` mm (default
+        max_range), so that every pixel of the LUT is cast; `expected_range_mm()` of the result is the predicted range image"""
+        ref = int(round(self.cfg.max_range * 1000.0)) if ref_range is None else int(ref_range)
+        if not 0 < ref < 1 << 32:
+            raise ValueError(f"ref_range = {ref} mm: must be a positive u32")
+        return self.cast_range(traj, lut, np.full((lut.H, lut.W), ref, dtype=np.uint32), col_ts)
+
+    def points(self):
+        """the map's stored points (N, 3) in pool order: `CastSweep.index` points into them"""
+        _, p = self.map_icp.map_size()
+        xyz, w = np.empty((max(p, 1), 3)), C.c_int64()
+        L.check(L.lib().ptl_cast_points(self._h, L.dptr(xyz), p, C.byref(w)))
+        return xyz[:w.value].copy()
 
 
 @dataclass

@@ -13,6 +13,7 @@
 #include "render_kernels.h"
 #include "compare_kernels.h"
 #include "carve_kernels.h"
+#include "cast_kernels.h"
 #include "grid_kernels.h"
 #include "paint_kernels.h"
 #include "pose_kernels.h"
@@ -3625,6 +3626,202 @@ extern "C" int ptl_carve_read(ptl_carve* h, ptl_carve_result* result, double* xy
         HIPCHK(hipMemcpy(support_out, h->d_support, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     if (given && n_written) *n_written = n;
+    return PTL_OK;
+}
+
+// ================================================================================================ rays cast through a map
+// The definition is in include/ptudes_mi.h, the kernel in cast_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// cast handle owns what its pass needs - stream, column table, sweep staging, prefixes, per-pixel outputs, counters - and only reads the map
+// handle.  Nothing is kept between calls but the prefixes.
+struct ptl_cast {
+    int device_id = 0;  // (first member, as in ptl_traj)
+    ptl_icp* map = nullptr;
+    ptl_cast_cfg cfg;
+    int64_t n_points = 0;  // the map's point count at create: every call compares
+    int n_alloc = 1;
+    Stream stream;
+    Event e0, e1;
+    double* coltab = nullptr;   // [12][W]
+    double* d_ts = nullptr;     // [W]
+    void* d_raw = nullptr;      // one sweep of the caller's: n_max pixels of f32 xyz or u32 ranges
+    FlyWs* d_fly = nullptr;     // k_fly_coltab's flag
+    int* d_blk_off = nullptr;   // [pool_cap]
+    unsigned char* d_status = nullptr;  // [n_max] per pixel, as are the next three
+    double *d_t = nullptr, *d_len = nullptr;
+    int* d_index = nullptr;
+    double* d_xyz = nullptr;    // [n_alloc][3], made by the first ptl_cast_points
+    unsigned long long* d_counts = nullptr;  // [CAST_COUNTERS]
+    int* d_bad = nullptr;
+    DevOwner mem;
+};
+static void cast_defaults(ptl_cast_cfg* cfg, double vs) {
+    PTL_CFG_INIT(cfg);
+    cfg->radius = vs / 5.0; cfg->step = vs / 2.0; cfg->min_range = 0.0; cfg->max_range = 120.0 * vs;
+}
+extern "C" int64_t ptl_cast_sizeof_cfg(void) { return (int64_t)sizeof(ptl_cast_cfg); }
+extern "C" int ptl_cast_default_cfg(ptl_cast_cfg* cfg, double voxel_size) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "cfg is null");
+    ABI_CHECK(ptl_cast_cfg, cfg);
+    if (!(voxel_size > 0.0) || !(voxel_size < 1.0e150)) return set_err(PTL_ERR_ARG, "voxel_size must be positive and finite (got %g)", voxel_size);
+    cast_defaults(cfg, voxel_size);
+    return PTL_OK;
+}
+// the map as it is now: its update waited for, its point count against the snapshot
+static int cast_map_unchanged(ptl_cast* h, const char* who) {
+    ptl_icp* m = h->map;
+    HIPCHK(hipSetDevice(h->device_id));
+    HIPCHK(hipStreamSynchronize(m->map_stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, m->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((int64_t)st.map_points != h->n_points)
+        return set_err(PTL_ERR_STATE, "%s: the map holds %lld points, it held %lld at ptl_cast_create: a map updated since then needs a new cast handle", who,
+                       (long long)st.map_points, (long long)h->n_points);
+    return PTL_OK;
+}
+extern "C" int ptl_cast_create(ptl_icp* map, const ptl_cast_cfg* cfg, ptl_cast** out) {
+    if (!map || !out) return set_err(PTL_ERR_ARG, "ptl_cast_create: null argument");
+    ptl_cast_cfg use;
+    if (cfg) { ABI_CHECK(ptl_cast_cfg, cfg); use = *cfg; } else cast_defaults(&use, map->cfg.voxel_size);
+    const double vs = map->cfg.voxel_size;
+    if (!(use.radius > 0.0) || !(use.radius < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_cast_create: radius = %g: must be positive and finite", use.radius);
+    if (!(use.step > 0.0) || !(use.step <= vs))
+        return set_err(PTL_ERR_ARG, "ptl_cast_create: step = %g: the march needs 0 < step <= the map's voxel size = %g", use.step, vs);
+    if (!(use.min_range >= 0.0)) return set_err(PTL_ERR_ARG, "ptl_cast_create: min_range = %g: must be >= 0", use.min_range);
+    if (!(use.max_range > use.min_range)) return set_err(PTL_ERR_ARG, "ptl_cast_create: max_range = %g: must be above min_range = %g", use.max_range, use.min_range);
+    if (!(use.max_range / use.step <= (double)CAST_MAX_SAMPLES))
+        return set_err(PTL_ERR_ARG, "ptl_cast_create: max_range / step = %g / %g = %g samples per ray: the limit is %d", use.max_range, use.step,
+                       use.max_range / use.step, CAST_MAX_SAMPLES);
+    HIPCHK(hipSetDevice(map->cfg.device_id));
+    std::unique_ptr<ptl_cast> h(new ptl_cast());
+    h->device_id = map->cfg.device_id; h->map = map; h->cfg = use;
+    HIPCHK(h->stream.create());
+    HIPCHK(h->e0.create(hipEventDefault)); HIPCHK(h->e1.create(hipEventDefault));
+    HIPCHK(hipStreamSynchronize(map->map_stream));  // (a map update may still be under way)
+    HIPCHK(hipStreamSynchronize(map->stream));
+    DevState st;
+    HIPCHK(hipMemcpyAsync(&st, map->c.st, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int64_t n = st.map_points;
+    if (n < 0 || n > (int64_t)0x7fffffff) return set_err(PTL_ERR_STATE, "ptl_cast_create: the map reports %lld points", (long long)n);
+    h->n_points = n; h->n_alloc = n > 0 ? (int)n : 1;
+    const Ctx& c = map->c;
+    const int n_chunks = (c.pool_cap + SCORE_CHUNK - 1) / SCORE_CHUNK;
+    const size_t px = (size_t)map->n_max;
+    h->mem.add(&h->coltab, (size_t)12 * c.W); h->mem.add(&h->d_ts, (size_t)c.W);
+    { unsigned char* raw = nullptr; h->mem.add(&raw, px * 12); h->d_raw = raw; }
+    h->mem.add(&h->d_fly, 1); h->mem.add(&h->d_blk_off, (size_t)c.pool_cap);
+    h->mem.add(&h->d_status, px); h->mem.add(&h->d_t, px); h->mem.add(&h->d_len, px); h->mem.add(&h->d_index, px);
+    h->mem.add(&h->d_counts, (size_t)CAST_COUNTERS); h->mem.add(&h->d_bad, 1);
+    HIPCHK(h->mem.err);
+    DevOwner tmp;
+    int *d_cnt = nullptr, *d_off = nullptr;
+    tmp.add(&d_cnt, (size_t)n_chunks); tmp.add(&d_off, (size_t)n_chunks + 1);
+    HIPCHK(tmp.err);
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemsetAsync(h->d_fly, 0, sizeof(FlyWs), s));
+    HIPCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), s));
+    k_score_count<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_cnt);
+    k_score_scan<<<1, 1024, 0, s>>>(d_cnt, n_chunks, d_off);
+    k_carve_blkoff<<<(c.pool_cap + 255) / 256, 256, 0, s>>>(c, d_off, h->d_blk_off);
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + n_chunks, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total != (int)n) return set_err(PTL_ERR_STATE, "ptl_cast_create: the block directory holds %d points, the map state %lld", total, (long long)n);
+    *out = h.release();
+    return PTL_OK;
+}
+extern "C" int ptl_cast_destroy(ptl_cast* c) { return c ? handle_destroy(c, c->device_id) : PTL_OK; }
+// what every call checks before any HIP call
+static int cast_check(ptl_cast* h, const ptl_traj* t, const ptl_lut* lut, int64_t H, int64_t W, const char* who) {
+    const ptl_icp* m = h->map;
+    if (t->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: trajectory on device %d, map on device %d", who, t->device_id, h->device_id);
+    if (lut && lut->device_id != h->device_id) return set_err(PTL_ERR_ARG, "%s: LUT on device %d, map on device %d", who, lut->device_id, h->device_id);
+    if (H < 1 || W < 1) return set_err(PTL_ERR_ARG, "%s: empty scan (%lld x %lld)", who, (long long)H, (long long)W);
+    if (W != m->c.W) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld columns, the map handle's scan_cols is %d", who, (long long)W, m->c.W);
+    if (H * W > m->n_max) return set_err(PTL_ERR_CAPACITY, "%s: the scan has %lld pixels, the map handle's max_points_per_scan is %lld", who, (long long)(H * W), (long long)m->n_max);
+    return PTL_OK;
+}
+static int cast_percall(ptl_cast* h, ptl_traj* t, ptl_lut* lut, const void* raw_host, size_t raw_bytes, bool is_range, int64_t H, int64_t W,
+                        const double* col_ts, ptl_cast_result* result, uint8_t* status_out, double* t_out, double* len_out, int32_t* index_out,
+                        const char* who) {
+    int rc = cast_check(h, t, lut, H, W, who);
+    if (rc) return rc;
+    rc = cast_map_unchanged(h, who);
+    if (rc) return rc;
+    const Ctx& c = h->map->c;
+    hipStream_t s = h->stream;
+    const int n = (int)(H * W);
+    CastArgs a = {};
+    a.r2 = h->cfg.radius * h->cfg.radius; a.step = h->cfg.step; a.min_range = h->cfg.min_range; a.max_range = h->cfg.max_range;
+    a.blk_off = h->d_blk_off; a.n_alloc = h->n_alloc; a.status = h->d_status; a.t_hit = h->d_t; a.len = h->d_len; a.index = h->d_index;
+    a.counts = h->d_counts; a.bad = h->d_bad;
+    const int per_wg = (CAST_THREADS / 64) * 2;
+    const int wg = (n + per_wg - 1) / per_wg, grid = wg < CAST_MAX_BLOCKS ? wg : CAST_MAX_BLOCKS;
+    HIPCHK(hipEventRecord(h->e0, s));
+    HIPCHK(hipMemcpyAsync(h->d_raw, raw_host, raw_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_ts, col_ts, (size_t)W * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->d_counts, 0, (size_t)CAST_COUNTERS * 8, s));
+    HIPCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), s));
+    k_fly_coltab<<<1, 256, 0, s>>>(t->d_kt, t->d_kp, t->n, t->before, t->after, h->d_ts, 0.0, 0.0, (int)W, h->coltab, h->d_fly);
+    if (is_range) k_cast_rays<true><<<grid, CAST_THREADS, 0, s>>>(h->d_raw, lut->dir, lut->off, n, (int)W, h->coltab, h->d_fly, c, a);
+    else k_cast_rays<false><<<grid, CAST_THREADS, 0, s>>>(h->d_raw, nullptr, nullptr, n, (int)W, h->coltab, h->d_fly, c, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->e1, s));
+    unsigned long long now[CAST_COUNTERS];
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(now, h->d_counts, sizeof now, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad) return set_err(PTL_ERR_STATE, "%s: the map's table led %d probes to a block that does not hold the probed voxel", who, bad);
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    if (status_out) HIPCHK(hipMemcpy(status_out, h->d_status, (size_t)n, hipMemcpyDeviceToHost));
+    if (t_out) HIPCHK(hipMemcpy(t_out, h->d_t, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (len_out) HIPCHK(hipMemcpy(len_out, h->d_len, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (index_out) HIPCHK(hipMemcpy(index_out, h->d_index, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (result) {
+        memset(result, 0, sizeof *result);
+        result->n_pixels = n;
+        result->n_no_return = (int64_t)now[CAST_N_NORET]; result->n_degenerate = (int64_t)now[CAST_N_DEGEN];
+        result->n_hit = (int64_t)now[CAST_N_HIT]; result->n_miss = (int64_t)now[CAST_N_MISS];
+        result->n_voxel_visits = (int64_t)now[CAST_N_VISITS];
+        result->skipped = now[CAST_N_SKIPPED] ? 1 : 0;
+        result->radius = h->cfg.radius; result->step = h->cfg.step; result->min_range = h->cfg.min_range; result->max_range = h->cfg.max_range;
+        result->device_ms = ms;
+    }
+    return PTL_OK;
+}
+extern "C" int ptl_cast_posed_range(ptl_cast* c, ptl_traj* t, ptl_lut* lut, const uint32_t* range_mm, const double* col_ts, ptl_cast_result* result,
+                                    uint8_t* status_out, double* t_out, double* len_out, int32_t* index_out) {
+    if (!c || !t || !lut || !range_mm || !col_ts) return set_err(PTL_ERR_ARG, "ptl_cast_posed_range: null argument");
+    return cast_percall(c, t, lut, range_mm, (size_t)lut->H * lut->W * 4, true, lut->H, lut->W, col_ts, result, status_out, t_out, len_out, index_out,
+                        "ptl_cast_posed_range");
+}
+extern "C" int ptl_cast_posed_xyz(ptl_cast* c, ptl_traj* t, const float* xyz, int32_t H, int32_t W, const double* col_ts, ptl_cast_result* result,
+                                  uint8_t* status_out, double* t_out, double* len_out, int32_t* index_out) {
+    if (!c || !t || !xyz || !col_ts) return set_err(PTL_ERR_ARG, "ptl_cast_posed_xyz: null argument");
+    return cast_percall(c, t, nullptr, xyz, (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) * 12, false, H, W, col_ts, result, status_out, t_out, len_out,
+                        index_out, "ptl_cast_posed_xyz");
+}
+extern "C" int ptl_cast_points(ptl_cast* h, double* xyz_out, int64_t max_points, int64_t* n_written) {
+    if (!h || !xyz_out) return set_err(PTL_ERR_ARG, "ptl_cast_points: null argument");
+    if (max_points < 0) return set_err(PTL_ERR_ARG, "ptl_cast_points: max_points = %lld: must not be negative", (long long)max_points);
+    const int64_t n = h->n_points;
+    if (max_points < n) return set_err(PTL_ERR_CAPACITY, "ptl_cast_points: the map holds %lld points, max_points = %lld", (long long)n, (long long)max_points);
+    { int rc = cast_map_unchanged(h, "ptl_cast_points"); if (rc) return rc; }
+    if (n_written) *n_written = 0;
+    if (n > 0) {
+        hipStream_t s = h->stream;
+        if (!h->d_xyz) HIPCHK(h->mem.alloc(&h->d_xyz, (size_t)n * 3));
+        k_carve_export<<<(h->map->c.pool_cap + 255) / 256, 256, 0, s>>>(h->map->c, h->d_blk_off, h->n_alloc, h->d_xyz);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(xyz_out, h->d_xyz, (size_t)n * 3 * 8, hipMemcpyDeviceToHost));
+    }
+    if (n_written) *n_written = n;
     return PTL_OK;
 }
 

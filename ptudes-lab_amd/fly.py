@@ -223,6 +223,48 @@ class MapCarver:
         self.carver.close()
 
 
+class SweepDiffer:
+    """What a localised sweep sees that the map does not, and what the map holds that the sweep no longer sees: a
+    core.Caster on a map handle (a core.Icp, or a MapAccumulator's), fed posed sweeps.  cfg: radius, step, min_range, max_range (defaults:
+    the library's for the map's voxel size) and `margin` of the class policy `core.cast_changes` (default: the voxel size) - all untuned.
+    The map handle's scan_cols must be the sweeps' W.  The map must not be updated while the differ lives"""
+    COLORS = np.array([(0, 0, 0, 255), (128, 128, 128, 255), (255, 48, 48, 255), (48, 96, 255, 255), (255, 208, 0, 255)], dtype=np.uint8)
+
+    def __init__(self, map_or_acc, lut=None, margin=None, **cfg):
+        icp = map_or_acc.icp if isinstance(map_or_acc, MapAccumulator) else map_or_acc
+        self.lut = lut if lut is not None else getattr(map_or_acc, "lut", None)
+        self.margin = float(icp.cfg.voxel_size if margin is None else margin)
+        if not self.margin > 0.0:
+            raise ValueError(f"margin = {margin}: must be positive")
+        self.caster = core.Caster(icp, **cfg)
+        self.last = None  # the core.CastSweep of the last update
+
+    def _classes(self, sweep):
+        self.last = sweep
+        classes = sweep.changes(self.margin)
+        return classes, core.change_counts(classes)
+
+    def update(self, scan, traj):
+        """one PosedScan or packets.PacketScan (a range image of this differ's LUT), posed by `traj` (a core.Traj) at its column timestamps.
+        Returns (the class image (H, W) u8 of `core.cast_changes`, {class name: pixels})"""
+        if self.lut is None:
+            raise ValueError("a range image needs the LUT this differ was made with")
+        range_mm = scan.range_mm if hasattr(scan, "range_mm") else scan.range
+        return self._classes(self.caster.cast_range(traj, self.lut, range_mm, np.asarray(scan.timestamp, dtype=np.float64) * 1e-9))
+
+    def update_xyz(self, xyz, H, W, traj, col_ts=None):
+        """the same for a sweep of H x W points in the sensor frame, (0, 0, 0) = no return"""
+        return self._classes(self.caster.cast_xyz(traj, xyz, H, W, col_ts))
+
+    @classmethod
+    def image(cls, classes):
+        """the class image as (H, W, 4) RGBA, one fixed colour per class: none black, agree grey, new red, gone blue, unmapped yellow"""
+        return cls.COLORS[np.asarray(classes, dtype=np.uint8)]
+
+    def close(self):
+        self.caster.close()
+
+
 class MapPainter:
     """The second pass over the sweeps that built `acc`'s map with a channel field each: a core.Painter on the accumulator's
     map handle, fed the way the accumulator was.  The map must not be updated while the painter lives"""
