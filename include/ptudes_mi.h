@@ -1174,6 +1174,102 @@ int ptl_cast_posed_xyz(ptl_cast *c, ptl_traj *t, const float *xyz, int32_t H, in
  * the map's point count: PTL_ERR_CAPACITY naming the count, nothing written. */
 int ptl_cast_points(ptl_cast *c, double *xyz_out, int64_t max_points, int64_t *n_written);
 
+/* ------------------------------------------------------------------------------------------------
+ * Revisited places: polar height descriptors of sweeps, matched on the device at every heading (the Scan Context idea of Kim &
+ * Kim, IROS 2018, in an integer form; no reference counterpart).  A descriptor is a polar grid of n_ring x n_sector cells around the sensor
+ * holding the greatest height level per cell; a turn about z is a cyclic shift of the sector axis.  The handle is a database of descriptors
+ * and compares a query with EVERY stored descriptor at EVERY shift: no ring-key pre-filter, no tree.  Past the binning comparisons everything
+ * is an integer; a maximum has no order of evaluation, so a descriptor is an exact function of the SET of points and the tables, and a match
+ * an exact function of the stored bytes - neither depends on the order of the points, the lane mapping or the launch geometry.
+ * Parameters: n_ring R in 1 .. 64; n_sector S in 4 .. 64; 0 < min_radius < max_radius / R; z_step > 0; z_min finite; capacity (entries) in
+ * 1 .. 2^20; max_points_per_scan in 1 .. 2^24.  ptl_place_default_cfg gives R = 20, S = 60, min_radius 1, max_radius 80, z_min -2,
+ * z_step 0.0625, capacity 4096, max_points_per_scan 2^20: a caller's choice that nothing here has tuned - nobody has run this on a real
+ * recording.
+ * Tables, made once on the host at create and uploaded (ptl_place_tables returns them; they are part of the input to the definition):
+ * ring_edge2[0] = min_radius min_radius, ring_edge2[i] = e e with e = max_radius (double)i / (double)R (i = 1 .. R);
+ * sector_dir[2 j], [2 j + 1] = cos t_j, sin t_j with t_j = 2 pi (double)j / (double)S.
+ * Descriptor of a sweep.  All arithmetic fp64 in the written order, without contraction; float32 input is converted first.  A point p is the
+ * LUT's sensor-frame point of a pixel as ptl_lut_apply gives it, or a row of an xyz array.
+ *   return   a range of 0, or an xyz row of (0, 0, 0), is no return (n_no_return); a non-finite coordinate drops the point (n_non_finite).
+ *   level    rot9 (nullable, row-major, every entry finite): p' = (r0 x + r1 y) + r2 z per row.  Null and the identity give the same bytes.
+ *   ring     rho2 = x x + y y; the ring is the largest i with ring_edge2[i] <= rho2; a point is kept iff ring_edge2[0] <= rho2 &&
+ *            rho2 < ring_edge2[R] (a NaN fails it), else it is dropped (n_out_of_radius).  No square root.
+ *   sector   c_j = ex_j y - ey_j x (two rounded products, one subtraction); the sector is the smallest j with c_j >= 0 &&
+ *            c_((j + 1) mod S) < 0; no such j drops the point (n_no_sector).  No arctangent.
+ *   level    h = (z - z_min) / z_step; a point is kept iff h >= 0 (a NaN fails it), else dropped (n_below); h >= 254.0 gives 255, compared
+ *            in fp64 before any integer conversion; otherwise the level is 1 + (int)h.
+ *   cell     the MAXIMUM level of its points, 0 if it has none.
+ * Layout: sector-major u8, desc[j][r], column stride Rpad = R rounded up to 4, pad bytes 0; an entry is S Rpad bytes with a ptl_place_info.
+ * Distance: dist(q, c, s) = sum over j < S, r < R of |q[(j + s) mod S][r] - c[j][r]| (u32, at most 64 64 255).  The best shift of a pair is
+ * the s with the smallest dist, ties to the smaller s.  Convention: a query whose points are the entry's points turned by +s 2 pi / S about z
+ * has best shift s and dist 0 up to binning; the rigid guess that takes query coordinates into the entry's frame is Rz(-2 pi s / S).
+ * Launch constants (ptl_build_info has no free slot): 256 threads per workgroup; the match gives a lane to each shift, a wavefront to four
+ * entries at a time. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(ptl_place_cfg) as the caller knows it (PTL_CFG_INIT) */
+    uint32_t abi_version;
+    double min_radius, max_radius, z_min, z_step;
+    int64_t max_points_per_scan; /* sizes the handle's sweep staging */
+    int32_t n_ring, n_sector;
+    int32_t capacity;            /* entries */
+    int32_t reserved;
+} ptl_place_cfg;
+typedef struct {
+    int64_t n_points;                                                /* pixels / rows of the sweep */
+    int64_t n_no_return, n_non_finite, n_out_of_radius, n_no_sector, n_below; /* dropped, in that order of the tests */
+    int64_t n_used;                                                  /* points that reached a cell */
+    int64_t n_cells, sum_levels;                                     /* non-zero cells and the sum of their levels */
+} ptl_place_info;
+typedef struct {
+    int64_t best_query;      /* ptl_place_match: the query as given; ptl_place_match_all: the query of the best pair, -1 when none */
+    int64_t best_entry;      /* the entry with the smallest dist, ties to the smaller index (match_all: then to the smaller query); -1 when none */
+    int64_t n_compared;      /* (query, entry) pairs compared */
+    uint32_t best_dist;
+    int32_t best_shift;
+    double device_ms;        /* HIP-event time of this call's device work */
+} ptl_place_result;
+typedef struct ptl_place ptl_place; /* a database of descriptors: its own stream, tables, sweep staging, the entries, their infos, a query slot */
+/* the library's sizeof(ptl_place_cfg) (ptl_sizeof_cfg keeps its six ids) */
+int64_t ptl_place_sizeof_cfg(void);
+/* the defaults above; cfg->struct_size / abi_version must hold the caller's values (PTL_CFG_INIT) - a mismatch is refused with PTL_ERR_ARG and
+ * nothing is written */
+int ptl_place_default_cfg(ptl_place_cfg *cfg);
+/* an empty database on that device.  Checked before any HIP call, refused with the numbers (PTL_ERR_ARG): null cfg / out, a cfg of another
+ * size or version, each parameter bound above. */
+int ptl_place_create(int32_t device_id, const ptl_place_cfg *cfg, ptl_place **out);
+int ptl_place_destroy(ptl_place *p);
+/* no entries, a zero query slot; parameters and tables stay */
+int ptl_place_clear(ptl_place *p);
+/* the number of entries */
+int ptl_place_size(ptl_place *p, int64_t *n_entries);
+/* the tables as uploaded: ring_edge2[R + 1], sector_dir[2 S] (both nullable) */
+int ptl_place_tables(ptl_place *p, double *ring_edge2, double *sector_dir);
+/* HIP-event time of the describe calls so far and their number (both nullable); reset != 0 zeroes both afterwards */
+int ptl_place_profile(ptl_place *p, double *describe_ms, int64_t *n_describes, int32_t reset);
+/* the descriptor of one sweep.  It always lands in the handle's QUERY SLOT; with keep = 1 it is also appended and *index is the entry count
+ * before, with keep = 0 *index = -1 (index, info nullable).  A full database with keep = 1: PTL_ERR_CAPACITY with the numbers, nothing is
+ * appended, the query slot and *info are still written.  Refused before any HIP call with the numbers: a LUT on another device or with more
+ * than max_points_per_scan pixels, n outside 0 .. max_points_per_scan (PTL_ERR_CAPACITY above it), a dtype that is neither PTL_F32 nor
+ * PTL_F64, a non-finite entry of rot9. */
+int ptl_place_describe_range(ptl_place *p, ptl_lut *lut, const uint32_t *range_mm, const double *rot9, int32_t keep, int64_t *index,
+                             ptl_place_info *info);
+int ptl_place_describe_xyz(ptl_place *p, const void *xyz, int dtype, int64_t n, const double *rot9, int32_t keep, int64_t *index,
+                           ptl_place_info *info);
+/* query (an entry index, or -1 for the query slot) against every entry c in [first, last]: dist_out[c - first], shift_out[c - first] its best
+ * shift and distance (both nullable), *result (nullable) the best entry.  last < first is an empty range and PTL_OK (best_entry = -1);
+ * otherwise 0 <= first <= last < entries, else PTL_ERR_ARG with the numbers. */
+int ptl_place_match(ptl_place *p, int64_t query, int64_t first, int64_t last, uint32_t *dist_out, int32_t *shift_out, ptl_place_result *result);
+/* the loop-closure batch form: for every entry i in [q_first, q_last] the best (dist, j) over the entries j <= i - min_gap with its shift, ties
+ * to the smaller j, then to the smaller shift; entry_out[i - q_first] = -1 (dist 0, shift 0) when no j qualifies.  Three integers per query
+ * cross the bus (every array nullable).  min_gap >= 0; q_last < q_first is an empty range and PTL_OK. */
+int ptl_place_match_all(ptl_place *p, int64_t q_first, int64_t q_last, int64_t min_gap, int32_t *entry_out, uint32_t *dist_out,
+                        int32_t *shift_out, ptl_place_result *result);
+/* entries [first, last]: desc_out (S Rpad bytes each) and info_out (both nullable); last < first reads nothing */
+int ptl_place_read(ptl_place *p, int64_t first, int64_t last, uint8_t *desc_out, ptl_place_info *info_out);
+/* appends n stored descriptors with their infos (a database saved and restored).  Refused before any HIP call: a non-zero pad byte
+ * (PTL_ERR_ARG naming entry, sector and byte), entries + n above the capacity (PTL_ERR_CAPACITY with the numbers); nothing is appended then. */
+int ptl_place_load(ptl_place *p, int64_t n, const uint8_t *desc, const ptl_place_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,30 @@ class CastResult(C.Structure):
                 ("min_range", C.c_double), ("max_range", C.c_double), ("device_ms", C.c_double)]
 
 
+class PlaceCfg(_Cfg):
+    """ptl_place_cfg (include/ptudes_mi.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("min_radius", C.c_double), ("max_radius", C.c_double),
+                ("z_min", C.c_double), ("z_step", C.c_double), ("max_points_per_scan", C.c_int64), ("n_ring", C.c_int32), ("n_sector", C.c_int32),
+                ("capacity", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PlaceInfo(C.Structure):
+    """ptl_place_info: what became of a sweep's points, and the descriptor's non-zero cells"""
+    _fields_ = [("n_points", C.c_int64), ("n_no_return", C.c_int64), ("n_non_finite", C.c_int64), ("n_out_of_radius", C.c_int64),
+                ("n_no_sector", C.c_int64), ("n_below", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int64), ("sum_levels", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PLACE_INFO_FIELDS = tuple(k for k, _ in PlaceInfo._fields_)  # the columns of an (n, 9) int64 array of infos
+
+
+class PlaceResult(C.Structure):
+    _fields_ = [("best_query", C.c_int64), ("best_entry", C.c_int64), ("n_compared", C.c_int64), ("best_dist", C.c_uint32),
+                ("best_shift", C.c_int32), ("device_ms", C.c_double)]
+
+
 class PoseSearchCfg(_Cfg):
     """ptl_pose_search_cfg (include/ptudes_mi.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("abi_version", C.c_uint32), ("max_dist", C.c_double), ("n_thresholds", C.c_int32),
@@ -384,6 +408,22 @@ PROTOTYPES = {
     "ptl_cast_posed_xyz": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.c_int32, C.c_int32, c_d_p, C.POINTER(CastResult), C.POINTER(C.c_uint8), c_d_p,
                                      c_d_p, C.POINTER(C.c_int32)]),
     "ptl_cast_points": (C.c_int, [_vp, c_d_p, C.c_int64, c_i64_p]),
+    # revisited places: polar height descriptors matched at every heading (include/ptudes_mi.h)
+    "ptl_place_sizeof_cfg": (C.c_int64, []),
+    "ptl_place_default_cfg": (C.c_int, [C.POINTER(PlaceCfg)]),
+    "ptl_place_create": (C.c_int, [C.c_int32, C.POINTER(PlaceCfg), _vpp]),
+    "ptl_place_destroy": (C.c_int, [_vp]),
+    "ptl_place_clear": (C.c_int, [_vp]),
+    "ptl_place_size": (C.c_int, [_vp, c_i64_p]),
+    "ptl_place_tables": (C.c_int, [_vp, c_d_p, c_d_p]),
+    "ptl_place_profile": (C.c_int, [_vp, c_d_p, c_i64_p, C.c_int32]),
+    "ptl_place_describe_range": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), c_d_p, C.c_int32, c_i64_p, C.POINTER(PlaceInfo)]),
+    "ptl_place_describe_xyz": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, c_d_p, C.c_int32, c_i64_p, C.POINTER(PlaceInfo)]),
+    "ptl_place_match": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(PlaceResult)]),
+    "ptl_place_match_all": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                      C.POINTER(PlaceResult)]),
+    "ptl_place_read": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(PlaceInfo)]),
+    "ptl_place_load": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_uint8), C.POINTER(PlaceInfo)]),
     "ptl_batch_gn_phases": (C.c_int, [_vp, c_i64_p]),
     "ptl_batch_icp": (C.c_int, [_vp, C.c_int32, _vpp]),
     "ptl_batch_profile": (C.c_int, [_vp, C.c_int, c_d_p, c_i64_p, C.c_int]),

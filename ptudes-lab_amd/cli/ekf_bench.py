@@ -607,6 +607,104 @@ def _bag_grid(bags, info, start_scan, end_scan, knots, grid, device_id=0):
     return counts
 
 
+LOOP_OPTIONS = [
+    click.option("--find-loops", is_flag=True,
+                 help="after the run, describe a sweep every --loop-spacing metres of the filter's trajectory (polar height descriptors, GPU), "
+                      "compare every one with all earlier ones at every heading, verify the best pairs by registration and print the accepted "
+                      "loops with the odometry's discrepancy at each; every threshold is the caller's and untuned"),
+    click.option("--loop-spacing", type=float, default=None, help="metres of travel between described sweeps (default 2; untuned)"),
+    click.option("--loop-min-gap", type=int, default=None, help="a sweep is only compared with those at least this many described sweeps "
+                                                                "before it (default 50; untuned)"),
+    click.option("--loop-max-cell-dist", type=float, default=None,
+                 help="policy: largest descriptor distance per occupied cell, dist / (cells_i + cells_j), of a pair worth verifying "
+                      "(default 20; untuned)"),
+    click.option("--loop-min-fraction", type=float, default=None,
+                 help="policy: share of a sweep's points that must lie within a voxel of the other sweep's after registration (default 0.5; untuned)"),
+    click.option("--save-loops", required=False, type=click.Path(dir_okay=False), help="write every verified pair to this .csv"),
+    click.option("--save-places", required=False, type=click.Path(dir_okay=False),
+                 help="write the described sweeps' descriptors with their poses and stamps to this .npz (what `localize --places` reads); "
+                      "works without --find-loops too"),
+]
+
+
+def loop_click_options(f):
+    for opt in reversed(LOOP_OPTIONS):
+        f = opt(f)
+    return f
+
+
+def loop_options(find_loops, loop_spacing, loop_min_gap, loop_max_cell_dist, loop_min_fraction, save_loops, save_places):
+    """the options of --find-loops / --save-places checked before any device is touched: None without either, else a dict with the policy's
+    (untuned) defaults filled in"""
+    given = {"--loop-min-gap": loop_min_gap, "--loop-max-cell-dist": loop_max_cell_dist, "--loop-min-fraction": loop_min_fraction,
+             "--save-loops": save_loops}
+    if not find_loops:
+        for name, v in given.items():
+            if v is not None:
+                raise click.ClickException(f"{name} belongs to --find-loops")
+        if not save_places:
+            if loop_spacing is not None:
+                raise click.ClickException("--loop-spacing belongs to --find-loops or --save-places")
+            return None
+    spacing = 2.0 if loop_spacing is None else loop_spacing
+    if not (spacing >= 0.0 and np.isfinite(spacing)):
+        raise click.ClickException(f"--loop-spacing {spacing:g}: must not be negative")
+    if loop_min_gap is not None and loop_min_gap < 0:
+        raise click.ClickException(f"--loop-min-gap {loop_min_gap}: must not be negative")
+    if loop_max_cell_dist is not None and not loop_max_cell_dist >= 0.0:
+        raise click.ClickException(f"--loop-max-cell-dist {loop_max_cell_dist:g}: must not be negative")
+    if loop_min_fraction is not None and not 0.0 <= loop_min_fraction <= 1.0:
+        raise click.ClickException(f"--loop-min-fraction {loop_min_fraction:g}: must be in [0, 1]")
+    if save_loops and not str(save_loops).endswith(".csv"):
+        raise click.ClickException(f"--save-loops {save_loops}: the loops are written to a .csv file")
+    if save_places and not str(save_places).endswith(".npz"):
+        raise click.ClickException(f"--save-places {save_places}: the places are written to a .npz file")
+    return dict(find=bool(find_loops), spacing=spacing, min_gap=50 if loop_min_gap is None else loop_min_gap,
+                max_cell_dist=20.0 if loop_max_cell_dist is None else loop_max_cell_dist,
+                min_fraction=0.5 if loop_min_fraction is None else loop_min_fraction, save=save_loops, places=save_places)
+
+
+def loop_report(finder, loops_opt):
+    """--find-loops / --save-places once every sweep has been added: prints the loops' block and writes the files"""
+    from .. import fly
+    from ..utils import save_places
+    print(f"Places: {len(finder.poses)} sweeps described, one per {loops_opt['spacing']:g} m")
+    if loops_opt["find"]:
+        loops = finder.find(min_gap=loops_opt["min_gap"], max_cell_dist=loops_opt["max_cell_dist"], min_fraction=loops_opt["min_fraction"])
+        print("\n".join(fly.loop_lines(loops)))
+        if loops_opt["save"]:
+            fly.save_loops_csv(loops_opt["save"], loops, finder.stamps)
+            print(f"Loops saved to: {loops_opt['save']}")
+    if loops_opt["places"]:
+        save_places(loops_opt["places"], finder.index, finder.poses, finder.stamps)
+        print(f"Places saved to: {loops_opt['places']}")
+
+
+def _run_loops(seq, first, rows_t, rows_p, loops_opt, device_id=0):
+    """--find-loops of a synthetic sequence: sweep first + k at the k-th pose of the run"""
+    from .. import fly
+    finder = fly.LoopFinder(spacing=loops_opt["spacing"], device_id=device_id, max_points_per_scan=seq.H * seq.W)
+    try:
+        for k, (t, p) in enumerate(zip(rows_t, rows_p)):
+            finder.add(seq.scan(first + k), p, t)
+        loop_report(finder, loops_opt)
+    finally:
+        finder.close()
+
+
+def _bag_loops(bags, info, start_scan, end_scan, rows_t, rows_p, loops_opt, device_id=0):
+    """... of a raw packet bag: a pass over the bag through the package's packet feed, sweep k at the k-th pose of the run"""
+    from .. import fly
+    lut = fly.sensor_lut(info, use_extrinsics=True, device_id=device_id)
+    finder = fly.LoopFinder(spacing=loops_opt["spacing"], lut=lut, device_id=device_id, max_points_per_scan=lut.H * lut.W)
+    try:
+        fly.loops_packet_bag(finder, bags, info, rows_t, rows_p, start_scan, end_scan, device_id=device_id)
+        loop_report(finder, loops_opt)
+    finally:
+        finder.close()
+        lut.close()
+
+
 def score_options(map_score, score_radius, voxel_size):
     """the keyword arguments of Icp.map_score for --map-score / --score-radius, or None; refusals before any device is touched"""
     if score_radius is not None and not map_score:
@@ -670,6 +768,7 @@ def score_options(map_score, score_radius, voxel_size):
 @compare_click_options
 @carve_click_options
 @grid_click_options
+@loop_click_options
 def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int, end_scan: Optional[int],
                       plot: Optional[str], use_imu_prediction: bool, use_gt_guess: bool, gt_file: Optional[str], beams: int,
                       save_kitti_poses: Optional[str], save_nc_gt_poses: Optional[str], kiss_min_range: float,
@@ -684,7 +783,10 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                       save_grid: Optional[str] = None, grid_cell: Optional[float] = None, grid_band: Optional[str] = None,
                       grid_margin: Optional[float] = None, grid_max_range: Optional[float] = None, grid_bounds: Optional[str] = None,
                       grid_min_hits: Optional[int] = None, grid_min_fraction: Optional[float] = None,
-                      save_grid_counts: Optional[str] = None) -> None:
+                      save_grid_counts: Optional[str] = None, find_loops: bool = False, loop_spacing: Optional[float] = None,
+                      loop_min_gap: Optional[int] = None, loop_max_cell_dist: Optional[float] = None,
+                      loop_min_fraction: Optional[float] = None, save_loops: Optional[str] = None,
+                      save_places: Optional[str] = None) -> None:
     """EKF with Ouster IMUs and scan KissICP poses updates (smoothing of the KissICP trajectory)."""
     if synthetic_size is not None and synthetic is None:
         raise click.ClickException("--synthetic-size belongs to --synthetic")
@@ -699,7 +801,9 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
                             want_map)
     gridding = grid_options(save_grid, grid_cell, grid_band, grid_margin, grid_max_range, grid_bounds, grid_min_hits, grid_min_fraction,
                             save_grid_counts)
-    want_sweeps = want_map or gridding is not None  # (the grid is a product of the same kind: it needs the sweeps' column times)
+    looping = loop_options(find_loops, loop_spacing, loop_min_gap, loop_max_cell_dist, loop_min_fraction, save_loops, save_places)
+    # (the grid and the places are products of the same kind: a second pass over the sweeps)
+    want_sweeps = want_map or gridding is not None or looping is not None
     if want_sweeps and map_from == "smoothed" and not save_smoothed_poses:
         raise click.ClickException("--map-from smoothed needs the smoother (--save-smoothed-poses)")
     if imu_deskew and (synthetic is None or plot):
@@ -720,7 +824,8 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
         native_bag = bool(file) and (native_packets or not have_sdk) and ((Path(file).is_file() and Path(file).suffix == ".bag") or Path(file).is_dir())
         if not native_bag:
             raise click.ClickException("--save-map needs --synthetic or a raw packet .bag read by the package's own decoder (--native-packets): "
-                                       "the sweep times of other recordings are not decoded here (the same holds for --map-score and --save-grid)")
+                                       "the sweep times of other recordings are not decoded here (the same holds for --map-score, --save-grid, --find-loops "
+                                       "and --save-places)")
     bags = None
     if synthetic is None and (native_packets or not have_sdk):
         # the package's own feed (packets.py): raw payloads from the bag(s), batched on the host, decoded on the device
@@ -868,6 +973,12 @@ def ptudes_ekf_ouster(file: Optional[str], meta: Optional[str], start_scan: int,
             grid_report(_run_grid(seq, start_scan, knots, gridding), gridding)
         else:
             grid_report(_bag_grid(bags, info, start_scan, end_scan, knots, gridding), gridding)
+    if looping is not None:
+        # revisited places along the filter's trajectory: sweep k of the run at its k-th pose
+        if seq is not None:
+            _run_loops(seq, start_scan, list(res_t), list(res_poses), looping)
+        else:
+            _bag_loops(bags, info, start_scan, end_scan, list(res_t), list(res_poses), looping)
     tm = out["timings"]
     if tm["n_imu"] and tm["n_corr"]:  # reference :590-595
         print("\nTimings:")

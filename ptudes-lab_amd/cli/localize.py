@@ -5,6 +5,8 @@ the map's points and poses the run went through.  Every keyframe, turned through
 is searched for among all of them on the GPU (`Icp.pose_hits`), the best `--top` are refined by the registration's own Gauss-Newton loop
 (`Icp.align`) and scored again.  The following sweeps are tracked from the previous fixes and searched for again when fewer than
 `--min-fraction` of their points lie within a voxel size of the map.  The map is never added to.
+With `--places FILE.npz` (the mapping run's `--save-places`) the candidates are instead the `--place-top` places whose polar height descriptor
+matches the sweep's best, each at its matched heading; `--keyframes` and `--yaws` are then not given.
 SOURCE is a raw packet .bag (or a directory of bags) read by the package's own packet decoder, with `-m META`; `--synthetic SEED` runs on the
 synthetic sequence instead.  The sweeps' poses are written with `--save-nc-gt-poses` / `--save-kitti-poses`."""
 from typing import Optional
@@ -15,9 +17,11 @@ import numpy as np
 from .ekf_bench import MAP_VOXEL_SIZE, parse_synthetic_size
 
 DEFAULTS = dict(yaws=16, top=4, min_fraction=0.5, query_voxel=1.0)  # a caller's policy, untuned (fly.MapLocalizer)
+DEFAULT_PLACE_TOP = 4  # places tried per search with --places, untuned (fly.PlaceLocalizer)
 
 
-def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan):
+def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan, places=None,
+                     place_top=None):
     """the options checked before any device is touched: a dict with the defaults filled in"""
     import os
     if not map_path:
@@ -26,11 +30,26 @@ def localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fract
         raise click.ClickException(f"--map {map_path}: no such file")
     if not str(map_path).endswith((".ply", ".npy")):
         raise click.ClickException(f"--map {map_path}: expected a .ply or .npy cloud")
-    if not keyframes:
-        raise click.ClickException("--keyframes POSES.csv is needed: the poses of the mapping run (its --save-nc-gt-poses)")
-    if not os.path.isfile(keyframes):
-        raise click.ClickException(f"--keyframes {keyframes}: no such file")
-    out = dict(DEFAULTS, map=map_path, keyframes=keyframes, spacing=keyframe_spacing, start_scan=start_scan, end_scan=end_scan)
+    if places:
+        # the start poses come from a places file instead of keyframes x yaws
+        for opt, v in (("--keyframes", keyframes), ("--yaws", yaws), ("--keyframe-spacing", keyframe_spacing)):
+            if v is not None:
+                raise click.ClickException(f"{opt} does not go with --places: the places file carries the poses, the match their headings")
+        if not os.path.isfile(places):
+            raise click.ClickException(f"--places {places}: no such file")
+        if not str(places).endswith(".npz"):
+            raise click.ClickException(f"--places {places}: expected the .npz of a mapping run's --save-places")
+        if place_top is not None and place_top < 1:
+            raise click.ClickException(f"--place-top {place_top}: at least one place is tried")
+    else:
+        if place_top is not None:
+            raise click.ClickException("--place-top belongs to --places")
+        if not keyframes:
+            raise click.ClickException("--keyframes POSES.csv is needed: the poses of the mapping run (its --save-nc-gt-poses)")
+        if not os.path.isfile(keyframes):
+            raise click.ClickException(f"--keyframes {keyframes}: no such file")
+    out = dict(DEFAULTS, map=map_path, keyframes=keyframes, spacing=keyframe_spacing, start_scan=start_scan, end_scan=end_scan, places=places,
+               place_top=DEFAULT_PLACE_TOP if place_top is None else place_top)
     for name, opt, v in (("yaws", "--yaws", yaws), ("top", "--top", top), ("min_fraction", "--min-fraction", min_fraction),
                          ("query_voxel", "--query-voxel", query_voxel)):
         if v is not None:
@@ -92,6 +111,10 @@ def fix_knots(t, fix):
               help=f"hit fraction below which a tracked sweep is searched for again (default {DEFAULTS['min_fraction']}, untuned)")
 @click.option("--query-voxel", type=float, default=None,
               help=f"side of the voxels that thin a sweep to one point each, metres (default {DEFAULTS['query_voxel']}, untuned)")
+@click.option("--places", required=False, type=click.Path(dir_okay=False),
+              help="places of the mapping run (its --save-places .npz): the start poses are the best-matching places at the matched heading "
+                   "instead of keyframes x yaws; excludes --keyframes")
+@click.option("--place-top", type=int, default=None, help=f"--places: places tried per search (default {DEFAULT_PLACE_TOP}, untuned)")
 @click.option("--start-scan", type=int, default=0, help="first sweep to localise (0-based)")
 @click.option("--end-scan", type=int, help="last sweep to localise (inclusive)")
 @click.option("--save-nc-gt-poses", required=False, type=click.Path(exists=False, dir_okay=False),
@@ -111,10 +134,10 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
                     top: Optional[int], min_fraction: Optional[float], query_voxel: Optional[float], start_scan: int,
                     end_scan: Optional[int], save_nc_gt_poses: Optional[str], save_kitti_poses: Optional[str], changes: bool,
                     cast_radius: Optional[float], change_margin: Optional[float], cast_max_range: Optional[float],
-                    save_changes: Optional[str]) -> None:
+                    save_changes: Optional[str], places: Optional[str] = None, place_top: Optional[int] = None) -> None:
     """Poses of the sweeps of SOURCE in the frame of a saved map."""
     diff_cfg = change_options(changes, cast_radius, change_margin, cast_max_range, save_changes)
-    opts = localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan)
+    opts = localize_options(map_path, keyframes, yaws, keyframe_spacing, top, min_fraction, query_voxel, start_scan, end_scan, places, place_top)
     if synthetic_size is not None and synthetic is None:
         raise click.ClickException("--synthetic-size belongs to --synthetic")
     H, W = parse_synthetic_size(synthetic_size)
@@ -131,9 +154,19 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
         if not meta:
             raise click.ClickException("File not found, please specify a metadata file with `-m`")
     from ..utils import load_map_ply, read_newer_college_gt, save_poses_kitti_format, save_poses_nc_gt_format
-    kf = read_newer_college_gt(opts["keyframes"])
-    if not kf:
-        raise click.ClickException(f"--keyframes {opts['keyframes']}: no pose in the file")
+    kf = place_data = None
+    if opts["places"]:
+        from ..utils import load_places
+        try:
+            place_data = load_places(opts["places"])
+        except ValueError as e:
+            raise click.ClickException(f"--places: {e}")
+        if not len(place_data["poses"]):
+            raise click.ClickException(f"--places {opts['places']}: no place in the file")
+    else:
+        kf = read_newer_college_gt(opts["keyframes"])
+        if not kf:
+            raise click.ClickException(f"--keyframes {opts['keyframes']}: no pose in the file")
     map_pts = np.ascontiguousarray(load_map_ply(opts["map"]), dtype=np.float64).reshape(-1, 3)
     from .. import fly
 
@@ -163,11 +196,17 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
             finally:
                 feed.close()
 
-    loc = fly.MapLocalizer(map_pts, [p for _, p in kf], n_yaw=opts["yaws"], spacing=opts["spacing"], top=opts["top"],
-                           min_fraction=opts["min_fraction"], query_voxel=opts["query_voxel"], voxel_size=MAP_VOXEL_SIZE,
-                           max_points_per_scan=max(points_per_sweep, 1 << 16), **(dict(scan_cols=sweep_hw[1]) if diff_cfg else {}))
+    common = dict(top=opts["top"], min_fraction=opts["min_fraction"], query_voxel=opts["query_voxel"], voxel_size=MAP_VOXEL_SIZE,
+                  max_points_per_scan=max(points_per_sweep, 1 << 16), **(dict(scan_cols=sweep_hw[1]) if diff_cfg else {}))
+    if place_data is not None:
+        loc = fly.PlaceLocalizer(map_pts, place_data, place_top=opts["place_top"], **common)
+    else:
+        loc = fly.MapLocalizer(map_pts, [p for _, p in kf], n_yaw=opts["yaws"], spacing=opts["spacing"], **common)
     print(f"map: {opts['map']} ({len(map_pts)} points, voxel size {MAP_VOXEL_SIZE})")
-    print(f"keyframes: {opts['keyframes']} ({len(kf)} poses, {len(loc.kept)} kept) x {opts['yaws']} yaws = {len(loc.candidates)} candidates")
+    if place_data is not None:
+        print(f"places: {opts['places']} ({len(place_data['poses'])} places), the best {opts['place_top']} per search are the candidates")
+    else:
+        print(f"keyframes: {opts['keyframes']} ({len(kf)} poses, {len(loc.kept)} kept) x {opts['yaws']} yaws = {len(loc.candidates)} candidates")
     res_t, res_poses, fractions = [], [], []
     differ, totals = None, {}
     try:
@@ -203,7 +242,8 @@ def ptudes_localize(source: Optional[str], meta: Optional[str], synthetic: Optio
         if differ is not None:
             differ.close()
         loc.close()
-    header = f"localize: map {opts['map']}, keyframes {opts['keyframes']}\n(sweeps num: {len(res_poses)})"
+    start_from = f"places {opts['places']}" if opts["places"] else f"keyframes {opts['keyframes']}"
+    header = f"localize: map {opts['map']}, {start_from}\n(sweeps num: {len(res_poses)})"
     if save_kitti_poses:
         save_poses_kitti_format(save_kitti_poses, res_poses, header=header)
         print(f"Kitti poses saved to: {save_kitti_poses}")

@@ -974,6 +974,159 @@ class OccupancyGrid:
         L.check(L.lib().ptl_grid_clear(self._h))
 
 
+def place_cfg(**over):
+    """the _lib.PlaceCfg: the library's defaults (UNTUNED: nobody has run this on a real recording) with the given fields on top"""
+    cfg = L.PlaceCfg()
+    L.check(L.lib().ptl_place_default_cfg(C.byref(cfg)))
+    for k, v in over.items():
+        if k not in ("n_ring", "n_sector", "min_radius", "max_radius", "z_min", "z_step", "capacity", "max_points_per_scan"):
+            raise ValueError(f"ptl_place_cfg has no field {k!r}")
+        setattr(cfg, k, int(v) if k in ("n_ring", "n_sector", "capacity", "max_points_per_scan") else float(v))
+    return cfg
+
+
+def place_infos_array(infos):
+    """ctypes array of _lib.PlaceInfo -> (n, 9) int64, columns `_lib.PLACE_INFO_FIELDS`"""
+    return np.array([[getattr(i, k) for k in L.PLACE_INFO_FIELDS] for i in infos], dtype=np.int64).reshape(-1, len(L.PLACE_INFO_FIELDS))
+
+
+@dataclass
+class PlaceMatch:
+    """What `PlaceIndex.match` returns: per entry of [first, last] its best shift and distance (exact integers), and the best entry (-1 for
+    an empty range) by smallest distance, ties to the smaller index.  The rigid guess that takes the query's coordinates into entry c's frame
+    is `place_shift_pose(shift[c - first], n_sector)`"""
+    first: int
+    dist: np.ndarray       # (n,) uint32
+    shift: np.ndarray      # (n,) int32
+    best_entry: int
+    best_dist: int
+    best_shift: int
+    device_ms: float
+
+
+@dataclass
+class PlaceLoops:
+    """What `PlaceIndex.match_all` returns: for query entry first + k the best earlier entry[k] (-1: none qualified) at least min_gap entries
+    before it, with its distance and shift"""
+    first: int
+    min_gap: int
+    entry: np.ndarray      # (n,) int32
+    dist: np.ndarray       # (n,) uint32
+    shift: np.ndarray      # (n,) int32
+    n_compared: int
+    device_ms: float
+
+
+def place_shift_pose(shift, n_sector):
+    """Rz(-2 pi shift / n_sector) as a 4x4: takes the coordinates of a query matched at `shift` into the entry's frame"""
+    t = -2.0 * np.pi * float(shift) / float(n_sector)
+    T = np.eye(4)
+    T[0, 0], T[0, 1], T[1, 0], T[1, 1] = np.cos(t), -np.sin(t), np.sin(t), np.cos(t)
+    return T
+
+
+class PlaceIndex:
+    """Revisited places (include/ptudes_mi.h ptl_place_*): a database of polar height descriptors of sweeps on the device,
+    compared with a query at every heading.  Every output is an exact integer function of the points and the stored bytes.  The defaults of
+    the parameters are the library's and UNTUNED"""
+
+    def __init__(self, device_id=0, **cfg):
+        self.cfg = place_cfg(**cfg)
+        self._h = C.c_void_p()
+        L.check(L.lib().ptl_place_create(int(device_id), C.byref(self.cfg), C.byref(self._h)))
+        self.n_ring, self.n_sector = int(self.cfg.n_ring), int(self.cfg.n_sector)
+        self.r_pad = (self.n_ring + 3) // 4 * 4
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().ptl_place_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        n = C.c_int64()
+        L.check(L.lib().ptl_place_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def tables(self):
+        """(ring_edge2 (R + 1,), sector_dir (S, 2)) as the device uses them: part of the input to the definition"""
+        e, d = np.empty(self.n_ring + 1), np.empty((self.n_sector, 2))
+        L.check(L.lib().ptl_place_tables(self._h, L.dptr(e), L.dptr(d)))
+        return e, d
+
+    def profile(self, reset=False):
+        """(HIP-event ms of the describe calls so far, their number)"""
+        ms, n = C.c_double(), C.c_int64()
+        L.check(L.lib().ptl_place_profile(self._h, C.byref(ms), C.byref(n), 1 if reset else 0))
+        return ms.value, n.value
+
+    def describe(self, points, rot=None, keep=True):
+        """The descriptor of a sweep: `points` an (n, 3) float32 / float64 array in the sensor frame, or a pair (lut, range image).  rot: a
+        3x3 that levels the sweep (p' = rot p).  The descriptor lands in the query slot and, with keep, behind the last entry.  Returns
+        (index, _lib.PlaceInfo), index = -1 without keep; a full database raises (RuntimeError, the numbers in the text) and the query slot
+        still holds the descriptor"""
+        r9 = None if rot is None else L.as_f64(rot).reshape(9)
+        idx, info = C.c_int64(-1), L.PlaceInfo()
+        if isinstance(points, tuple):
+            lut, rng = points
+            r = np.ascontiguousarray(rng, dtype=np.uint32).reshape(-1)
+            if r.size != lut.H * lut.W:
+                raise ValueError("range image size mismatch")
+            rc = L.lib().ptl_place_describe_range(self._h, lut._h, r.ctypes.data_as(C.POINTER(C.c_uint32)), None if r9 is None else L.dptr(r9),
+                                                  1 if keep else 0, C.byref(idx), C.byref(info))
+        else:
+            x = np.asarray(points)
+            x = np.ascontiguousarray(x, dtype=np.float32 if x.dtype == np.float32 else np.float64).reshape(-1, 3)
+            rc = L.lib().ptl_place_describe_xyz(self._h, x.ctypes.data_as(C.c_void_p), L.PTL_F32 if x.dtype == np.float32 else L.PTL_F64, len(x),
+                                                None if r9 is None else L.dptr(r9), 1 if keep else 0, C.byref(idx), C.byref(info))
+        L.check(rc)
+        return int(idx.value), info
+
+    def match(self, query=-1, first=0, last=None):
+        """`query` (an entry index, -1: the query slot) against every entry of [first, last] (default: all) at every shift: a `PlaceMatch`"""
+        last = len(self) - 1 if last is None else int(last)
+        n = max(last - int(first) + 1, 0)
+        dist, shift, res = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32), L.PlaceResult()
+        L.check(L.lib().ptl_place_match(self._h, int(query), int(first), last, dist.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        shift.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)))
+        return PlaceMatch(int(first), dist, shift, int(res.best_entry), int(res.best_dist), int(res.best_shift), float(res.device_ms))
+
+    def match_all(self, min_gap, first=0, last=None):
+        """the loop-closure batch form: every entry of [first, last] (default: all) against the entries at least min_gap before it: a
+        `PlaceLoops`"""
+        last = len(self) - 1 if last is None else int(last)
+        n = max(last - int(first) + 1, 0)
+        entry, dist, shift = np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32)
+        res = L.PlaceResult()
+        L.check(L.lib().ptl_place_match_all(self._h, int(first), last, int(min_gap), entry.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            dist.ctypes.data_as(C.POINTER(C.c_uint32)), shift.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(res)))
+        return PlaceLoops(int(first), int(min_gap), entry, dist, shift, int(res.n_compared), float(res.device_ms))
+
+    def descriptors(self, first=0, last=None):
+        """(desc (n, S, Rpad) uint8, infos (n, 9) int64 with the columns `_lib.PLACE_INFO_FIELDS`) of the entries [first, last]"""
+        last = len(self) - 1 if last is None else int(last)
+        n = max(last - int(first) + 1, 0)
+        desc = np.zeros((n, self.n_sector, self.r_pad), dtype=np.uint8)
+        infos = (L.PlaceInfo * max(n, 1))()
+        L.check(L.lib().ptl_place_read(self._h, int(first), last, desc.ctypes.data_as(C.POINTER(C.c_uint8)), infos))
+        return desc, place_infos_array(infos[:n])
+
+    def load(self, desc, infos):
+        """appends stored descriptors (n, S, Rpad) uint8 with their infos (n, 9) int64; a non-zero pad byte is refused (ValueError)"""
+        d = np.ascontiguousarray(desc, dtype=np.uint8)
+        if d.ndim != 3 or d.shape[1:] != (self.n_sector, self.r_pad):
+            raise ValueError(f"descriptors of shape {d.shape}: this index holds (n, {self.n_sector}, {self.r_pad})")
+        a = np.ascontiguousarray(infos, dtype=np.int64).reshape(-1, len(L.PLACE_INFO_FIELDS))
+        if len(a) != len(d):
+            raise ValueError(f"{len(d)} descriptors with {len(a)} infos")
+        L.check(L.lib().ptl_place_load(self._h, len(d), d.ctypes.data_as(C.POINTER(C.c_uint8)), a.ctypes.data_as(C.POINTER(L.PlaceInfo))))
+
+    def clear(self):
+        """no entries; parameters and tables stay"""
+        L.check(L.lib().ptl_place_clear(self._h))
+
+
 def rgba_word(rgba):
     """(..., 4) uint8 R, G, B, A -> the uint32 words the renderer's keys carry (R the lowest byte)"""
     a = np.ascontiguousarray(rgba, dtype=np.uint8)

@@ -16,6 +16,7 @@
 #include "cast_kernels.h"
 #include "grid_kernels.h"
 #include "paint_kernels.h"
+#include "place_kernels.h"
 #include "pose_kernels.h"
 #include "hip_own.h"
 
@@ -4010,6 +4011,303 @@ extern "C" int ptl_paint_read(ptl_paint* h, ptl_paint_result* result, double* xy
         HIPCHK(hipMemcpy(count_out, h->d_count, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     if (given && n_written) *n_written = n;
+    return PTL_OK;
+}
+
+// ================================================================================================ revisited places
+// The definition is in include/ptudes_mi.h, the kernels in place_kernels.h.  Everything is checked on the host before the first HIP call.  The
+// handle owns its stream, events, both tables, one sweep's staging, the u32 cell grid of a describe, the entries with their infos (the query
+// slot is entry number `capacity`) and the outputs of a match.
+struct ptl_place {
+    int device_id = 0;             // (first member, as in ptl_traj)
+    int64_t n_entries = 0;
+    ptl_place_cfg cfg;
+    int Rpad = 0, RD = 0;          // column stride in bytes and in dwords
+    size_t entry_bytes = 0;
+    double describe_ms = 0;
+    int64_t n_describes = 0;
+    std::vector<double> ring_edge2, sector_dir;
+    Stream stream;
+    Event e0, e1;
+    double* d_tab = nullptr;       // ring_edge2[R + 1], sector_dir[2 S]
+    void* d_raw = nullptr;         // one sweep of the caller's: max_points_per_scan rows of f64 xyz at most
+    unsigned* d_grid = nullptr;    // [S Rpad]
+    unsigned long long* d_counts = nullptr;  // [PLACE_COUNTERS], then the best key of a match
+    unsigned char* d_desc = nullptr;         // [capacity + 1] entries
+    PlaceInfoDev* d_info = nullptr;          // [capacity + 1]
+    unsigned* d_dist = nullptr;    // [capacity] each: the outputs of a match
+    int *d_shift = nullptr, *d_entry = nullptr;
+    DevOwner mem;
+};
+static_assert(sizeof(PlaceInfoDev) == sizeof(ptl_place_info), "the device's info record is ptl_place_info");
+#define PLACE_MAX_CAPACITY ((int64_t)1 << 20)
+#define PLACE_MAX_POINTS ((int64_t)1 << 24)
+extern "C" int64_t ptl_place_sizeof_cfg(void) { return (int64_t)sizeof(ptl_place_cfg); }
+extern "C" int ptl_place_default_cfg(ptl_place_cfg* cfg) {
+    if (!cfg) return set_err(PTL_ERR_ARG, "ptl_place_default_cfg: cfg is null");
+    ABI_CHECK(ptl_place_cfg, cfg);
+    PTL_CFG_INIT(cfg);
+    cfg->n_ring = 20; cfg->n_sector = 60; cfg->min_radius = 1.0; cfg->max_radius = 80.0; cfg->z_min = -2.0; cfg->z_step = 0.0625;
+    cfg->capacity = 4096; cfg->max_points_per_scan = (int64_t)1 << 20;
+    return PTL_OK;
+}
+static int place_clock(ptl_place* h, double* ms_out) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    *ms_out = ms;
+    return PTL_OK;
+}
+static int place_zero(ptl_place* h) {
+    const size_t slot = (size_t)h->cfg.capacity;
+    HIPCHK(hipMemsetAsync(h->d_desc + slot * h->entry_bytes, 0, h->entry_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_info + slot, 0, sizeof(PlaceInfoDev), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->n_entries = 0;
+    return PTL_OK;
+}
+extern "C" int ptl_place_create(int32_t device_id, const ptl_place_cfg* cfg, ptl_place** out) {
+    if (!cfg || !out) return set_err(PTL_ERR_ARG, "ptl_place_create: null argument");
+    ABI_CHECK(ptl_place_cfg, cfg);
+    const ptl_place_cfg& u = *cfg;
+    if (u.n_ring < 1 || u.n_ring > PLACE_MAX_RING) return set_err(PTL_ERR_ARG, "ptl_place_create: n_ring = %d: must be in 1 .. %d", u.n_ring, PLACE_MAX_RING);
+    if (u.n_sector < 4 || u.n_sector > PLACE_MAX_SECTOR) return set_err(PTL_ERR_ARG, "ptl_place_create: n_sector = %d: must be in 4 .. %d", u.n_sector, PLACE_MAX_SECTOR);
+    if (!(u.max_radius < 1.0e150) || !(u.min_radius > 0.0) || !(u.min_radius < u.max_radius / (double)u.n_ring))
+        return set_err(PTL_ERR_ARG, "ptl_place_create: min_radius = %g, max_radius = %g, n_ring = %d: need 0 < min_radius < max_radius / n_ring = %g, finite",
+                       u.min_radius, u.max_radius, u.n_ring, u.max_radius / (double)u.n_ring);
+    if (!(u.z_step > 0.0) || !(u.z_step < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_place_create: z_step = %g: must be positive and finite", u.z_step);
+    if (!(fabs(u.z_min) < 1.0e150)) return set_err(PTL_ERR_ARG, "ptl_place_create: z_min = %g: must be finite", u.z_min);
+    if (u.capacity < 1 || (int64_t)u.capacity > PLACE_MAX_CAPACITY)
+        return set_err(PTL_ERR_ARG, "ptl_place_create: capacity = %d entries: must be in 1 .. %lld", u.capacity, (long long)PLACE_MAX_CAPACITY);
+    if (u.max_points_per_scan < 1 || u.max_points_per_scan > PLACE_MAX_POINTS)
+        return set_err(PTL_ERR_ARG, "ptl_place_create: max_points_per_scan = %lld: must be in 1 .. %lld", (long long)u.max_points_per_scan, (long long)PLACE_MAX_POINTS);
+    if (device_id < 0) return set_err(PTL_ERR_ARG, "ptl_place_create: device_id = %d: must not be negative", device_id);
+    if (ptl_device_count() <= device_id) return set_err(PTL_ERR_HIP, "no HIP device %d (the HIP backend is the only backend)", device_id);
+    HIPCHK(hipSetDevice(device_id));
+    std::unique_ptr<ptl_place> h(new ptl_place());
+    const int R = u.n_ring, S = u.n_sector;
+    h->device_id = device_id; h->cfg = u; h->Rpad = (R + 3) / 4 * 4; h->RD = h->Rpad / 4; h->entry_bytes = (size_t)S * h->Rpad;
+    h->ring_edge2.resize((size_t)R + 1); h->sector_dir.resize((size_t)2 * S);
+    h->ring_edge2[0] = u.min_radius * u.min_radius;
+    for (int i = 1; i <= R; ++i) { const double e = u.max_radius * (double)i / (double)R; h->ring_edge2[(size_t)i] = e * e; }
+    for (int j = 0; j < S; ++j) {
+        const double t = 2.0 * 3.14159265358979323846 * (double)j / (double)S;
+        h->sector_dir[(size_t)2 * j] = cos(t); h->sector_dir[(size_t)2 * j + 1] = sin(t);
+    }
+    HIPCHK(h->stream.create());
+    HIPCHK(h->e0.create(hipEventDefault)); HIPCHK(h->e1.create(hipEventDefault));
+    const size_t slots = (size_t)u.capacity + 1;
+    h->mem.add(&h->d_tab, (size_t)R + 1 + 2 * (size_t)S);
+    { unsigned char* raw = nullptr; h->mem.add(&raw, (size_t)u.max_points_per_scan * 24); h->d_raw = raw; }
+    h->mem.add(&h->d_grid, h->entry_bytes); h->mem.add(&h->d_counts, (size_t)PLACE_COUNTERS + 1);
+    h->mem.add(&h->d_desc, slots * h->entry_bytes); h->mem.add(&h->d_info, slots);
+    h->mem.add(&h->d_dist, (size_t)u.capacity); h->mem.add(&h->d_shift, (size_t)u.capacity); h->mem.add(&h->d_entry, (size_t)u.capacity);
+    HIPCHK(h->mem.err);
+    HIPCHK(hipMemcpyAsync(h->d_tab, h->ring_edge2.data(), ((size_t)R + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_tab + R + 1, h->sector_dir.data(), (size_t)2 * S * 8, hipMemcpyHostToDevice, h->stream));
+    { int rc = place_zero(h.get()); if (rc) return rc; }
+    *out = h.release();
+    return PTL_OK;
+}
+extern "C" int ptl_place_destroy(ptl_place* p) { return p ? handle_destroy(p, p->device_id) : PTL_OK; }
+extern "C" int ptl_place_clear(ptl_place* p) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_clear: null argument");
+    HIPCHK(hipSetDevice(p->device_id));
+    return place_zero(p);
+}
+extern "C" int ptl_place_size(ptl_place* p, int64_t* n_entries) {
+    if (!p || !n_entries) return set_err(PTL_ERR_ARG, "ptl_place_size: null argument");
+    *n_entries = p->n_entries;
+    return PTL_OK;
+}
+extern "C" int ptl_place_tables(ptl_place* p, double* ring_edge2, double* sector_dir) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_tables: null argument");
+    if (ring_edge2) memcpy(ring_edge2, p->ring_edge2.data(), p->ring_edge2.size() * 8);
+    if (sector_dir) memcpy(sector_dir, p->sector_dir.data(), p->sector_dir.size() * 8);
+    return PTL_OK;
+}
+extern "C" int ptl_place_profile(ptl_place* p, double* describe_ms, int64_t* n_describes, int32_t reset) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_profile: null argument");
+    if (describe_ms) *describe_ms = p->describe_ms;
+    if (n_describes) *n_describes = p->n_describes;
+    if (reset) { p->describe_ms = 0; p->n_describes = 0; }
+    return PTL_OK;
+}
+// one sweep into the query slot, and behind the last entry when kept; mode as k_place_bin's; the arguments have been checked
+static int place_describe(ptl_place* h, const void* raw_host, size_t raw_bytes, int mode, const ptl_lut* lut, int64_t n, const double* rot9,
+                          int32_t keep, int64_t* index, ptl_place_info* info, const char* who) {
+    if (rot9)
+        for (int e = 0; e < 9; ++e)
+            if (!(fabs(rot9[e]) < 1.0e150)) return set_err(PTL_ERR_ARG, "%s: rot9[%d] = %g: every entry must be finite", who, e, rot9[e]);
+    const ptl_place_cfg& u = h->cfg;
+    HIPCHK(hipSetDevice(h->device_id));
+    hipStream_t s = h->stream;
+    PlaceArgs a = {};
+    a.R = u.n_ring; a.S = u.n_sector; a.Rpad = h->Rpad; a.z_min = u.z_min; a.z_step = u.z_step;
+    a.ring_edge2 = h->d_tab; a.sector_dir = h->d_tab + u.n_ring + 1;
+    a.has_rot = rot9 ? 1 : 0;
+    for (int e = 0; e < 9; ++e) a.rot[e] = rot9 ? rot9[e] : 0.0;
+    a.grid = h->d_grid; a.counts = h->d_counts;
+    const size_t slot = (size_t)u.capacity;
+    const int64_t wg = (n + PLACE_THREADS - 1) / PLACE_THREADS;
+    const int blocks = (int)(wg < 1 ? 1 : wg < PLACE_MAX_BLOCKS ? wg : PLACE_MAX_BLOCKS);
+    HIPCHK(hipEventRecord(h->e0, s));
+    if (raw_bytes) HIPCHK(hipMemcpyAsync(h->d_raw, raw_host, raw_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->d_grid, 0, h->entry_bytes * 4, s));
+    HIPCHK(hipMemsetAsync(h->d_counts, 0, (size_t)PLACE_COUNTERS * 8, s));
+    if (mode == 0) k_place_bin<0><<<blocks, PLACE_THREADS, 0, s>>>(h->d_raw, lut->dir, lut->off, (long long)n, a);
+    else if (mode == 1) k_place_bin<1><<<blocks, PLACE_THREADS, 0, s>>>(h->d_raw, nullptr, nullptr, (long long)n, a);
+    else k_place_bin<2><<<blocks, PLACE_THREADS, 0, s>>>(h->d_raw, nullptr, nullptr, (long long)n, a);
+    k_place_pack<<<1, PLACE_THREADS, 0, s>>>(h->d_grid, h->d_counts, (int)h->entry_bytes, (long long)n, h->d_desc + slot * h->entry_bytes, h->d_info + slot);
+    HIPCHK(hipGetLastError());
+    const bool full = keep && h->n_entries >= (int64_t)u.capacity;
+    if (keep && !full) {
+        const size_t at = (size_t)h->n_entries;
+        HIPCHK(hipMemcpyAsync(h->d_desc + at * h->entry_bytes, h->d_desc + slot * h->entry_bytes, h->entry_bytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->d_info + at, h->d_info + slot, sizeof(PlaceInfoDev), hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(hipEventRecord(h->e1, s));
+    ptl_place_info got;
+    HIPCHK(hipMemcpyAsync(&got, h->d_info + slot, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    double ms = 0;
+    { int rc = place_clock(h, &ms); if (rc) return rc; }
+    h->describe_ms += ms; h->n_describes += 1;
+    if (info) *info = got;
+    if (index) *index = -1;
+    if (full)
+        return set_err(PTL_ERR_CAPACITY, "%s: the database holds %lld entries, its capacity is %d: nothing was appended (the query slot holds the descriptor)",
+                       who, (long long)h->n_entries, u.capacity);
+    if (keep) { if (index) *index = h->n_entries; h->n_entries += 1; }
+    return PTL_OK;
+}
+extern "C" int ptl_place_describe_range(ptl_place* p, ptl_lut* lut, const uint32_t* range_mm, const double* rot9, int32_t keep, int64_t* index,
+                                        ptl_place_info* info) {
+    if (!p || !lut || !range_mm) return set_err(PTL_ERR_ARG, "ptl_place_describe_range: null argument");
+    if (lut->device_id != p->device_id) return set_err(PTL_ERR_ARG, "ptl_place_describe_range: LUT on device %d, places on device %d", lut->device_id, p->device_id);
+    const int64_t n = (int64_t)lut->H * lut->W;
+    if (n > p->cfg.max_points_per_scan)
+        return set_err(PTL_ERR_CAPACITY, "ptl_place_describe_range: the sweep has %lld pixels, the handle's max_points_per_scan is %lld", (long long)n,
+                       (long long)p->cfg.max_points_per_scan);
+    return place_describe(p, range_mm, (size_t)n * 4, 0, lut, n, rot9, keep, index, info, "ptl_place_describe_range");
+}
+extern "C" int ptl_place_describe_xyz(ptl_place* p, const void* xyz, int dtype, int64_t n, const double* rot9, int32_t keep, int64_t* index,
+                                      ptl_place_info* info) {
+    if (!p || (!xyz && n > 0)) return set_err(PTL_ERR_ARG, "ptl_place_describe_xyz: null argument");
+    if (dtype != PTL_F32 && dtype != PTL_F64) return set_err(PTL_ERR_ARG, "ptl_place_describe_xyz: dtype = %d: PTL_F32 (%d) or PTL_F64 (%d)", dtype, PTL_F32, PTL_F64);
+    if (n < 0) return set_err(PTL_ERR_ARG, "ptl_place_describe_xyz: n = %lld: must not be negative", (long long)n);
+    if (n > p->cfg.max_points_per_scan)
+        return set_err(PTL_ERR_CAPACITY, "ptl_place_describe_xyz: the sweep has %lld points, the handle's max_points_per_scan is %lld", (long long)n,
+                       (long long)p->cfg.max_points_per_scan);
+    return place_describe(p, xyz, (size_t)n * (dtype == PTL_F32 ? 12 : 24), dtype == PTL_F32 ? 1 : 2, nullptr, n, rot9, keep, index, info,
+                          "ptl_place_describe_xyz");
+}
+// RD = 5 (R = 17 .. 20, the default's) has its own instance of the match kernels, every other RD the general one
+extern "C" int ptl_place_match(ptl_place* p, int64_t query, int64_t first, int64_t last, uint32_t* dist_out, int32_t* shift_out, ptl_place_result* result) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_match: null argument");
+    if (query < -1 || query >= p->n_entries) return set_err(PTL_ERR_ARG, "ptl_place_match: query = %lld: -1 (the query slot) or an entry below %lld", (long long)query, (long long)p->n_entries);
+    const bool empty = last < first;
+    if (!empty && (first < 0 || last >= p->n_entries))
+        return set_err(PTL_ERR_ARG, "ptl_place_match: entries [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)p->n_entries);
+    ptl_place_result res = {};
+    res.best_query = query; res.best_entry = -1;
+    if (!empty) {
+        HIPCHK(hipSetDevice(p->device_id));
+        hipStream_t s = p->stream;
+        const int S = p->cfg.n_sector, RD = p->RD;
+        const int64_t n = last - first + 1, tiles = (n + PLACE_TILE - 1) / PLACE_TILE, wg = (tiles + PLACE_THREADS / 64 - 1) / (PLACE_THREADS / 64);
+        const int blocks = (int)(wg < PLACE_MAX_BLOCKS ? wg : PLACE_MAX_BLOCKS);
+        const size_t lds = (size_t)2 * S * (RD | 1) * 4;
+        const unsigned* desc = (const unsigned*)p->d_desc;
+        const unsigned* q = (const unsigned*)(p->d_desc + (size_t)(query < 0 ? (int64_t)p->cfg.capacity : query) * p->entry_bytes);
+        unsigned long long* d_best = p->d_counts + PLACE_COUNTERS;
+        unsigned long long best = PLACE_KEY_NONE;
+        HIPCHK(hipEventRecord(p->e0, s));
+        HIPCHK(hipMemsetAsync(d_best, 0xff, 8, s));
+        if (RD == 5) k_place_match<5><<<blocks, PLACE_THREADS, lds, s>>>(desc, q, S, RD, (int)first, (int)last, p->d_dist, p->d_shift, d_best);
+        else k_place_match<0><<<blocks, PLACE_THREADS, lds, s>>>(desc, q, S, RD, (int)first, (int)last, p->d_dist, p->d_shift, d_best);
+        HIPCHK(hipEventRecord(p->e1, s));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, s));
+        if (dist_out) HIPCHK(hipMemcpyAsync(dist_out, p->d_dist, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (shift_out) HIPCHK(hipMemcpyAsync(shift_out, p->d_shift, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        { int rc = place_clock(p, &res.device_ms); if (rc) return rc; }
+        res.n_compared = n;
+        res.best_dist = (uint32_t)(best >> 26); res.best_entry = (int64_t)((best >> 6) & 0xfffffu); res.best_shift = (int32_t)(best & 63u);
+    }
+    if (result) *result = res;
+    return PTL_OK;
+}
+extern "C" int ptl_place_match_all(ptl_place* p, int64_t q_first, int64_t q_last, int64_t min_gap, int32_t* entry_out, uint32_t* dist_out,
+                                   int32_t* shift_out, ptl_place_result* result) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_match_all: null argument");
+    if (min_gap < 0) return set_err(PTL_ERR_ARG, "ptl_place_match_all: min_gap = %lld: must not be negative", (long long)min_gap);
+    const bool empty = q_last < q_first;
+    if (!empty && (q_first < 0 || q_last >= p->n_entries))
+        return set_err(PTL_ERR_ARG, "ptl_place_match_all: queries [%lld, %lld] of %lld entries", (long long)q_first, (long long)q_last, (long long)p->n_entries);
+    ptl_place_result res = {};
+    res.best_query = -1; res.best_entry = -1;
+    if (!empty) {
+        HIPCHK(hipSetDevice(p->device_id));
+        hipStream_t s = p->stream;
+        const int S = p->cfg.n_sector, RD = p->RD;
+        const int64_t n = q_last - q_first + 1;
+        const int gap = (int)(min_gap < PLACE_MAX_CAPACITY ? min_gap : PLACE_MAX_CAPACITY);  // (beyond the capacity no entry qualifies either)
+        const int blocks = (int)((n + PLACE_THREADS / 64 - 1) / (PLACE_THREADS / 64));
+        const size_t lds = (size_t)(PLACE_THREADS / 64) * 2 * S * (RD | 1) * 4;
+        const unsigned* desc = (const unsigned*)p->d_desc;
+        unsigned long long* d_best = p->d_counts + PLACE_COUNTERS;
+        unsigned long long best = PLACE_KEY_NONE;
+        HIPCHK(hipEventRecord(p->e0, s));
+        HIPCHK(hipMemsetAsync(d_best, 0xff, 8, s));
+        if (RD == 5) k_place_match_all<5><<<blocks, PLACE_THREADS, lds, s>>>(desc, S, RD, (int)q_first, (int)q_last, gap, p->d_entry, p->d_dist, p->d_shift, d_best);
+        else k_place_match_all<0><<<blocks, PLACE_THREADS, lds, s>>>(desc, S, RD, (int)q_first, (int)q_last, gap, p->d_entry, p->d_dist, p->d_shift, d_best);
+        HIPCHK(hipEventRecord(p->e1, s));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, s));
+        if (entry_out) HIPCHK(hipMemcpyAsync(entry_out, p->d_entry, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (dist_out) HIPCHK(hipMemcpyAsync(dist_out, p->d_dist, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (shift_out) HIPCHK(hipMemcpyAsync(shift_out, p->d_shift, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        { int rc = place_clock(p, &res.device_ms); if (rc) return rc; }
+        for (int64_t i = q_first; i <= q_last; ++i) res.n_compared += i - min_gap >= 0 ? i - min_gap + 1 : 0;
+        if (best != PLACE_KEY_NONE) {
+            const int64_t qi = (int64_t)(best & 0xfffffu);
+            int32_t sh = 0;
+            HIPCHK(hipMemcpy(&sh, p->d_shift + qi, 4, hipMemcpyDeviceToHost));
+            res.best_query = q_first + qi; res.best_entry = (int64_t)((best >> 20) & 0xfffffu); res.best_dist = (uint32_t)(best >> 40); res.best_shift = sh;
+        }
+    }
+    if (result) *result = res;
+    return PTL_OK;
+}
+extern "C" int ptl_place_read(ptl_place* p, int64_t first, int64_t last, uint8_t* desc_out, ptl_place_info* info_out) {
+    if (!p) return set_err(PTL_ERR_ARG, "ptl_place_read: null argument");
+    if (last < first) return PTL_OK;
+    if (first < 0 || last >= p->n_entries) return set_err(PTL_ERR_ARG, "ptl_place_read: entries [%lld, %lld] of %lld", (long long)first, (long long)last, (long long)p->n_entries);
+    HIPCHK(hipSetDevice(p->device_id));
+    const size_t n = (size_t)(last - first + 1);
+    if (desc_out) HIPCHK(hipMemcpy(desc_out, p->d_desc + (size_t)first * p->entry_bytes, n * p->entry_bytes, hipMemcpyDeviceToHost));
+    if (info_out) HIPCHK(hipMemcpy(info_out, p->d_info + first, n * sizeof(ptl_place_info), hipMemcpyDeviceToHost));
+    return PTL_OK;
+}
+extern "C" int ptl_place_load(ptl_place* p, int64_t n, const uint8_t* desc, const ptl_place_info* info) {
+    if (!p || n < 0 || (n > 0 && (!desc || !info))) return set_err(PTL_ERR_ARG, "ptl_place_load: null argument or n = %lld below zero", (long long)n);
+    if (p->n_entries + n > (int64_t)p->cfg.capacity)
+        return set_err(PTL_ERR_CAPACITY, "ptl_place_load: %lld entries + %lld to load are above the capacity of %d: nothing was appended", (long long)p->n_entries,
+                       (long long)n, p->cfg.capacity);
+    const int R = p->cfg.n_ring, S = p->cfg.n_sector;
+    for (int64_t k = 0; k < n && R < p->Rpad; ++k)
+        for (int j = 0; j < S; ++j)
+            for (int r = R; r < p->Rpad; ++r)
+                if (desc[(size_t)k * p->entry_bytes + (size_t)j * p->Rpad + r])
+                    return set_err(PTL_ERR_ARG, "ptl_place_load: entry %lld, sector %d, byte %d = %u: a pad byte (ring >= %d) must be 0; nothing was appended",
+                                   (long long)k, j, r, (unsigned)desc[(size_t)k * p->entry_bytes + (size_t)j * p->Rpad + r], R);
+    if (n == 0) return PTL_OK;
+    HIPCHK(hipSetDevice(p->device_id));
+    HIPCHK(hipMemcpy(p->d_desc + (size_t)p->n_entries * p->entry_bytes, desc, (size_t)n * p->entry_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_info + p->n_entries, info, (size_t)n * sizeof(ptl_place_info), hipMemcpyHostToDevice));
+    p->n_entries += n;
     return PTL_OK;
 }
 

@@ -562,6 +562,241 @@ class MapLocalizer:
         return Localization(pose, hits, len(q), fraction, -1, -1, int(it))
 
 
+# ------------------------------------------------------------------------------------------------ revisited places
+def thin_sweep(points, voxel, device_id=0):
+    """`MapLocalizer.query`'s thinning as a function (that class is left as it is): the first point per voxel of side `voxel` of a sweep's
+    returns, sorted by (x, y, z)"""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    p = p[np.isfinite(p).all(axis=1) & (p != 0.0).any(axis=1)]
+    if not len(p):
+        return p
+    scratch = core.map_from_points(p, voxel_size=voxel, max_points_per_voxel=1, device_id=device_id, max_points_per_scan=max(len(p), 1024),
+                                   map_block_capacity=max(len(p), 1024), map_table_capacity=1 << max(12, int(4 * len(p) - 1).bit_length()))
+    try:
+        out = scratch.map_points()
+        return np.ascontiguousarray(out[np.lexsort(out.T[::-1])])
+    finally:
+        scratch.close()
+
+
+def place_candidates(dist, shift, poses, n_sector, place_top, first=0):
+    """Start poses out of a `PlaceIndex.match`: the `place_top` entries with the smallest distance (ties to the smaller index), each at
+    pose_entry @ Rz(-2 pi shift / n_sector) - the rigid guess that takes the query's coordinates through the entry's frame into the world.
+    Returns (poses (K, 4, 4), entries (K,))"""
+    d = np.asarray(dist).reshape(-1).astype(np.int64)
+    s = np.asarray(shift).reshape(-1)
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if int(place_top) < 1:
+        raise ValueError(f"place_top = {place_top}: at least one place is tried")
+    if first + len(d) > len(P):
+        raise ValueError(f"{len(d)} matched entries from {first} on, {len(P)} poses")
+    order = np.lexsort((np.arange(len(d)), d))[:int(place_top)]
+    out = np.array([P[first + c] @ core.place_shift_pose(int(s[c]), n_sector) for c in order]).reshape(-1, 4, 4)
+    return out, first + order.astype(np.int64)
+
+
+def loop_candidates(entry, dist, shift, n_cells, max_cell_dist, top, first=0):
+    """Host policy on a `PlaceIndex.match_all`: the pairs (i, j = entry[i - first]) with cell_dist = dist / (n_cells[i] + n_cells[j]) <=
+    max_cell_dist, the `top` smallest of them (ties to the smaller i).  n_cells: per ENTRY of the index.  A pair without a non-zero cell
+    never qualifies.  Returns [(i, j, shift, dist, cell_dist)]"""
+    out = []
+    nc = np.asarray(n_cells).reshape(-1).astype(np.int64)
+    for k, j in enumerate(np.asarray(entry).reshape(-1)):
+        i = first + k
+        cells = int(nc[i] + nc[j]) if j >= 0 else 0
+        if j < 0 or cells == 0:
+            continue
+        cd = int(dist[k]) / cells
+        if cd <= max_cell_dist:
+            out.append((i, int(j), int(shift[k]), int(dist[k]), cd))
+    out.sort(key=lambda r: (r[4], r[0]))
+    return out[:max(int(top), 0)]
+
+
+def _rot_deg(R):
+    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0))))
+
+
+@dataclass
+class Loop:
+    """One revisit found by `LoopFinder.find`: sweep i saw the place of the earlier sweep j (keyframe numbers).  shift, dist: the descriptors'
+    exact match; cell_dist = dist / (n_cells_i + n_cells_j); T_ji_measured: sweep i's coordinates in sweep j's frame as `Icp.align` of i's
+    points on j's gives it from Rz(-2 pi shift / S); fraction: i's points within the hit threshold of j's there; T_ji_odometry =
+    inv(pose_j) pose_i; dt_m / drot_deg: the size of inv(T_ji_odometry) T_ji_measured - what the odometry is off by at this pair; accepted:
+    fraction >= min_fraction"""
+    i: int
+    j: int
+    shift: int
+    dist: int
+    cell_dist: float
+    fraction: float
+    T_ji_measured: np.ndarray
+    T_ji_odometry: np.ndarray
+    dt_m: float
+    drot_deg: float
+    accepted: bool = True
+
+
+def loop_from(i, j, shift, dist, cell_dist, fraction, T_meas, pose_i, pose_j, min_fraction):
+    """the `Loop` of a verified pair: the odometry's relative pose and its discrepancy against the measured one"""
+    T_odo = np.linalg.inv(pose_j) @ pose_i
+    D = np.linalg.inv(T_odo) @ T_meas
+    return Loop(int(i), int(j), int(shift), int(dist), float(cell_dist), float(fraction), np.asarray(T_meas), T_odo,
+                float(np.linalg.norm(D[:3, 3])), _rot_deg(D[:3, :3]), bool(fraction >= min_fraction))
+
+
+class LoopFinder:
+    """Loops within a run: a `core.PlaceIndex` of the keyframe sweeps and HOST POLICY on its exact integers.  Every default
+    here is UNTUNED - nobody has run this on a real recording: `spacing` metres of travel between described sweeps (the thinning rule of
+    `candidate_poses`), `query_voxel` of the points kept per keyframe (`thin_sweep`), `map_voxel` of the scratch map a pair is verified in.
+    lut: needed for scans that carry a range image.  index: an existing PlaceIndex, else one is made from **place_cfg and closed with this"""
+
+    def __init__(self, index=None, spacing=2.0, query_voxel=1.0, map_voxel=1.0, sigma=None, lut=None, device_id=0, **place_cfg):
+        if not spacing >= 0.0:
+            raise ValueError(f"spacing = {spacing}: must not be negative")
+        if not query_voxel > 0.0 or not map_voxel > 0.0:
+            raise ValueError(f"query_voxel = {query_voxel}, map_voxel = {map_voxel}: must be positive")
+        self._own = index is None
+        self.index = core.PlaceIndex(device_id=device_id, **place_cfg) if index is None else index
+        self.spacing, self.query_voxel, self.map_voxel, self.sigma = float(spacing), float(query_voxel), float(map_voxel), sigma
+        self.lut, self.device_id = lut, int(device_id)
+        self.points, self.poses, self.stamps, self.infos = [], [], [], []
+        self._last, self._since = None, 0.0
+        self.match_ms = self.verify_ms = 0.0  # device time of match_all / wall time of the verifications
+
+    def close(self):
+        if self._own and self.index is not None:
+            self.index.close()
+        self.index = None
+
+    def add(self, scan_or_points, pose, stamp):
+        """the next sweep of the run at its odometry pose (4x4, world <- sensor).  Described and kept when the path length since the last kept
+        sweep has reached `spacing` (the first always is).  scan_or_points: (N, 3) sensor-frame points, or a scan with a range image
+        (range_mm / range; needs lut).  Returns the keyframe number, or -1 for a sweep passed over"""
+        P = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+        if self._last is not None:
+            self._since += float(np.linalg.norm(P[:3, 3] - self._last[:3, 3]))
+        keep = self._last is None or not self.spacing or self._since >= self.spacing
+        self._last = P
+        if not keep:
+            return -1
+        self._since = 0.0
+        if hasattr(scan_or_points, "range_mm") or hasattr(scan_or_points, "range"):
+            if self.lut is None:
+                raise ValueError("a scan with a range image needs the LoopFinder's lut")
+            rng = scan_or_points.range_mm if hasattr(scan_or_points, "range_mm") else scan_or_points.range
+            k, info = self.index.describe((self.lut, rng), keep=True)
+            xyz = self.lut(rng)
+        else:
+            xyz = np.asarray(scan_or_points)
+            k, info = self.index.describe(xyz, keep=True)
+        self.points.append(thin_sweep(xyz, self.query_voxel, self.device_id))
+        self.poses.append(P.copy()); self.stamps.append(float(stamp)); self.infos.append(info.as_dict())
+        return k
+
+    def verify(self, i, j, shift):
+        """(T_ji_measured, fraction): `Icp.align` of keyframe i's points on a scratch map of keyframe j's from Rz(-2 pi shift / S), and the
+        share of i's points within the map's voxel size of a stored point there"""
+        m = core.map_from_points(self.points[j], voxel_size=self.map_voxel, device_id=self.device_id,
+                                 max_points_per_scan=max(len(self.points[j]), len(self.points[i]), 1024))
+        try:
+            sigma = float(m.cfg.initial_threshold if self.sigma is None else self.sigma)
+            q = self.points[i]
+            T, _ = m.align(q, core.place_shift_pose(shift, self.index.n_sector), 3.0 * sigma, sigma / 3.0)
+            _, hits = m.pose_hits(q, T[None])
+            return T, (int(hits[0, -1]) / len(q) if len(q) and hits[0, -1] >= 0 else 0.0)
+        finally:
+            m.close()
+
+    def find(self, min_gap=50, max_cell_dist=20.0, top=16, min_fraction=0.5):
+        """`match_all` over the keyframes, `loop_candidates`, each kept pair verified: the list of `Loop`s, best cell_dist first, accepted
+        or not (`Loop.accepted`).  min_gap: in KEYFRAMES"""
+        import time
+        if not len(self.points):
+            return []
+        r = self.index.match_all(int(min_gap))
+        self.match_ms += r.device_ms
+        pairs = loop_candidates(r.entry, r.dist, r.shift, [f["n_cells"] for f in self.infos], max_cell_dist, top)
+        t0 = time.perf_counter()
+        out = []
+        for i, j, s, d, cd in pairs:
+            if not len(self.points[i]) or not len(self.points[j]):
+                continue
+            T, fraction = self.verify(i, j, s)
+            out.append(loop_from(i, j, s, d, cd, fraction, T, self.poses[i], self.poses[j], min_fraction))
+        self.verify_ms += 1000.0 * (time.perf_counter() - t0)
+        return out
+
+
+def loop_lines(loops):
+    """the block `ekf-bench --find-loops` prints: the accepted loops and the odometry's discrepancy at each"""
+    acc = [l for l in loops if l.accepted]
+    lines = [f"loops: {len(acc)} accepted of {len(loops)} verified (every threshold is the caller's and untuned)"]
+    for l in acc:
+        lines.append(f"  keyframe {l.i} revisits {l.j}: shift {l.shift}, dist {l.dist} ({l.cell_dist:.2f} per cell), fraction {l.fraction:.3f}, "
+                     f"odometry off by {l.dt_m:.3f} m, {l.drot_deg:.2f} deg")
+    return lines
+
+
+def save_loops_csv(path, loops, stamps=None):
+    """one row per verified loop: i, j, [stamp_i, stamp_j,] shift, dist, cell_dist, fraction, accepted, dt_m, drot_deg, then T_ji_measured's
+    top three rows"""
+    with open(path, "w") as f:
+        f.write("i,j," + ("stamp_i,stamp_j," if stamps is not None else "") + "shift,dist,cell_dist,fraction,accepted,dt_m,drot_deg," +
+                ",".join(f"T{r}{c}" for r in range(3) for c in range(4)) + "\n")
+        for l in loops:
+            st = f"{stamps[l.i]!r},{stamps[l.j]!r}," if stamps is not None else ""
+            f.write(f"{l.i},{l.j},{st}{l.shift},{l.dist},{l.cell_dist!r},{l.fraction!r},{int(l.accepted)},{l.dt_m!r},{l.drot_deg!r}," +
+                    ",".join(repr(float(v)) for v in l.T_ji_measured[:3].reshape(-1)) + "\n")
+
+
+class PlaceLocalizer(MapLocalizer):
+    """`MapLocalizer` whose start poses come from places: the sweep is described, compared with every entry of a loaded
+    places file at every heading, and the `place_top` best entries - each at pose_entry @ Rz(-2 pi shift / S) - are the candidates of
+    `locate`, instead of keyframes x yaws.  Scoring, refinement, rescoring and `track` are MapLocalizer's.  place_top is UNTUNED.
+    places: the path of a file `utils.save_places` wrote, or its loaded dict.  index: a PlaceIndex to load it into (default: one of the
+    file's parameters, closed with this object)"""
+
+    def __init__(self, map, places, place_top=4, index=None, device_id=0, **kw):
+        from .utils import load_places
+        if int(place_top) < 1:
+            raise ValueError(f"place_top = {place_top}: at least one place is tried")
+        data = load_places(places) if isinstance(places, str) else places
+        if not len(data["poses"]):
+            raise ValueError("the places file holds no entry: nothing to search from")
+        self._own_index = index is None
+        if index is None:
+            index = core.PlaceIndex(device_id=device_id, capacity=max(len(data["desc"]), 1), **data["cfg"])
+        self.index = index
+        try:
+            have = index.tables()
+            if not (np.array_equal(have[0], data["ring_edge2"]) and np.array_equal(have[1], data["sector_dir"])):
+                raise ValueError("the places file's tables differ from the handle's: its descriptors do not compare bit for bit")
+            self.first = len(index)
+            index.load(data["desc"], data["infos"])
+            self.place_poses, self.place_top = np.asarray(data["poses"], dtype=np.float64).reshape(-1, 4, 4), int(place_top)
+            self.places_tried = None     # the entries behind the last search's candidates
+            self.place_ms = 0.0          # device time of the matches
+            super().__init__(map, self.place_poses, n_yaw=1, **kw)
+        except Exception:
+            if self._own_index:
+                index.close()
+            raise
+
+    def close(self):
+        super().close()
+        if self._own_index and self.index is not None:
+            self.index.close()
+        self.index = None
+
+    def locate(self, points, query=None):
+        self.index.describe(points, keep=False)
+        m = self.index.match(-1, self.first, self.first + len(self.place_poses) - 1)
+        self.place_ms += m.device_ms
+        self.candidates, self.places_tried = place_candidates(m.dist, m.shift, self.place_poses, self.index.n_sector, self.place_top)
+        return super().locate(points, query)
+
+
 # ------------------------------------------------------------------------------------------------ the camera path (DESIGN.md 3.21)
 class FlyingState(Enum):
     """Camera movement states (reference fly.py:19-24)"""
@@ -898,6 +1133,22 @@ def grid_packet_bag(builder, bags, info, traj, start_scan=0, end_scan=None, devi
         for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
             if not hasattr(d, "lacc"):
                 builder.update(d, traj)
+    finally:
+        feed.close()
+
+
+def loops_packet_bag(finder, bags, info, stamps, poses, start_scan=0, end_scan=None, device_id=0):
+    """the counterpart of `add_packet_bag` for a `LoopFinder` (which needs its lut): sweep k of the same bag(s), decoded by the package's packet
+    feed, at the k-th of `poses` / `stamps`; sweeps beyond the poses are left out"""
+    from . import packets as pk
+    from .bag import OusterPacketBagSource
+    feed = pk.PacketFeed(OusterPacketBagSource(bags, info), info, device_id=device_id)
+    try:
+        k = 0
+        for _, d in feed.withScanIdx(start_scan=start_scan, end_scan=end_scan):
+            if not hasattr(d, "lacc") and k < len(poses):
+                finder.add(d, poses[k], stamps[k])
+                k += 1
     finally:
         feed.close()
 

@@ -611,3 +611,52 @@ def nc_gt_file_rows(t, poses) -> List[Tuple[float, np.ndarray]]:
     save_poses_nc_gt_format(buf, t=t, poses=poses)
     buf.seek(0)
     return read_newer_college_gt(buf)
+
+
+# ------------------------------------------------------------------------------------------------ places files
+PLACE_CFG_KEYS = ("n_ring", "n_sector", "min_radius", "max_radius", "z_min", "z_step")
+
+
+def _place_cfg_row(index) -> np.ndarray:
+    return np.array([float(getattr(index.cfg, k)) for k in PLACE_CFG_KEYS])
+
+
+def save_places(path: str, index, poses, stamps) -> None:
+    """The entries of a `core.PlaceIndex` with the pose and stamp of the sweep behind each, as one .npz: cfg (the six parameters of
+    PLACE_CFG_KEYS, float64), ring_edge2, sector_dir (the tables as the device uses them), desc (n, S, Rpad) uint8, infos (n, 9) int64, poses
+    (n, 4, 4), stamps (n,).  `index` needs .cfg, .tables() and .descriptors() - nothing else is asked of it"""
+    desc, infos = index.descriptors()
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    t = np.asarray(stamps, dtype=np.float64).reshape(-1)
+    if len(P) != len(desc) or len(t) != len(desc):
+        raise ValueError(f"save_places: {len(desc)} entries with {len(P)} poses and {len(t)} stamps")
+    edge2, sdir = index.tables()
+    with open(path, "wb") as f:  # (np.savez appends .npz to a bare name: the file is called what the caller said)
+        np.savez(f, cfg=_place_cfg_row(index), ring_edge2=np.asarray(edge2), sector_dir=np.asarray(sdir), desc=desc, infos=infos, poses=P, stamps=t)
+
+
+def load_places(path: str, index=None) -> dict:
+    """The arrays of a file `save_places` wrote, as a dict (cfg is a dict of PLACE_CFG_KEYS).  With `index` the entries are APPENDED to it
+    (`index.load`) - after the file's cfg and tables have been held against the handle's: any difference is a ValueError that names it, since
+    descriptors binned by other tables do not compare"""
+    with np.load(path) as z:
+        missing = [k for k in ("cfg", "ring_edge2", "sector_dir", "desc", "infos", "poses", "stamps") if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not a places file (no {', '.join(missing)})")
+        out = {k: z[k] for k in z.files}
+    n = len(out["desc"])
+    if out["desc"].ndim != 3 or out["infos"].shape != (n, 9) or out["poses"].shape != (n, 4, 4) or out["stamps"].shape != (n,):
+        raise ValueError(f"{path}: {n} descriptors with infos {out['infos'].shape}, poses {out['poses'].shape}, stamps {out['stamps'].shape}")
+    if index is not None:
+        have = _place_cfg_row(index)
+        for k, a, b in zip(PLACE_CFG_KEYS, out["cfg"], have):
+            if a != b:
+                raise ValueError(f"{path}: {k} = {a:g} in the file, {b:g} in the handle: descriptors of other parameters do not compare")
+        edge2, sdir = index.tables()
+        for name, a, b in (("ring_edge2", out["ring_edge2"], edge2), ("sector_dir", out["sector_dir"], sdir)):
+            if a.shape != np.shape(b) or not np.array_equal(a, b):
+                raise ValueError(f"{path}: the table {name} differs from the handle's (another libm made it): the descriptors were binned "
+                                 "by other edges and do not compare bit for bit")
+        index.load(out["desc"], out["infos"])
+    out["cfg"] = {k: (int(v) if k in ("n_ring", "n_sector") else float(v)) for k, v in zip(PLACE_CFG_KEYS, out["cfg"])}
+    return out
